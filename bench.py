@@ -11,9 +11,12 @@ GU encoder (+ covariance branch) -> BEV head + ego-motion vote -> consistency lo
 residual, ICP) -> backward -> Adam step.  Raw points are resident in HBM before the timed region.
 N > 1: pure data parallel (each rank its own frame pairs, weak scaling), DDP gradient all-reduce over RCCL.
 
-Prints ONE JSON line (rank 0).  `roofline` describes the dominant hand-written kernel (the sparse-conv
-implicit GEMM): algorithmic bytes (SURVEY.md 8d formula) / HIP-event time per launch, measured live in the
-timed region.  `cpu_baseline` is the same path on the host cores over the oracle backend, on a bounded sample.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and prints the line; `roofline` and
+`cpu_baseline` are then null.  --full adds everything else: `roofline` describes the dominant hand-written kernel (the
+sparse-conv implicit GEMM): algorithmic bytes (SURVEY.md 8d formula) / HIP-event time per launch, measured live in the
+last timed steps; `cpu_baseline` is the same path on the host cores over the oracle backend, on a bounded sample; the
+train-stream split, the multi-rank path child and the other BASELINE configs run after the timed region.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -92,6 +95,12 @@ def parse():
                          "non-GPU test of `--gpus N` runs (no kernels, value is not a measurement)")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"],
                     help="f32 = C3 (the headline line); bf16 = the single-GPU half of C4: apex.amp O1, bf16 conv operands")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: launch-probe roofline, train-stream split, CPU baseline, "
+                         "multi-rank path child, the other BASELINE configs (c2 / c4 / c5); a plain run only times its steps")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed to DIR/<name>.npy (float32 / float64; "
+                         "arrays past a per-array budget as a fixed seeded sample, 64 MB in all)")
     args = ap.parse_args()
     if args.config is None:
         args.config = "c4" if args.dtype == "bf16" else "c3"
@@ -153,6 +162,39 @@ def _flush_c_stdio():
         ctypes.CDLL(None).fflush(None)
     except OSError:
         pass
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: arrays = [(name, tensor)] of what the last timed step computed -> out_dir/<name>.npy, float64 tensors
+    as float64, every other one as float32.  Each array gets an equal share of DUMP_BYTES; a larger one is stored as a fixed
+    seeded sample of its flattened elements (the same indices for the same shape, so two builds compare element for
+    element).  Call after the stream is drained, before anything runs another step."""
+    arrays = [(n, t) for n, t in arrays if t is not None and t.numel() > 0]
+    if not arrays:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    budget = DUMP_BYTES // 8 // len(arrays)          # elements per array at 8 bytes each: the total stays within DUMP_BYTES
+    for name, t in arrays:
+        flat = t.detach().reshape(-1)
+        if flat.numel() > budget:
+            idx = np.sort(np.random.default_rng(0).choice(flat.numel(), budget, replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a.reshape(t.shape) if a.size == t.numel() else a)
+
+
+def _named_tensors(obj, prefix):
+    """Every tensor of a nested dict / list / tuple as (dotted name, tensor)."""
+    if isinstance(obj, torch.Tensor):
+        return [(prefix, obj)]
+    if isinstance(obj, dict):
+        return [nt for k in sorted(obj) for nt in _named_tensors(obj[k], "%s.%s" % (prefix, k) if prefix else str(k))]
+    if isinstance(obj, (list, tuple)):
+        return [nt for i, v in enumerate(obj) for nt in _named_tensors(v, "%s.%d" % (prefix, i))]
+    return []
 
 
 PMC_TRAFFIC = "r06_pmc_traffic_bench.json"
@@ -661,7 +703,7 @@ def run_encoder(args, world, rank, local_rank, dist_on, dev):
 
     probe = ConvProbe(capi)
     probe.pmc_workload_ok = False
-    use_probe = (not args.no_kernel_events) and rank == 0
+    use_probe = args.full and (not args.no_kernel_events) and rank == 0
     if use_probe:
         probe.install()
     for _ in range(args.warmup):
@@ -680,12 +722,14 @@ def run_encoder(args, world, rank, local_rank, dist_on, dev):
     for i in range(args.steps):
         if use_probe and runner is None and i == args.steps - probe_steps:
             probe.enabled = probe.keep_tables = True
-        step()
+        last = step()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [("bev", last)])      # the step's result, before a later pass recycles its buffer
     st_ = dict(runner.stats) if runner is not None else None
     graph_extras = {}
-    if runner is not None:
+    if args.full and runner is not None:
         # the same scans through the same modules issued EAGERLY (what the graph replays): the launch probe's per-kernel numbers
         # come from these passes, and their time is what the graph is compared with
         eager_pass[0] = True
@@ -736,7 +780,7 @@ def run_encoder(args, world, rank, local_rank, dist_on, dev):
         mult = 3.0 if backward else 1.0
         ms = 1e3 * elapsed / args.steps
         extras = {}
-        if cfg == "c2":       # the same pass on rulebooks planned once, eager and replayed from one hipGraph
+        if args.full and cfg == "c2":       # the same pass on rulebooks planned once, eager and replayed from one hipGraph
             def planned():
                 return enc(feats, coords, frames, plan=plan)[0]
             with torch.no_grad():
@@ -807,7 +851,7 @@ def run_encoder(args, world, rank, local_rank, dist_on, dev):
                             "ms_per_step_max": round(1e3 * max(per_rank) / args.steps, 3)}
         if prefetch is not None:
             prefetch.close()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = encoder_cpu_baseline(args)
             except Exception as e:
@@ -884,7 +928,7 @@ def other_configs(args, affinity=None):
         t0 = time.time()
         try:
             env = dict(os.environ, RSLO_BENCH_OTHER_CONFIGS="0", RSLO_BENCH_MULTIRANK_CHILD="0", RSLO_BENCH_STREAM_SPLIT="0")
-            cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg] + extra
+            cmd = [sys.executable, os.path.abspath(__file__), "--config", cfg, "--full"] + extra
             # (the parent is pinned to 8 cores; a child starts from the host's whole mask -- it pins its own GPU run, and its
             # CPU baseline uses every core, like the headline line's)
             pre = (lambda a=set(affinity): os.sched_setaffinity(0, a)) if affinity else None
@@ -1078,10 +1122,16 @@ def main():
     # RSLO_BENCH_BATCHES distinct resident batches (default 3), used round-robin: consecutive steps voxelize and plan
     # DIFFERENT scans (different voxel counts, tables, pair lists), not one cache-warm batch over and over
     n_sets = max(1, int(os.environ.get("RSLO_BENCH_BATCHES", "3")))
-    cloud_sets = []
-    for k in range(n_sets):
-        cs = workload.kitti_pairs(args.batch, n_el=args.rings, start=(rank * n_sets + k) * args.batch)
-        cloud_sets.append([[torch.from_numpy(c).to(dev) for c in pair] for pair in cs])
+    # every frame pair is seeded numpy work of its own (~1 s per scan): drawn on a thread pool (numpy's array operations
+    # release the interpreter lock), the same arrays as workload.kitti_pairs(batch, start=...) per set
+    from concurrent.futures import ThreadPoolExecutor
+    first = rank * n_sets * args.batch
+    n_threads = min(8, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else 4)
+    with ThreadPoolExecutor(max(1, n_threads)) as pool:
+        pairs = list(pool.map(lambda i: workload.kitti_pairs(1, n_el=args.rings, start=i)[0],
+                              range(first, first + n_sets * args.batch)))
+    cloud_sets = [[[torch.from_numpy(c).to(dev) for c in pair] for pair in pairs[k * args.batch:(k + 1) * args.batch]]
+                  for k in range(n_sets)]
     clouds = cloud_sets[0]
     submitted = [0]
 
@@ -1175,7 +1225,7 @@ def main():
         torch.cuda.set_stream(train_stream)
 
     probe = ConvProbe(capi)
-    use_probe = (not args.no_kernel_events) and rank == 0
+    use_probe = args.full and (not args.no_kernel_events) and rank == 0
     if use_probe:
         probe.install()
 
@@ -1221,6 +1271,14 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     probe.enabled = False
+    if args.dump_outputs and rank == 0:
+        # what the caller of the step receives (the network's outputs) and what the step left in the model (the last
+        # backward's gradients, the parameters after the optimizer step), before any later step can recycle a buffer
+        named = [(n_, p_) for n_, p_ in net.named_parameters() if p_.requires_grad]
+        grads = [p_.grad.reshape(-1) for _, p_ in named if p_.grad is not None]
+        dump_outputs(args.dump_outputs, _named_tensors(ret, "out") + [
+            ("param_grads", torch.cat(grads) if grads else None),
+            ("params_after_step", torch.cat([p_.detach().reshape(-1) for _, p_ in named]))])
     per_rank = [elapsed]
     if dist_on:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
@@ -1302,7 +1360,7 @@ def main():
     # Where the training stream's time goes, from HIP events alone (rslo_amd/streamprobe.py): extra steps AFTER the timed
     # region, every launching library call and every explicit stream join bracketed by events on its stream
     stream_split = None
-    if world == 1 and not dist_on and not args.no_kernel_events and os.environ.get("RSLO_BENCH_STREAM_SPLIT", "1") != "0":
+    if args.full and world == 1 and not dist_on and not args.no_kernel_events and os.environ.get("RSLO_BENCH_STREAM_SPLIT", "1") != "0":
         from rslo_amd import streamprobe
         n_split = 3
         tstream = torch.cuda.current_stream(dev)
@@ -1432,7 +1490,8 @@ def main():
                             # topology lines
                             "grad_exchange_exposed_ms_per_step": gx_exposed, "syncbn_wait_us": peer_waits,
                             "syncbn_transport_per_rank": transports, "topology_lines": topo}
-        if world == 1 and not dist_on and os.environ.get("RSLO_BENCH_MULTIRANK_CHILD", "1") != "0" and not args.no_kernel_events:
+        if args.full and world == 1 and not dist_on and os.environ.get("RSLO_BENCH_MULTIRANK_CHILD", "1") != "0" \
+                and not args.no_kernel_events:
             # The step a rank of an N > 1 job really runs, measured on this one GPU: a child process with a ONE-rank RCCL
             # group and the multi-rank code path forced (RSLO_FORCE_SYNCBN_PATH=1: SyncBN statistics meet the "peers" through
             # a world-size-1 peer comm, gradient buckets go through the overlapped RCCL exchange).  What it cannot show is
@@ -1474,14 +1533,14 @@ def main():
                             line["config"]["multirank_path"]["two_cores_per_rank"] = {"error": repr(e)[:400]}
             except Exception as e:
                 line["config"]["multirank_path"] = dict(line["config"].get("multirank_path") or {}, error=repr(e))
-        if (world == 1 and not dist_on and args.config == "c3" and args.batch == 4 and args.rings == 64
-                and not args.no_cpu_baseline and not args.no_kernel_events      # (the plain default invocation only)
+        if (args.full and world == 1 and not dist_on and args.config == "c3" and args.batch == 4 and args.rings == 64
+                and not args.no_cpu_baseline and not args.no_kernel_events      # (the default invocation with --full only)
                 and os.environ.get("RSLO_BENCH_OTHER_CONFIGS", "1") != "0"):
             # BASELINE.json configs[1], [3] (per-GPU part) and [4] measured by the SAME invocation the driver runs, each in a
             # child process of this script (`--config c2 | c4 | c5`: its own timing protocol, roofline and CPU baseline), and
             # carried under config.other_configs of the one final line.  The C3 headline above is already measured.
             line["config"]["other_configs"] = other_configs(args, orig_affinity)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 if pinned is not None:
                     # the GPU run is pinned to 8 cores; the CPU baseline gets the whole host: a child process with the

@@ -1,5 +1,5 @@
 # C2 (one scan per step, replayed encoder pass + structure plan of the coming scans): what moves the 0.75 ms
-run() { env "$@" python bench.py --config c2 --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+run() { env "$@" python bench.py --config c2 --full --steps 300 --warmup 30 --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); print('$*', d['ms_per_step'], d['config'].get('runner_host_split'))"; }
 run A=1

@@ -59,9 +59,7 @@ def test_state_dict_keys_and_shapes_match_reference():
 
 def test_reference_prototxt_parses_to_the_shipped_config():
     from rslo.utils import config_text
-    path = "/root/reference/config/kitti_train_ours.prototxt"
-    if not os.path.exists(path):
-        pytest.skip("reference tree absent")
+    path = os.path.join(GOLD, "kitti_train_ours.prototxt")       # the reference's shipped training config
     a = config_text.load(path).model.second.to_dict()
     b = config_text.shipped_config().model.second.to_dict()
     a.pop("post_center_limit_range", None)

@@ -254,16 +254,26 @@ def test_c5_dense_scan_encoder_fwd_bwd_matches_cpu_oracle(hip):
                                                  for k in ("conv3d2", "conv3d3", "conv3d4", "conv3d5")]
     assert n_lvl[0] > n_lvl[1] > n_lvl[2] > n_lvl[3] > n_lvl[4] > 3000
     assert rel(bev, bev_c) < 2e-5 and rel(cov, cov_c) < 2e-5
-    assert rel(x.grad, xc.grad) < 2e-3
-    # weight gradients against the float64 arbiter (the same modules in double): 5e-3 of the largest entry; the CPU
-    # fp32 path's own distance to the arbiter is measured beside it -- the covariance branch's first layer feeds a
-    # BatchNorm over 56 k rows and a LeakyReLU whose mask flips for |y| ~ 1e-7, both fp32 paths sit at ~3e-3 there
+    # weight and data gradients against the float64 arbiter (the same modules in double): 5e-3 (weights) / 2e-3 (data)
+    # of the largest entry; the CPU fp32 path's own distance to the arbiter is measured beside it -- the covariance
+    # branch's first layer feeds a BatchNorm over 56 k rows and a LeakyReLU whose mask flips for |y| ~ 1e-7, both fp32
+    # paths sit at ~3e-3 there
     enc_f64 = copy.deepcopy(enc).cpu().double()
     enc_f64.zero_grad()
+    xd = feats.cpu().double().clone().requires_grad_(True)
     with cpu_backend.patched():
-        bev_d, cov_d = enc_f64(feats.cpu().double(), coords.cpu(), 2)
+        bev_d, cov_d = enc_f64(xd, coords.cpu(), 2)
         ((bev_d * g_bev.cpu().double()).sum() + (cov_d * g_cov.cpu().double()).sum()).backward()
     assert rel(bev, bev_d) < 2e-5 and rel(cov, cov_d) < 2e-5
+    # data gradient, measured: GPU max 8.8e-3, CPU fp32 max 1.8e-2 of the largest entry (the two fp32 paths are 1.8e-2 apart,
+    # so neither can be the other's yardstick); 99th percentile 6.8e-6 (GPU) / 1.5e-3 (CPU fp32).  The tail (a few hundred
+    # of 780 k entries past 2e-3) is the mask-flip / BatchNorm-statistics effect above: its bar is the CPU path's own
+    # distance x 1.5; the bulk must sit within 1e-4 of the arbiter
+    e_x = (x.grad.detach().cpu().double() - xd.grad).abs() / xd.grad.abs().max()
+    e_xc = (xc.grad.double() - xd.grad).abs() / xd.grad.abs().max()
+    assert float(e_x.max()) < max(2e-3, 1.5 * float(e_xc.max())), (float(e_x.max()), float(e_xc.max()))
+    q99 = float(torch.quantile(e_x.flatten(), 0.99))
+    assert q99 < 1e-4, q99
     skip = bias_before_bn(enc)
     rows = [(rel(p.grad, pd.grad), rel(pc.grad, pd.grad), n) for (n, p), (_, pc), (_, pd) in
             zip(enc.named_parameters(), enc_cpu.named_parameters(), enc_f64.named_parameters()) if n not in skip]
