@@ -675,6 +675,33 @@ RSLO_API int rslo_conv2d_dgrad_s2(const float *dout, const void *Ws, int B, int 
  *      BE din (in place) -- the 1x1 gradient lands on the pixels (2y, 2x), the other three quarters of din are not touched. */
 RSLO_API int rslo_conv2d_dgrad_s2_add(const float *dout, const void *Ws, const float *res, int B, int cin, int cout, int H,
                                       int W, int ksize, float *din, void *stream);
+/*      Eval-mode (running-statistics) BatchNorm folded into the epilogue of the forward convolutions (the streaming
+ *      odometry path, rslo_amd/inference.py OdometryRunner):  v = (conv + bias[m]) * scale[m] + shift[m];  v += res[o]
+ *      (res may be NULL);  act != 0: v = v >= 0 ? v : slope * v (slope 0 = ReLU).  rslo_conv2d_fwd_bn: 3x3, stride 1,
+ *      padding 1 (Ws from rslo_conv2d_wsplit, transpose 0); rslo_conv2d_fwd_s2_bn: stride 2, ksize 3 / 1 (Ws from
+ *      rslo_conv2d_wsplit_k, transpose 0).  bias, res may be NULL; res must not alias out.
+ *      rslo_bn_fold_many: scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale for all layers
+ *      of a model in one launch (gamma / beta NULL: affine-free layer); max_c = the largest C. */
+RSLO_API int rslo_conv2d_fwd_bn(const float *in, const void *Ws, const float *bias, const float *scale, const float *shift,
+                                const float *res, int B, int cin, int cout, int H, int W, int act, float slope, float *out,
+                                void *stream);
+RSLO_API int rslo_conv2d_fwd_s2_bn(const float *in, const void *Ws, const float *bias, const float *scale,
+                                   const float *shift, const float *res, int B, int cin, int cout, int H, int W, int ksize,
+                                   int act, float slope, float *out, void *stream);
+typedef struct {
+  const float *gamma, *beta;        /* affine parameters [C] (NULL: 1 / 0) */
+  const float *mean, *var;          /* running statistics [C] */
+  float *scale, *shift;             /* [C] outputs */
+  int32_t C;
+  float eps;
+} RsloBnFoldDesc;
+RSLO_API int rslo_bn_fold_many(const RsloBnFoldDesc *desc_dev, int n_layers, int max_c, void *stream);
+/*      Pose chaining of a streamed sequence (rslo/utils/geometric.py odom_to_abs_pose one scan at a time), one thread:
+ *      n = *count; the scan's odometry (t [3], q [4] wxyz, fp32).  n == 0 seeds the float64 state with (t, q) and emits
+ *      the identity; n >= 1: t_s += rotate(t, q_s), q_s = qmult(q_s, q) / (|.| + 1e-6), emits (t_s, q_s).  Row n of
+ *      rel_rows [cap,7] (fp32) and traj [cap,7] (fp64) is written while n < cap; *count = n + 1. */
+RSLO_API int rslo_pose_chain(const float *t, const float *q, double *state, int32_t *count, float *rel_rows, double *traj,
+                             int cap, void *stream);
 /*      C4 (bf16 operands, fp32 accumulation and storage): the same kernels issuing only the product of the
  *      round-to-nearest bf16 values of activations and weights (1 MFMA instead of 6).  Ws is the operand block of
  *      rslo_conv2d_wsplit (its first plane IS the bf16-rounded weight); the stride-2 weight gradient keeps the split form. */

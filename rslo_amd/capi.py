@@ -184,6 +184,10 @@ SIGNATURES = {
     "rslo_conv2d_fwd_p": (C.c_int, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "rslo_opt_clip_grad_norm": (C.c_int, [_vp, _vp, _i, _f, _vp, _vp, _vp]),
     "rslo_opt_adam_step": (C.c_int, [_vp, _vp, _i, _vp, _f, _vp]),
+    "rslo_conv2d_fwd_bn": (C.c_int, [_vp] * 6 + [_i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "rslo_conv2d_fwd_s2_bn": (C.c_int, [_vp] * 6 + [_i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
+    "rslo_bn_fold_many": (C.c_int, [_vp, _i, _i, _vp]),
+    "rslo_pose_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
 }
 
 
@@ -1592,6 +1596,76 @@ def conv2d_wsplit_many(weights):
 
 def conv2d_wsplit_run(plan):
     _chk(lib().rslo_conv2d_wsplit_many(_ptr(plan["table"]), plan["n"], plan["max"], _stream()), "rslo_conv2d_wsplit_many")
+
+
+def conv2d_fwd_bn(x, ws, bias, scale, shift, cout, residual=None, slope=None, out=None):
+    """Eval-mode 3x3 / stride 1 / padding 1 convolution with the folded BatchNorm in its epilogue (rslo_conv2d_fwd_bn):
+    act((conv(x) + bias) * scale + shift + residual), slope None = no activation, 0 = ReLU, else LeakyReLU(slope)."""
+    B, cin, H, W = x.shape
+    if out is None:
+        out = torch.empty((B, cout, H, W), dtype=torch.float32, device=x.device)
+    if residual is not None and (tuple(residual.shape) != tuple(out.shape) or not residual.is_contiguous()):
+        raise ValueError("conv2d_fwd_bn: residual must be a contiguous %s tensor" % (tuple(out.shape),))
+    rc = lib().rslo_conv2d_fwd_bn(_ptr(x, torch.float32, "x"), ws.data_ptr(), _dp(bias), _ptr(scale, torch.float32, "scale"),
+                                  _ptr(shift, torch.float32, "shift"), _dp(residual), B, cin, cout, H, W,
+                                  0 if slope is None else 1, 0.0 if slope is None else float(slope), out.data_ptr(), _stream())
+    if rc:
+        _chk(rc, "rslo_conv2d_fwd_bn")
+    return out
+
+
+def conv2d_fwd_s2_bn(x, ws, bias, scale, shift, cout, ksize, residual=None, slope=None):
+    """Eval-mode stride-2 convolution (ksize 3 / padding 1 or 1 / padding 0) with the folded BatchNorm, an optional
+    residual and activation in its epilogue (rslo_conv2d_fwd_s2_bn); ws from conv2d_wsplit_k(w, False)."""
+    B, cin, H, W = x.shape
+    out = torch.empty((B, cout, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.float32, device=x.device)
+    if residual is not None and (tuple(residual.shape) != tuple(out.shape) or not residual.is_contiguous()):
+        raise ValueError("conv2d_fwd_s2_bn: residual must be a contiguous %s tensor" % (tuple(out.shape),))
+    rc = lib().rslo_conv2d_fwd_s2_bn(_ptr(x, torch.float32, "x"), ws.data_ptr(), _dp(bias),
+                                     _ptr(scale, torch.float32, "scale"), _ptr(shift, torch.float32, "shift"), _dp(residual),
+                                     B, cin, cout, H, W, ksize, 0 if slope is None else 1,
+                                     0.0 if slope is None else float(slope), out.data_ptr(), _stream())
+    if rc:
+        _chk(rc, "rslo_conv2d_fwd_s2_bn")
+    return out
+
+
+class BnFoldDesc(C.Structure):
+    _fields_ = [("gamma", C.c_void_p), ("beta", C.c_void_p), ("mean", C.c_void_p), ("var", C.c_void_p),
+                ("scale", C.c_void_p), ("shift", C.c_void_p), ("C", C.c_int32), ("eps", C.c_float)]
+
+
+def bn_fold_many(bns):
+    """bns: BatchNorm modules with running statistics (CUDA fp32).  Returns (plan, [(scale, shift) per layer]); every
+    bn_fold_run(plan) re-derives scale = gamma / sqrt(running_var + eps), shift = beta - running_mean * scale for all
+    layers in one launch from the LIVE parameter and buffer storage."""
+    dev = bns[0].running_mean.device
+    sizes = [int(b.running_mean.numel()) for b in bns]
+    pool = torch.empty((2 * sum(sizes),), dtype=torch.float32, device=dev)
+    arr = (BnFoldDesc * len(bns))()
+    views, off = [], 0
+    for i, (b, n) in enumerate(zip(bns, sizes)):
+        sc, sh = pool[off:off + n], pool[off + n:off + 2 * n]
+        off += 2 * n
+        views.append((sc, sh))
+        g = _ptr(b.weight, torch.float32, "bn.weight") if b.weight is not None else None
+        be = _ptr(b.bias, torch.float32, "bn.bias") if b.bias is not None else None
+        arr[i] = BnFoldDesc(g, be, _ptr(b.running_mean, torch.float32, "running_mean"),
+                            _ptr(b.running_var, torch.float32, "running_var"), sc.data_ptr(), sh.data_ptr(), n, float(b.eps))
+    table = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(dev)
+    return {"table": table, "n": len(bns), "max": max(sizes), "pool": pool}, views
+
+
+def bn_fold_run(plan):
+    _chk(lib().rslo_bn_fold_many(_ptr(plan["table"]), plan["n"], plan["max"], _stream()), "rslo_bn_fold_many")
+
+
+def pose_chain(t, q, state, count, rel_rows, traj):
+    """One step of the streamed pose chain (rslo_pose_chain): t [3] / q [4] fp32 CUDA, state [7] fp64, count [1] int32,
+    rel_rows [cap,7] fp32, traj [cap,7] fp64 -- row *count of both is written, then *count += 1."""
+    _chk(lib().rslo_pose_chain(_ptr(t, torch.float32, "t"), _ptr(q, torch.float32, "q"), _ptr(state, torch.float64, "state"),
+                               _ptr(count, torch.int32, "count"), _ptr(rel_rows, torch.float32, "rel_rows"),
+                               _ptr(traj, torch.float64, "traj"), int(traj.shape[0]), _stream()), "rslo_pose_chain")
 
 
 def conv2d_s2_supported(cin, cout, ksize):

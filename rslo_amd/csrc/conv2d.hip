@@ -579,7 +579,9 @@ __global__ void k_conv2d_wsplit_many(const RsloConv2dSplitDesc *__restrict__ des
 // accumulator sets meet through LDS (set 0 + set 1, a fixed order).  On the 12x22 / 24x44 maps a launch is less than one
 // workgroup per CU and lasts as long as ONE workgroup's chain of n_chunks x (global load -> split -> LDS -> 9 taps),
 // 2.7 us per chunk against 0.7 us of MFMAs: two half-length chains side by side on the CU halve it.
-template <int TR, int MTW, bool FULLA, bool LP = false, int KC = 1, int OCC = 2 / KC>
+// EP: the eval-BatchNorm epilogue of Conv2dFwdGeom (scale / shift, residual, activation); EP = false instantiations
+// never read those fields and keep their code and bits.
+template <int TR, int MTW, bool FULLA, bool LP = false, int KC = 1, int OCC = 2 / KC, bool EP = false>
 __global__ __launch_bounds__(256 * KC, OCC) void k_conv2d_fwd(const float *__restrict__ in, const unsigned short *__restrict__ Ws,
                                                     const float *__restrict__ bias, Conv2dFwdGeom gm,
                                                     float *__restrict__ out) {
@@ -790,13 +792,19 @@ __global__ __launch_bounds__(256 * KC, OCC) void k_conv2d_fwd(const float *__res
     for (int j = 0; j < 4; ++j) {
       const int m = (mt0 + mt) * 16 + 4 * g + j;
       const float bv = bias ? bias[m] : 0.f;
+      float sc = 1.f, sh = 0.f;
+      if constexpr (EP) { sc = gm.scale[m]; sh = gm.shift[m]; }
 #pragma unroll
       for (int nt = 0; nt < NTW; ++nt) {
         const int y = y0 + wn * NTW + nt;
         if (x < W && y < H) {
           const int64_t o = ((int64_t)b * gm.cout + m) * HW + (int64_t)y * W + x;
           float v = acc[mt][nt][j] + bv;
+          if constexpr (EP) v = v * sc + sh;
           if (gm.res) v += gm.res[o];      // the residual branch's gradient of a BasicBlock: same bits as a separate add
+          if constexpr (EP) {
+            if (gm.act) v = v >= 0.f ? v : gm.slope * v;
+          }
           out[o] = v;
         }
       }
@@ -962,6 +970,37 @@ static int conv2d_fwd_launch(const float *in, const void *Ws, const float *bias,
   return RSLO_OK;
 }
 
+// Eval-mode conv -> BatchNorm (running statistics folded into scale / shift) -> (+ res) -> activation in one launch: the
+// default tile configuration of conv2d_fwd_launch (4-row tiles, one 16-channel block per wave; the lean one-tap-ahead
+// variant on maps of >= 512 workgroups, two wave sets on long chains of few workgroups), with the EP epilogue.
+extern "C" int rslo_conv2d_fwd_bn(const float *in, const void *Ws, const float *bias, const float *scale, const float *shift,
+                                  const float *res, int B, int cin, int cout, int H, int W, int act, float slope, float *out,
+                                  void *stream) {
+  int tr, mtw;
+  RSLO_CHECK_ARG(in && Ws && scale && shift && out && conv2d_fwd_plan(B, cin, cout, H, W, &tr, &mtw),
+                 "rslo_conv2d_fwd_bn: unsupported shape cin=%d cout=%d H=%d W=%d", cin, cout, H, W);
+  Conv2dFwdGeom gm;
+  gm.B = B; gm.cin = cin; gm.cout = cout; gm.H = H; gm.W = W;
+  gm.res = res; gm.scale = scale; gm.shift = shift; gm.slope = slope; gm.act = act ? 1 : 0;
+  gm.tiles_x = (int)rslo_cdiv(W, 16);
+  gm.tiles_y = (int)rslo_cdiv(H, 4);
+  gm.npix = B * gm.tiles_x * gm.tiles_y;
+  gm.ny = cout / 32;
+  gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_FWD_XSC, gm.ny, 3.0 * 18.0 * cin * cout, 4.0 * B * cin * H * W * 1.5);
+  const dim3 grid = conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short *ws = (const unsigned short *)Ws;
+  const int64_t wgs4 = (int64_t)gm.npix * gm.ny;
+  if (cin >= 256 && wgs4 <= 200)
+    hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, false, 2, 1, true>), grid, dim3(512), 0, st, in, ws, bias, gm, out);
+  else if (wgs4 >= 512)
+    hipLaunchKernelGGL((k_conv2d_fwd<4, 1, false, false, 1, 5, true>), grid, dim3(256), 0, st, in, ws, bias, gm, out);
+  else
+    hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, false, 1, 2, true>), grid, dim3(256), 0, st, in, ws, bias, gm, out);
+  RSLO_CHECK_LAUNCH("k_conv2d_fwd(bn)");
+  return RSLO_OK;
+}
+
 // ---------------------------------------------------------------------------------------------------------------------
 // Stride-2 layers of the BEV encoder (the first 3x3 convolution and the 1x1 downsample of every stage:
 // rslo/models/odom_pred.py:398-426 -> custom_resnet_spc.BasicBlock / conv1x1): forward and data gradient on the same
@@ -998,6 +1037,10 @@ struct Conv2dStrGeom {
   int xsc, npix, ny;      // XCD-aware workgroup order, as in Conv2dFwdGeom
   const float *res;       // optional [B][cout][Ho][Wo] added in the epilogue (NULL: none)
   Conv2dStrClass cls[4];
+  // eval-BatchNorm epilogue, read only by the EP = true instantiations (as in Conv2dFwdGeom; bias may be NULL)
+  const float *bias, *scale, *shift;
+  float slope;
+  int act;
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -1030,7 +1073,7 @@ __device__ constexpr StrTap str_tap(int t) {
   return StrTap{0, 0, 0, 0};
 }
 
-template <int MODE, int MTW, int OCC, bool FULLA = (MTW == 1)>
+template <int MODE, int MTW, int OCC, bool FULLA = (MTW == 1), bool EP = false>
 __global__ __launch_bounds__(256, OCC) void k_conv2d_str2(const float *__restrict__ in, const unsigned short *__restrict__ Ws,
                                                           Conv2dStrGeom gm, float *__restrict__ out) {
   constexpr int TR = 4, NTW = TR / 2;
@@ -1188,12 +1231,21 @@ __global__ __launch_bounds__(256, OCC) void k_conv2d_str2(const float *__restric
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int m = (mt0 + mt) * 16 + 4 * g + j;
+        float bv = 0.f, sc = 1.f, sh = 0.f;
+        if constexpr (EP) { bv = gm.bias ? gm.bias[m] : 0.f; sc = gm.scale[m]; sh = gm.shift[m]; }
 #pragma unroll
         for (int nt = 0; nt < NTW; ++nt) {
           const int r = r0 + wn * NTW + nt;
           if (col < cl.cols && r < cl.rows) {
             const int64_t o = ((int64_t)b * gm.cout + m) * HWo + (int64_t)(gm.s_out * r + cl.py) * gm.Wo + gm.s_out * col + cl.px;
-            out[o] = gm.res ? acc[c][mt][nt][j] + gm.res[o] : acc[c][mt][nt][j];
+            if constexpr (EP) {
+              float v = (acc[c][mt][nt][j] + bv) * sc + sh;
+              if (gm.res) v += gm.res[o];
+              if (gm.act) v = v >= 0.f ? v : gm.slope * v;
+              out[o] = v;
+            } else {
+              out[o] = gm.res ? acc[c][mt][nt][j] + gm.res[o] : acc[c][mt][nt][j];
+            }
           }
         }
       }
@@ -1241,6 +1293,59 @@ extern "C" int rslo_conv2d_fwd_s2(const float *in, const void *Ws, int B, int ci
     else hipLaunchKernelGGL((k_conv2d_str2<1, 1, 4>), grid, dim3(256), 0, st, in, ws, gm, out);
   }
   RSLO_CHECK_LAUNCH("k_conv2d_str2(fwd)");
+  return RSLO_OK;
+}
+
+// Eval-mode stride-2 conv (3x3 / padding 1 or 1x1 / padding 0) -> folded BatchNorm -> (+ res) -> activation in one launch,
+// one 16-channel block per wave (the default configuration of rslo_conv2d_fwd_s2)
+extern "C" int rslo_conv2d_fwd_s2_bn(const float *in, const void *Ws, const float *bias, const float *scale,
+                                     const float *shift, const float *res, int B, int cin, int cout, int H, int W, int ksize,
+                                     int act, float slope, float *out, void *stream) {
+  RSLO_CHECK_ARG(in && Ws && scale && shift && out && B > 0 && H > 0 && W > 0 && rslo_conv2d_s2_supported(cin, cout, ksize),
+                 "rslo_conv2d_fwd_s2_bn: unsupported shape cin=%d cout=%d ksize=%d", cin, cout, ksize);
+  Conv2dStrGeom gm = {};
+  gm.B = B; gm.cin = cin; gm.cout = cout; gm.Hi = H; gm.Wi = W;
+  gm.Ho = (H - 1) / 2 + 1; gm.Wo = (W - 1) / 2 + 1;
+  gm.s_out = 1; gm.ntap_w = ksize * ksize; gm.n_class = gm.cls_out = 1;
+  gm.tiles_x = (int)rslo_cdiv(gm.Wo, 16); gm.tiles_y = (int)rslo_cdiv(gm.Ho, 4);
+  gm.res = res; gm.bias = bias; gm.scale = scale; gm.shift = shift; gm.slope = slope; gm.act = act ? 1 : 0;
+  Conv2dStrClass &c = gm.cls[0];
+  c.rows = gm.Ho; c.cols = gm.Wo;
+  gm.npix = B * gm.tiles_x * gm.tiles_y;
+  gm.ny = cout / 32;
+  gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_S2_XSC, gm.ny, 6.0 * ksize * ksize * cin * cout, 4.0 * B * cin * H * W * (ksize == 3 ? 1.5 : 0.25));
+  const dim3 grid = conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
+  hipStream_t st = (hipStream_t)stream;
+  const unsigned short *ws = (const unsigned short *)Ws;
+  if (ksize == 3) {
+    gm.src_stride = 1; gm.by = gm.bx = -1; c.ny = c.nx = 3;
+    for (int i = 0; i < 3; ++i) c.oy[i] = c.ox[i] = i;
+    for (int i = 0; i < 9; ++i) c.wt[i] = i;
+    hipLaunchKernelGGL((k_conv2d_str2<0, 1, 2, true, true>), grid, dim3(256), 0, st, in, ws, gm, out);
+  } else {
+    gm.src_stride = 2; c.ny = c.nx = 1;
+    hipLaunchKernelGGL((k_conv2d_str2<1, 1, 4, true, true>), grid, dim3(256), 0, st, in, ws, gm, out);
+  }
+  RSLO_CHECK_LAUNCH("k_conv2d_str2(fwd, bn)");
+  return RSLO_OK;
+}
+
+// One launch for all BatchNorm layers of a model in eval mode: scale = gamma / sqrt(running_var + eps),
+// shift = beta - running_mean * scale (gamma / beta NULL: 1 / 0).  Grid (ceil(max_c / 256), n_layers).
+__global__ void k_bn_fold_many(const RsloBnFoldDesc *__restrict__ desc) {
+  const RsloBnFoldDesc d = desc[blockIdx.y];
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= d.C) return;
+  const float s = (d.gamma ? d.gamma[c] : 1.f) / sqrtf(d.var[c] + d.eps);
+  d.scale[c] = s;
+  d.shift[c] = (d.beta ? d.beta[c] : 0.f) - d.mean[c] * s;
+}
+
+extern "C" int rslo_bn_fold_many(const RsloBnFoldDesc *desc_dev, int n_layers, int max_c, void *stream) {
+  RSLO_CHECK_ARG(desc_dev && n_layers > 0 && n_layers < 65536 && max_c > 0, "rslo_bn_fold_many: bad sizes");
+  hipLaunchKernelGGL(k_bn_fold_many, dim3((unsigned)rslo_cdiv(max_c, 256), (unsigned)n_layers), dim3(256), 0,
+                     (hipStream_t)stream, desc_dev);
+  RSLO_CHECK_LAUNCH("k_bn_fold_many");
   return RSLO_OK;
 }
 

@@ -52,6 +52,11 @@ struct Conv2dFwdGeom {
   int tiles_x, tiles_y;
   int xsc, npix, ny;           // XCD-aware workgroup order (conv2d_xcd_tile); xsc = 0: plain (pixel tile, channel group) grid
   const float *res;            // optional [B][cout][H][W] added to the result in the epilogue (out = conv + bias + res), or NULL
+  // eval-BatchNorm epilogue, read only by the EP = true instantiations: v = (conv + bias) * scale[m] + shift[m], then
+  // v += res, then (act != 0) v = v >= 0 ? v : slope * v
+  const float *scale, *shift;
+  float slope;
+  int act;
 };
 
 // Which (pixel tile bx, output-channel group by) a workgroup takes.  Workgroups of a one-dimensional grid are dealt to the

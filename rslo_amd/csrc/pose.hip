@@ -132,3 +132,59 @@ extern "C" int rslo_pose_targets(const float *res_r, const float *res_t, const f
                                  float *rot_targets_wxyz, float *trans_targets, void *stream) {
   return rslo_pose_targets_tq(res_r, res_t, R_pred, T_pred, B, rot_targets_wxyz, trans_targets, nullptr, stream);
 }
+
+// Absolute pose of a streamed sequence, one scan per launch (rslo/utils/geometric.py odom_to_abs_pose restated for one
+// step; captured in the head's hipGraph, so the row index comes from the device counter, not the host).  The state is
+// kept in float64 so that thousands of steps follow the float64 host function.
+__device__ __forceinline__ void pc_cross(const double *a, const double *b, double *c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+__global__ void k_pose_chain(const float *__restrict__ t_in, const float *__restrict__ q_in, double *__restrict__ state,
+                             int32_t *__restrict__ count, float *__restrict__ rel_rows, double *__restrict__ traj, int cap) {
+  if (threadIdx.x != 0) return;
+  const int n = *count;
+  double t[3], q[4], pose[7];
+  for (int i = 0; i < 3; ++i) t[i] = (double)t_in[i];
+  for (int i = 0; i < 4; ++i) q[i] = (double)q_in[i];
+  if (n == 0) {      // scan 0 seeds the chain with its own odometry and is the origin
+    for (int i = 0; i < 3; ++i) state[i] = t[i];
+    for (int i = 0; i < 4; ++i) state[3 + i] = q[i];
+    for (int i = 0; i < 7; ++i) pose[i] = i == 3 ? 1.0 : 0.0;
+  } else {
+    double ts[3], qs[4];
+    for (int i = 0; i < 3; ++i) ts[i] = state[i];
+    for (int i = 0; i < 4; ++i) qs[i] = state[3 + i];
+    // t_s + rotate_vec_by_q(t, q_s):  t + 2 w (v x t) + 2 v x (v x t)
+    double b[3], c[3];
+    pc_cross(qs + 1, t, b);
+    pc_cross(qs + 1, b, c);
+    for (int i = 0; i < 3; ++i) ts[i] = ts[i] + (t[i] + 2.0 * b[i] * qs[0] + 2.0 * c[i]);
+    // qmult(q_s, q), re-normalised with the eps inside the division (pose_utils_np.normalize)
+    double vx[3];
+    pc_cross(qs + 1, q + 1, vx);
+    double r[4];
+    r[0] = qs[0] * q[0] - (qs[1] * q[1] + qs[2] * q[2] + qs[3] * q[3]);
+    for (int i = 0; i < 3; ++i) r[1 + i] = qs[1 + i] * q[0] + q[1 + i] * qs[0] + vx[i];
+    const double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]) + 1e-6;
+    for (int i = 0; i < 4; ++i) r[i] /= nr;
+    for (int i = 0; i < 3; ++i) state[i] = pose[i] = ts[i];
+    for (int i = 0; i < 4; ++i) state[3 + i] = pose[3 + i] = r[i];
+  }
+  if (n < cap) {
+    for (int i = 0; i < 3; ++i) rel_rows[(int64_t)n * 7 + i] = t_in[i];
+    for (int i = 0; i < 4; ++i) rel_rows[(int64_t)n * 7 + 3 + i] = q_in[i];
+    for (int i = 0; i < 7; ++i) traj[(int64_t)n * 7 + i] = pose[i];
+  }
+  *count = n + 1;
+}
+
+extern "C" int rslo_pose_chain(const float *t, const float *q, double *state, int32_t *count, float *rel_rows, double *traj,
+                               int cap, void *stream) {
+  RSLO_CHECK_ARG(t && q && state && count && rel_rows && traj && cap > 0, "rslo_pose_chain: bad arguments");
+  hipLaunchKernelGGL(k_pose_chain, dim3(1), dim3(64), 0, (hipStream_t)stream, t, q, state, count, rel_rows, traj, cap);
+  RSLO_CHECK_LAUNCH("k_pose_chain");
+  return RSLO_OK;
+}

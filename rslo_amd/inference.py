@@ -38,8 +38,10 @@ class EncoderGraphRunner:
        bev, cov, n_rows = runner.run(job)           # graph replay on the current stream; cov[:n_rows] are the valid rows
     `bev` / `cov` are static tensors of the job's arena: consume (or copy) them before that arena's next run()."""
 
-    def __init__(self, net_like, max_voxels, device="cuda", point_capacity=160000, arenas=4, frames_per_job=1):
+    def __init__(self, net_like, max_voxels, device="cuda", point_capacity=160000, arenas=4, frames_per_job=1,
+                 with_cov=True):
         self.net = net_like
+        self.with_cov = bool(with_cov)      # False: the covariance branch is not issued (run() returns cov = None)
         self.enc = net_like.middle_feature_extractor
         if self.enc.training:
             raise capi.RsloHipError("EncoderGraphRunner is an inference path: put the encoder in eval() mode")
@@ -114,15 +116,18 @@ class EncoderGraphRunner:
     def _forward(self, job):
         vox, num, plan, rows_dev = self.planner.finish_static(job)
         x = capi.vfe_mean(vox, num)
-        bev, cov = self.enc(x, plan.indices, job.n_clouds, plan=plan)
-        return bev, cov, rows_dev[0]
+        bev, cov = self.enc(x, plan.indices, job.n_clouds, plan=plan, defer_cov=not self.with_cov)
+        return bev, cov if self.with_cov else None, rows_dev[0]
 
     def _exact(self, job):
         """Exact-size plan + eager pass of a scan whose static plan overflowed a level's capacity (fresh tensors, no graph)."""
         ex = self._exact_planner.finish(self._exact_planner.submit(job.clouds, with_pairs=False))
         vox, num = ex["_frame_major"]
         with torch.no_grad():
-            bev, cov = self.enc(capi.vfe_mean(vox, num), ex["sparse_plan"].indices, job.n_clouds, plan=ex["sparse_plan"])
+            bev, cov = self.enc(capi.vfe_mean(vox, num), ex["sparse_plan"].indices, job.n_clouds, plan=ex["sparse_plan"],
+                                defer_cov=not self.with_cov)
+        if not self.with_cov:
+            return bev, None, torch.tensor([vox.shape[0]], dtype=torch.int32, device=bev.device)
         return bev, cov, torch.tensor([cov.shape[0]], dtype=torch.int32, device=cov.device)
 
     def _capture(self, job, cur):
@@ -176,3 +181,167 @@ class EncoderGraphRunner:
         ev.record(cur)
         self._last_use[a] = ev
         return out
+
+
+def pose_chain_host(rows):
+    """The recurrence of rslo_pose_chain on the host, one scan at a time, float64: rows [N,7] (t, q wxyz) -> poses [N,7].
+    Scan 0 seeds the state with its own odometry and is the identity (the quirk of geometric.odom_to_abs_pose)."""
+    import numpy as np
+    rows = np.asarray(rows, dtype=np.float64)
+    out = np.zeros_like(rows)
+    t = q = None
+    for i, r in enumerate(rows):
+        if i == 0:
+            t, q = r[:3].copy(), r[3:].copy()
+            out[0] = (0, 0, 0, 1, 0, 0, 0)
+            continue
+        ti, qi = r[:3], r[3:]
+        b = np.cross(q[1:], ti)
+        t = t + (ti + 2.0 * b * q[0] + 2.0 * np.cross(q[1:], b))
+        p = np.concatenate([[q[0] * qi[0] - np.dot(q[1:], qi[1:])], q[1:] * qi[0] + qi[1:] * q[0] + np.cross(q[1:], qi[1:])])
+        q = p / (np.linalg.norm(p) + 1e-6)
+        out[i, :3], out[i, 3:] = t, q
+    return out
+
+
+class OdometryRunner:
+    """Streaming odometry of the whole network in eval mode (evaluate.py:363-408 fed one scan at a time):
+
+        runner = OdometryRunner(net)        # UnVoxelOdomNetICP3 in eval(), CUDA, fp32
+        h = runner.submit(cloud)            # [P, 7] fp32 CUDA scan, in sequence order
+        rel, pose = runner.run(h)           # [7] (t, q) each: odometry of (previous, this) and absolute pose
+        traj = runner.trajectory()          # [N, 7] fp64 device tensor = odom_to_abs_pose of the rel rows
+        runner.reset()                      # new sequence: the next scan pairs with itself, the trajectory restarts
+
+    * Encoder: an EncoderGraphRunner with one frame per job and no covariance branch (poses do not depend on it): every
+      scan is voxelized, planned and encoded ONCE.  (The dataset builds example i from frames (max(i-1, 0), i), so an
+      eager loop encodes every scan twice; in eval mode a frame's encoding does not depend on its partner.)
+    * Pair map: the head's static input [1, 2C, H, W] = [previous | current], the channel order of
+      voxel_odom_net.network_forward: per scan the current half moves to the previous half and the scan's BEV map is
+      copied in (two device copies of C*H*W floats); the first scan of a sequence is paired with itself.
+    * Head: the eval forward without autograd (odom_pred._forward_eval_fused: every conv -> BN -> activation one launch of
+      a hand-written kernel) plus the pose chain (rslo_pose_chain, float64 state, row n of the trajectory) captured
+      once into a hipGraph over that static input and replayed once per scan on the caller's stream.  Both graphs are
+      single-stream captures; no stream is opened beyond the encoder runner's plan stream.
+    * Weights: split operands and folded BatchNorms are derived outside the graph (hip_conv2d.EvalOperands) and
+      re-derived before the next replay when a parameter or running statistic of the head changed in place
+      (load_state_dict, an optimizer step, bn.running_var.mul_(...)); a storage that moved is re-planned and the head
+      graph captured again.  A replaced parameter object, or a write through `.data` (it bumps no version counter):
+      call refresh_weights(force=True).
+    * Handles: the outstanding-handle rule of EncoderGraphRunner (fewer than `arenas` submitted and not yet run).
+    `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
+
+    def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000):
+        from rslo_amd import synthetic
+        self.net = net
+        self.head = net.odom_predictor
+        if net.training or self.head.training:
+            raise capi.RsloHipError("OdometryRunner is an inference path: put the network in eval() mode")
+        why = self.head.eval_fused_unsupported()
+        if why is not None:
+            raise capi.RsloHipError("OdometryRunner: unsupported configuration: " + why)
+        p = next(self.head.parameters())
+        if not p.is_cuda:
+            raise capi.RsloHipError("OdometryRunner: the network must live on the GPU")
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        from rslo.layers import hip_conv2d
+        self.operands = hip_conv2d.EvalOperands(self.head)
+        self.encoder = EncoderGraphRunner(net, synthetic.MAX_VOXELS if max_voxels is None else max_voxels, self.device,
+                                          point_capacity=point_capacity, arenas=arenas, with_cov=False)
+        self.capacity = int(capacity)
+        dev = self.device
+        self._state = torch.zeros((7,), dtype=torch.float64, device=dev)
+        self._count = torch.zeros((1,), dtype=torch.int32, device=dev)
+        self._rel = torch.zeros((self.capacity, 7), dtype=torch.float32, device=dev)
+        self._traj = torch.zeros((self.capacity, 7), dtype=torch.float64, device=dev)
+        self._pair = None          # [1, 2C, H, W] static input of the head graph
+        self._graph = None
+        self._n = 0                # scans of the current sequence (host mirror of the device counter)
+        self.stats = {"scans": 0, "encoder_runs": 0, "head_replays": 0, "head_eager": 0, "captures": 0,
+                      "weight_refreshes": 0}
+
+    def submit(self, cloud):
+        return self.encoder.submit(cloud)
+
+    def close(self):
+        self.encoder.close()
+
+    def reset(self):
+        """A new sequence: the next scan is paired with itself and seeds a new trajectory."""
+        self._count.zero_()
+        self._n = 0
+
+    def trajectory(self):
+        return self._traj[:min(self._n, self.capacity)]
+
+    def relative(self):
+        return self._rel[:min(self._n, self.capacity)]
+
+    def refresh_weights(self, force=False):
+        """Re-derive the head's split operands and folded BatchNorms if a parameter / running statistic changed (or
+        always, force=True); a storage that moved invalidates the captured head graph."""
+        if force:           # the tensors are collected again: a parameter object may have been replaced
+            from rslo.layers import hip_conv2d
+            self.operands = hip_conv2d.EvalOperands(self.head)
+        n0 = self.operands.refreshes
+        if self.operands.refresh():
+            self._graph = None
+        self.stats["weight_refreshes"] += self.operands.refreshes - n0
+
+    def _head(self):
+        self.head.__dict__["_eval_fused"] = True
+        try:
+            with torch.no_grad():
+                out = self.head(self._pair)
+        finally:
+            self.head.__dict__.pop("_eval_fused", None)
+        return out["translation_preds"][0], out["rotation_preds"][0]
+
+    def _head_and_chain(self):
+        t, r = self._head()
+        capi.pose_chain(t[0], r[0], self._state, self._count, self._rel, self._traj)
+
+    def run(self, handle, graph=True):
+        """Encoder pass of the submitted scan, pair map, head + pose chain (a replay of the head graph, or with
+        graph=False the same kernels issued eagerly).  Returns (rel [7] fp32, pose [7] fp64) device rows."""
+        if self._n >= self.capacity:
+            raise capi.RsloHipError("OdometryRunner: more than %d scans in one sequence (capacity); reset() or a larger "
+                                    "capacity" % self.capacity)
+        bev, _, _ = self.encoder.run(handle, graph=graph)
+        self.stats["encoder_runs"] += 1
+        C = bev.shape[1]
+        if self._pair is None or self._pair.shape[1] != 2 * C or self._pair.shape[2:] != bev.shape[2:]:
+            self._pair = torch.empty((1, 2 * C) + tuple(bev.shape[2:]), dtype=torch.float32, device=self.device)
+            self._graph = None
+        prev, cur = self._pair[:, :C], self._pair[:, C:]
+        if self._n == 0:
+            prev.copy_(bev[:1])
+        else:
+            prev.copy_(cur)
+        cur.copy_(bev[:1])
+        self.refresh_weights()
+        if graph:
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+            self.stats["head_replays"] += 1
+        else:
+            self._head_and_chain()
+            self.stats["head_eager"] += 1
+        n = self._n
+        self._n += 1
+        self.stats["scans"] += 1
+        return self._rel[n], self._traj[n]
+
+    def _capture(self):
+        """Warm up (the kernels' first launches, the allocator's blocks) with the head alone -- the pose chain must not
+        advance -- then capture head + pose chain over the static pair map."""
+        self._head()
+        torch.cuda.current_stream(self.device).synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._head_and_chain()
+        self._graph = g
+        self.stats["captures"] += 1

@@ -276,6 +276,29 @@ class FusedSequential(nn.Sequential):
         head's fused concatenation + nn.Upsample in front of a deblock)."""
         return self._run(x, self._steps(), first_child)
 
+    def forward_eval_fused(self, x, first_child=0):
+        """Eval mode without autograd (rslo_amd.inference.OdometryRunner only): every conv -> BN -> activation step is
+        one launch with the folded BatchNorm in the convolution's epilogue (hip_conv2d.conv_bn_eval), a 1x1 output
+        convolution is rslo_conv1x1_fwd, a child with a forward_eval_fused of its own (BasicBlock) runs that.  Anything
+        else has no such path and raises RsloHipError."""
+        from rslo.layers import hip_conv2d
+        skip = first_child
+        for m, slope in self._steps():
+            if skip > 0:
+                if isinstance(m, tuple) or slope is not None:
+                    raise ValueError("forward_eval_fused: child %d is inside a fused group" % first_child)
+                skip -= 1
+                continue
+            if isinstance(m, tuple):
+                x = hip_conv2d.conv_bn_eval(m[0], m[1], x, slope)
+            elif slope is None and hasattr(m, "forward_eval_fused"):
+                x = m.forward_eval_fused(x)
+            elif slope is None and isinstance(m, hip_conv2d.Conv2d) and m._kind() == "1x1":
+                x = hip_conv2d.conv1x1_eval(m, x)
+            else:
+                raise hip_conv2d._rslo_error("forward_eval_fused: no fused eval path for %s" % type(m).__name__)
+        return x
+
     @staticmethod
     def _run(x, steps, first_child):
         skip = first_child

@@ -259,3 +259,78 @@ class Conv2d(nn.Conv2d):
             if kind == "3x3" and self._eligible(input):
                 return _Conv3x3Fn.apply(input, weight, bias, self.stride[0], self._hip_ok[2], self._hip_ok[1])
         return super()._conv_forward(input, weight, bias)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Eval-mode path without autograd (rslo_amd.inference.OdometryRunner): every conv -> BatchNorm (running statistics) ->
+# (+ residual) -> activation is ONE launch of rslo_conv2d_fwd_bn / _fwd_s2_bn, the BatchNorm folded into a per-channel
+# scale / shift by EvalOperands.refresh().  Nothing here runs under a plain net(example).
+# ---------------------------------------------------------------------------------------------------------------------
+def _rslo_error(msg):
+    from rslo_amd import capi
+    return capi.RsloHipError(msg)
+
+
+def conv_bn_eval(conv, bn, x, slope, residual=None):
+    """act(bn(conv(x)) + residual) in one launch; conv a Conv2d (or a MaskConv around one) whose split forward operand
+    and bn whose folded scale / shift EvalOperands.refresh() has made current.  slope None: no activation."""
+    from rslo_amd import capi
+    c = getattr(conv, "conv1", conv)
+    fold = bn.__dict__.get("_eval_fold")
+    ws = getattr(c.weight, "_hip_split", None)
+    if fold is None or ws is None or ws[2] != c.weight._version or ws[3] != c.weight.data_ptr():
+        raise _rslo_error("conv_bn_eval: operands of %s are not current (EvalOperands.refresh)" % type(c).__name__)
+    x = x.contiguous()
+    if c.stride == (2, 2):
+        return capi.conv2d_fwd_s2_bn(x, ws[0], c.bias, fold[0], fold[1], c.out_channels, c.kernel_size[0], residual, slope)
+    return capi.conv2d_fwd_bn(x, ws[0], c.bias, fold[0], fold[1], c.out_channels, residual, slope)
+
+
+def conv1x1_eval(conv, x):
+    """A 1x1 / stride-1 output convolution (<= 8 channels) through rslo_conv1x1_fwd."""
+    from rslo_amd import capi
+    if not (isinstance(conv, Conv2d) and conv._kind() == "1x1"):
+        raise _rslo_error("conv1x1_eval: %s is not a 1x1 output convolution" % type(conv).__name__)
+    return capi.conv1x1_fwd(x.contiguous(), conv.weight, conv.bias)
+
+
+def fold_bn_host(weight, bias, running_mean, running_var, eps):
+    """What rslo_bn_fold_many computes per channel: (scale, shift) with bn_eval(x) = x * scale + shift."""
+    scale = (torch.ones_like(running_var) if weight is None else weight) / torch.sqrt(running_var + eps)
+    shift = (torch.zeros_like(running_mean) if bias is None else bias) - running_mean * scale
+    return scale, shift
+
+
+class EvalOperands:
+    """The derived operands of the eval path for every layer under `root`: split-bf16 weights (presplit, one launch)
+    and folded BatchNorms (rslo_bn_fold_many, one launch), issued on the current stream -- outside any graph capture.
+    refresh() re-derives them when a parameter or running-statistic tensor of `root` has changed (version counter or
+    storage; a write through `.data` bumps neither) and returns True when a storage moved: the operand buffers or the
+    parameters a captured graph reads directly (conv biases) are then new, and such a graph must be captured again."""
+
+    def __init__(self, root):
+        self.root = root
+        self.bns = [m for m in root.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        self.tensors = list(root.parameters()) + [t for b in self.bns for t in (b.running_mean, b.running_var)]
+        self.key = None
+        self.plan = None
+        self.refreshes = 0
+
+    def _key(self):
+        return [(t._version, t.data_ptr()) for t in self.tensors]
+
+    def refresh(self):
+        from rslo_amd import capi
+        key = self._key()
+        if key == self.key:
+            return False
+        moved = self.key is None or any(a[1] != b[1] for a, b in zip(key, self.key))
+        if moved:
+            self.plan, views = capi.bn_fold_many(self.bns)
+            for b, v in zip(self.bns, views):
+                b.__dict__["_eval_fold"] = v
+        presplit(self.root)
+        capi.bn_fold_run(self.plan)
+        self.key = key
+        self.refreshes += 1
+        return moved

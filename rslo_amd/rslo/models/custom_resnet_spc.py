@@ -196,6 +196,24 @@ class BasicBlock(nn.Module):
         self._fused_hip_w1 = bool(c1._hip_ok[1])
         return True
 
+    def forward_eval_fused(self, x):
+        """Eval mode without autograd (FusedSequential.forward_eval_fused): the reference's order
+        relu(bn2(conv2(relu(bn1(conv1(x))))) + identity), identity = bn_d(conv1x1_s2(x)) computed first, each
+        conv -> BN (-> + identity) -> ReLU one launch."""
+        from rslo.layers import hip_conv2d
+        slope = act_slope_of(self.relu)
+        if self.downsample is not None:
+            ds = list(self.downsample.children()) if isinstance(self.downsample, nn.Sequential) else []
+            if len(ds) != 2 or not isinstance(ds[1], SPC_SyncBN2d):
+                raise hip_conv2d._rslo_error("BasicBlock.forward_eval_fused: downsample is not (conv1x1, BatchNorm)")
+            identity = hip_conv2d.conv_bn_eval(ds[0], ds[1], x, None)
+        else:
+            identity = x.contiguous()
+        if not (isinstance(self.bn1, SPC_SyncBN2d) and isinstance(self.bn2, SPC_SyncBN2d)):
+            raise hip_conv2d._rslo_error("BasicBlock.forward_eval_fused: %s has no fused eval path" % type(self.bn1).__name__)
+        out = hip_conv2d.conv_bn_eval(self.conv1, self.bn1, x, slope)
+        return hip_conv2d.conv_bn_eval(self.conv2, self.bn2, out, slope, residual=identity)
+
     def forward(self, x):
         pair = isinstance(x, (list, tuple))
         if (not pair or x[1] is None) and self._fused_node_ok(x[0] if pair else x):

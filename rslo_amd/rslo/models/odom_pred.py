@@ -24,7 +24,7 @@ from rslo.layers.hip_conv2d import Conv2d
 from rslo.layers.MaskConv import MaskConv
 from rslo.models.odom_pred_base import OdomPredEncDecBase, conf_trunk
 from rslo.utils.pose_utils import rotate_vec_by_q
-from rslo.layers.SparseConv import FusedSequential
+from rslo.layers.SparseConv import FusedSequential, SPC_SyncBN2d
 from torchplus.nn import Empty
 
 # with the ROCm apex stand-in the per-layer `num_batches_tracked += 1` launches are batched (compat/apex/parallel.py);
@@ -99,8 +99,70 @@ class UNOdomPredEncDecSVDTempMaskBase(OdomPredEncDecBase):
 
     @amp.float_function
     def forward(self, xs, tq_map_gt=None, local_spatial_features=None, **kwargs):
+        if self.__dict__.get("_eval_fused", False):      # set by rslo_amd.inference.OdometryRunner around its own calls
+            return self._forward_eval_fused(xs)
         with _defer_batch_counts():      # one multi-tensor add for all num_batches_tracked buffers of the head
             return self._forward(xs)
+
+    def eval_fused_unsupported(self):
+        """Why the eval path without autograd (_forward_eval_fused) cannot run this head, or None."""
+        if self.training:
+            return "the head is in training mode"
+        if self.use_svd:
+            return "use_svd: the rigid fit has no fused eval path"
+        if self.track_masks:
+            return "MaskSyncBN (track_masks): statistics over occupied cells have no fused eval path"
+        if self.odom_format != "rx+t" or not self.dense_predict:
+            return "odom_format %r / dense_predict %r" % (self.odom_format, self.dense_predict)
+        ok = self.__dict__.get("_fused_tail_static")
+        if ok is None:
+            self._fused_tail_ok(torch.zeros(1), torch.zeros(1))
+            ok = self.__dict__.get("_fused_tail_static")
+        if not ok:
+            return "the head's tail is not the fused softmax / vote tail"
+        for name, m in self.named_modules():
+            if isinstance(m, nn.modules.batchnorm._BatchNorm):
+                if not isinstance(m, SPC_SyncBN2d):
+                    return "%s: %s has no fused eval path" % (name, type(m).__name__)
+                if not m.track_running_stats or m.running_mean is None or m.running_var is None:
+                    return "%s: BatchNorm without running statistics" % name
+            if isinstance(m, (nn.Conv2d,)) or isinstance(m, nn.modules.batchnorm._BatchNorm):
+                for p in list(m.parameters(recurse=False)) + list(m.buffers(recurse=False)):
+                    if p.is_floating_point() and p.dtype != torch.float32:
+                        return "%s: dtype %s (the fused eval path is fp32)" % (name, p.dtype)
+        return None
+
+    def _forward_eval_fused(self, x):
+        """Eval mode, no autograd, hand-written kernels only: x [B, 2C, H, W] = [previous | current] BEV maps -> the
+        translation / rotation predictions of the pair, as _forward computes them in eval mode.  Each conv -> BN ->
+        activation is one launch (FusedSequential / BasicBlock .forward_eval_fused); the decoder inputs are
+        rslo_cat_upsample_fwd, the tail the same fused kernels as _forward (q normalisation, confidence softmaxes, vote,
+        pose tail).  The pyramid predictions and the temperature-20 weights only feed the loss and the testing extras:
+        not computed."""
+        from rslo_amd import capi
+        if isinstance(x, (list, tuple)):
+            raise capi.RsloHipError("_forward_eval_fused takes the [B, 2C, H, W] pair map")
+        x = x.contiguous()
+        _, _, _, outside = capi.bev_channel_sums(x, 2, masks=True)       # occupancy of the first frame of the pair
+        ups = []
+        for blk, skip in zip(self.blocks, self.skip_blocks):
+            x = blk.forward_eval_fused(x)
+            ups.append(skip.forward_eval_fused(x))
+        for i, deblock in enumerate(self.deblocks):
+            up = list(deblock.children())[0]
+            if not (isinstance(up, nn.Upsample) and up.mode == "nearest" and up.size is None
+                    and float(up.scale_factor) == int(up.scale_factor)):
+                raise capi.RsloHipError("_forward_eval_fused: deblock %d does not start with a nearest integer upsampling" % i)
+            x = deblock.forward_eval_fused(capi.cat_upsample_fwd(x, ups[-(i + 1)].contiguous(), int(up.scale_factor)), 1)
+        tq_map = capi.tq_normalize_fwd(self.tq_map_conv.forward_eval_fused(x))
+        t_logit = self.t_map_conf.conf_model.forward_eval_fused(x)
+        r_logit = self.q_map_conf.conf_model.forward_eval_fused(x)
+        t_conf, r_conf, _ = capi.conf_softmax_fwd(t_logit, r_logit, outside, 20.0)
+        _, vs, origin = _grid_geometry([1, tq_map.shape[2], tq_map.shape[3]], self.point_cloud_range)
+        _, odom, _ = capi.vote_fwd(tq_map, t_conf, r_conf, tuple(float(np.float32(v)) for v in origin),
+                                   tuple(float(np.float32(v)) for v in vs))
+        t, r = capi.pose_tail_fwd(odom)
+        return {"translation_preds": [t], "rotation_preds": [r]}
 
     def _forward(self, xs):
         if not isinstance(xs, list):

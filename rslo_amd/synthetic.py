@@ -115,3 +115,16 @@ def small_cloud(n=4000, seed=0, extent=(20.0, 10.0, 2.0)):
     nrm = r.normal(size=(n, 3))
     nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
     return np.concatenate([xyz, r.random((n, 1)), nrm], 1).astype(np.float32)
+
+
+def sequence_scan(i, seed=0, n_el=64, n_az=2083):
+    """Scan i of a synthetic drive through one world (streaming odometry, scripts/odometry_stream.py): the sensor
+    advances 0.8-1.2 m per scan with a slowly varying heading (a few tenths of a degree per scan, from `seed`), so
+    consecutive scans overlap like a KITTI sequence at 10 Hz."""
+    r = np.random.default_rng(5000 + seed)
+    steps = r.uniform(0.8, 1.2, i + 1)
+    dyaw = np.deg2rad(r.uniform(-0.4, 0.4, i + 1))
+    yaw = np.cumsum(dyaw) - dyaw[0]
+    x = float(np.sum(steps[1:] * np.cos(yaw[1:]))) if i > 0 else 0.0
+    y = float(np.sum(steps[1:] * np.sin(yaw[1:]))) if i > 0 else 0.0
+    return scan(n_az, n_el, (x, y), float(yaw[i]), scan_seed=7 * seed + 3 * i + 1)

@@ -241,3 +241,29 @@ class ExamplePrefetcher:
             self._in.put(None)
         for t in self._threads:
             t.join(timeout=10)
+
+
+def calibrate_head_bn(net, pair, seed=9):
+    """Eval-mode statistics for a freshly initialised network (the streaming odometry tests / scripts): every BatchNorm of
+    the head takes the mean / variance of its input on the frame pair `pair` (two clouds) as running statistics, and
+    affine parameters around (1, 0).  With the initial statistics (0 / 1) the eval activations grow by orders of
+    magnitude per stage and the poses are meaningless."""
+    head = net.odom_predictor
+    bns = [m for m in head.modules() if isinstance(m, torch.nn.modules.batchnorm._BatchNorm)]
+
+    def hook(mod, inputs):
+        t = inputs[0][0] if isinstance(inputs[0], (list, tuple)) else inputs[0]
+        mod.running_mean.copy_(t.mean((0, 2, 3)))
+        mod.running_var.copy_(t.var((0, 2, 3)) + 1e-2)
+    hs = [b.register_forward_pre_hook(hook) for b in bns]
+    try:
+        with torch.no_grad():
+            net(make_example(net, [list(pair)]))
+    finally:
+        for h in hs:
+            h.remove()
+    gen = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for b in bns:
+            b.weight.copy_(torch.rand(b.weight.shape, generator=gen) * 0.5 + 0.75)
+            b.bias.copy_(torch.randn(b.bias.shape, generator=gen) * 0.1)

@@ -1,0 +1,190 @@
+"""Streaming odometry in eval mode: the eager reference loop against rslo_amd.inference.OdometryRunner.
+
+    python scripts/odometry_stream.py --scans 200 --warmup 20 --seed 0 [--out profiles/odometry_stream_eager_vs_runner.json]
+    python scripts/odometry_stream.py --save-scans /tmp/drive.npz --scans 60 --warmup 5
+    python scripts/odometry_stream.py --runner-only --load-scans /tmp/drive.npz --scans 20 --warmup 5   # under rocprofv3
+    python scripts/odometry_stream.py --launches A_kernel_stats.csv B_kernel_stats.csv --scans-a 20 --scans-b 60
+
+A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
+scan by scan to
+  (a) the eager loop of evaluate.py:363-408: the example of scan i is built from frames (max(i-1, 0), i) the way the
+      dataset builds it (kitti_dataset_hdf5.py:184-185, workload.make_example) and `net(example)` runs under no_grad;
+  (b) the runner: submit one scan ahead, run, no host read.
+Both are timed with device events over --scans scans after --warmup scans; one JSON line is printed.
+--launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
+(their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
+import argparse
+import csv
+import json
+import os
+import re
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _scan(args):
+    from rslo_amd import synthetic
+    i, seed = args
+    return synthetic.sequence_scan(i, seed=seed)
+
+
+def make_scans(n, seed, workers):
+    """The scans of the drive, ray-cast on `workers` processes (about a second of numpy per scan)."""
+    if workers <= 1:
+        return [_scan((i, seed)) for i in range(n)]
+    import multiprocessing as mp
+    with mp.get_context("spawn").Pool(workers) as pool:
+        return pool.map(_scan, [(i, seed) for i in range(n)])
+
+
+def _kernel_counts(path):
+    out = {}
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            out[row["Name"]] = out.get(row["Name"], 0) + int(row["Calls"])
+    return out
+
+
+def _hand_written_names():
+    """The text of rslo_amd/csrc: a kernel is hand-written when its name is defined there."""
+    import glob
+    return "\n".join(open(f).read() for f in glob.glob(os.path.join(ROOT, "rslo_amd", "csrc", "*.hip")))
+
+
+def _is_hand_written(name, src):
+    base = re.split(r"[<(]", name[5:] if name.startswith("void ") else name, 1)[0].strip()
+    return bool(re.match(r"^\w+$", base)) and re.search(r"\b%s\b" % base, src) is not None
+
+
+def launches(a_csv, b_csv, n_a, n_b):
+    a, b = _kernel_counts(a_csv), _kernel_counts(b_csv)
+    per = {k: (b.get(k, 0) - a.get(k, 0)) / float(n_b - n_a) for k in set(a) | set(b)}
+    per = {k: v for k, v in per.items() if abs(v) > 1e-9}
+    names = _hand_written_names()
+    foreign = {k: v for k, v in per.items() if not _is_hand_written(k, names)}
+    return {"launches_per_scan": round(sum(per.values()), 2),
+            "hand_written_per_scan": round(sum(v for k, v in per.items() if _is_hand_written(k, names)), 2),
+            "hand_written_kernels_per_scan": {k[:120]: round(v, 2) for k, v in sorted(per.items(), key=lambda kv: -kv[1])
+                                              if _is_hand_written(k, names)},
+            "other_per_scan": {k[:160]: round(v, 2) for k, v in sorted(foreign.items(), key=lambda kv: -kv[1])},
+            "miopen_kernels": sorted(k[:160] for k in per if "miopen" in k.lower() or "MIOpen" in k),
+            "scans_a": n_a, "scans_b": n_b}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scans", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--workers", type=int, default=14)
+    ap.add_argument("--runner-only", action="store_true")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--launches", nargs=2, default=None)
+    ap.add_argument("--scans-a", type=int, default=20)
+    ap.add_argument("--scans-b", type=int, default=60)
+    ap.add_argument("--save-scans", default=None, help="write the drive's scans to this .npz and stop")
+    ap.add_argument("--load-scans", default=None, help="read the scans from a --save-scans file (profiled runs)")
+    args = ap.parse_args()
+    if args.launches:
+        res = launches(args.launches[0], args.launches[1], args.scans_a, args.scans_b)
+        line = json.dumps(res)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
+
+    t0 = time.time()
+    n_scans = args.warmup + args.scans
+    if args.load_scans:
+        import numpy as np
+        with np.load(args.load_scans) as z:
+            clouds = [z["s%d" % i] for i in range(n_scans)]
+    else:
+        clouds = make_scans(n_scans, args.seed, args.workers)
+    if args.save_scans:
+        import numpy as np
+        np.savez(args.save_scans, **{"s%d" % i: c for i, c in enumerate(clouds)})
+        return
+    t_scans = time.time() - t0
+    import torch
+    import rslo_amd  # noqa: F401
+    from rslo_amd import inference, workload
+    torch.manual_seed(args.seed)
+    net, _ = workload.build_network()
+    net.eval()
+    dev = torch.device("cuda", 0)
+    scans = [torch.from_numpy(c).to(dev) for c in clouds]
+    if not args.runner_only:       # (a profiled run keeps the eager pass -- and its library kernels -- out of the trace)
+        workload.calibrate_head_bn(net, (scans[0], scans[1]))      # eval statistics: poses of a sane magnitude
+    W, N = args.warmup, args.scans
+    res = {"metric": "odometry_stream_ms_per_scan", "scans": N, "warmup": W, "seed": args.seed,
+           "points_per_scan": int(sum(c.shape[0] for c in clouds) / len(clouds)), "scan_generation_s": round(t_scans, 1)}
+
+    def timed(loop):
+        loop(range(W))
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        h0 = time.perf_counter()
+        e0.record()
+        loop(range(W, W + N))
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / N, (time.perf_counter() - h0) * 1e3 / N
+
+    if not args.runner_only:
+        def eager(rng):
+            with torch.no_grad():
+                for i in rng:
+                    out = net(workload.make_example(net, [[scans[max(i - 1, 0)], scans[i]]]))
+                    out["translation_preds"], out["rotation_preds"]
+        res["eager_ms_per_scan"], res["eager_host_ms_per_scan"] = [round(v, 3) for v in timed(eager)]
+
+    runner = inference.OdometryRunner(net)
+    pend = {}
+
+    def run(rng):
+        rng = list(rng)
+        for k, i in enumerate(rng):
+            if i not in pend:
+                pend[i] = runner.submit(scans[i])
+            if k + 1 < len(rng) and rng[k + 1] not in pend:
+                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])      # one scan ahead
+            runner.run(pend.pop(i))
+    res["runner_ms_per_scan"], res["runner_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+    # the pair map: the two device copies per scan, measured on their own
+    C = runner._pair.shape[1] // 2
+    bev = torch.empty_like(runner._pair[:, C:])
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(100):
+        runner._pair[:, :C].copy_(runner._pair[:, C:])
+        runner._pair[:, C:].copy_(bev)
+    e1.record()
+    e1.synchronize()
+    res["pair_map_copies_ms_per_scan"] = round(e0.elapsed_time(e1) / 100, 4)
+    res["pair_map_bytes_per_scan"] = int(2 * 2 * bev.numel() * 4)
+    res["runner_stats"] = dict(runner.stats)
+    res["encoder_runs_per_scan"] = round(runner.encoder.stats["runs"] / max(1, runner.stats["scans"]), 3)
+    if "eager_ms_per_scan" in res:
+        res["speedup"] = round(res["eager_ms_per_scan"] / res["runner_ms_per_scan"], 2)
+    # the two paths on the same drive: the last scan's relative pose
+    if not args.runner_only:
+        i = W + N - 1
+        with torch.no_grad():
+            out = net(workload.make_example(net, [[scans[i - 1], scans[i]]]))
+        ref = torch.cat([out["translation_preds"][0], out["rotation_preds"][0]])
+        res["last_rel_max_rel_diff"] = float((runner.relative()[-1] - ref).abs().max() / ref.abs().max())
+    runner.close()
+    line = json.dumps(res)
+    print(line)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
