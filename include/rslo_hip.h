@@ -851,6 +851,26 @@ RSLO_API int rslo_peer_capture_end(void *comm, int *n_exchanges);
 RSLO_API int rslo_peer_replay_prepare(void *comm, int n_exchanges, void *stream);
 RSLO_API int rslo_peer_destroy(void *comm);
 
+/* ------------------------------------------------------------------------------------
+ * Point normals of a raw scan (csrc/normals.hip).  Replaces the offline step of script/create_hdf5.py:130-147:
+ *     pcd.estimate_normals(KDTreeSearchParamHybrid(radius=0.6, max_nn=30)); pcd.orient_normals_towards_camera_location((0,0,0))
+ * Open3D is not part of the reference tree: the rules are recalled from it, not verified against it; their float64
+ * restatement is rslo_amd/normals.py.  For every point i of ONE cloud:
+ *   neighbours = the points j with |p_j - p_i|^2 < radius^2 (strict, i included), at most the max_nn nearest, ties to
+ *   the lower index; counts[i] = how many.  counts[i] >= 3: normals[i] = unit eigenvector of the smallest eigenvalue of
+ *   the neighbours' covariance, else (0, 0, 1); flipped when it points away from the viewpoint (h_viewpoint3: three HOST
+ *   floats read during the call, NULL = the origin).  zero_vertical != 0 applies the reader's rule
+ *   (rslo/data/kitti_dataset_hdf5.py:197-198): a component whose absolute value equals that of (0, 0, 1) becomes 0.
+ *   A point with a non-finite coordinate is nobody's neighbour: counts = 0, normal = 0.
+ * points is read as points[i * stride_floats + 0..2] (stride_floats >= 3): a [P,4] scan or a [P,7] cloud needs no copy.
+ * max_nn in 3..32, radius > 0.  N == 0 is a successful no-op.  counts may be NULL.  Six launches on `stream`, no host
+ * read, nothing allocated: capturable.  Two calls on the same input give the same bits.
+ * ------------------------------------------------------------------------------------ */
+RSLO_API size_t rslo_normals_ws_bytes(int N);
+RSLO_API int rslo_estimate_normals(const float *points, int stride_floats, int N, float radius, int max_nn,
+                                   const float *h_viewpoint3, int zero_vertical, float *normals /*[N,3]*/,
+                                   int32_t *counts /*[N]*/, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

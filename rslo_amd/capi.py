@@ -188,6 +188,8 @@ SIGNATURES = {
     "rslo_conv2d_fwd_s2_bn": (C.c_int, [_vp] * 6 + [_i, _i, _i, _i, _i, _i, _i, _f, _vp, _vp]),
     "rslo_bn_fold_many": (C.c_int, [_vp, _i, _i, _vp]),
     "rslo_pose_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "rslo_normals_ws_bytes": (_sz, [_i]),
+    "rslo_estimate_normals": (C.c_int, [_vp, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -956,6 +958,58 @@ def chamfer_nn(xyz1, xyz2, dist=None, idx=None, ncnt=None, mcnt=None, method=Non
                                _ptr(dist, torch.float32, "dist"), _ptr(idx, torch.int32, "idx"), _ptr(ws), wsb,
                                _stream()), entry)
     return dist, idx
+
+
+# --------------------------------------------------------------------------------------
+# point normals of a raw scan (csrc/normals.hip)
+# --------------------------------------------------------------------------------------
+def estimate_normals(points, radius=0.6, max_nn=30, viewpoint=None, zero_vertical=False, out=None, counts=None, ws=None):
+    """points: contiguous fp32 CUDA [P, F >= 3] (x, y, z first; read in place through its row stride).  Returns
+    (normals [P, 3] fp32, counts [P] int32): script/create_hdf5.py:130-147 on the current stream (rules: include/rslo_hip.h).
+    out / counts / ws: optional preallocated outputs and workspace (ws: uint8, >= rslo_normals_ws_bytes(P))."""
+    src = _ptr(points, torch.float32, "points")
+    if points.dim() != 2 or points.shape[1] < 3:
+        raise RsloHipError("estimate_normals: points must be [P, F >= 3], got %s" % (tuple(points.shape),))
+    P, F = points.shape
+    dev = points.device
+    if out is None:
+        out = torch.empty((P, 3), dtype=torch.float32, device=dev)
+    if counts is None:
+        counts = torch.empty((P,), dtype=torch.int32, device=dev)
+    if out.shape != (P, 3) or counts.shape != (P,):
+        raise RsloHipError("estimate_normals: out must be [P, 3] and counts [P]")
+    wsb = lib().rslo_normals_ws_bytes(P)
+    if ws is None:
+        ws = _ws(wsb, dev)
+    vp = None if viewpoint is None else _F3(*[float(v) for v in viewpoint])
+    _chk(lib().rslo_estimate_normals(src, F, P, float(radius), int(max_nn), vp, int(bool(zero_vertical)),
+                                     _ptr(out, torch.float32, "out"), _ptr(counts, torch.int32, "counts"), _ptr(ws),
+                                     ws.numel() * ws.element_size(), _stream()), "rslo_estimate_normals")
+    return out, counts
+
+
+def append_normals(points_xyzi, radius=0.6, max_nn=30, viewpoint=None, out=None, counts=None, ws=None, normals=None):
+    """A raw [P, 4] scan (or [P, 3]: intensity 0) -> the [P, 7] cloud the reference's reader produces
+    (kitti_dataset_hdf5.py:253-261): cat(x, y, z, intensity, normals with the reader's zero_vertical rule).
+    out: optional [>= P, 7] fp32 buffer whose first P rows are written and returned; normals / counts / ws: optional
+    [>= P, 3] fp32, [>= P] int32 and workspace buffers (a caller that must not allocate passes all four)."""
+    _ptr(points_xyzi, torch.float32, "points")
+    if points_xyzi.dim() != 2 or points_xyzi.shape[1] not in (3, 4):
+        raise RsloHipError("append_normals: a raw scan is [P, 4] (x, y, z, intensity) or [P, 3], got %s"
+                           % (tuple(points_xyzi.shape),))
+    P, F = points_xyzi.shape
+    if out is None:
+        out = torch.empty((P, 7), dtype=torch.float32, device=points_xyzi.device)
+    if out.dim() != 2 or out.shape[1] != 7 or out.shape[0] < P or not out.is_contiguous():
+        raise RsloHipError("append_normals: out must be a contiguous [>= P, 7] buffer")
+    cloud = out[:P]
+    cloud[:, :F].copy_(points_xyzi)
+    if F == 3:
+        cloud[:, 3].zero_()
+    nrm, _ = estimate_normals(points_xyzi, radius, max_nn, viewpoint, True, out=None if normals is None else normals[:P],
+                              counts=None if counts is None else counts[:P], ws=ws)
+    cloud[:, 4:].copy_(nrm)
+    return cloud
 
 
 def chamfer_grad(xyz1, xyz2, graddist1, idx1, g1=None, g2=None):

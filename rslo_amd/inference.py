@@ -39,8 +39,12 @@ class EncoderGraphRunner:
     `bev` / `cov` are static tensors of the job's arena: consume (or copy) them before that arena's next run()."""
 
     def __init__(self, net_like, max_voxels, device="cuda", point_capacity=160000, arenas=4, frames_per_job=1,
-                 with_cov=True):
+                 with_cov=True, pre_plan=None):
         self.net = net_like
+        # optional hook of the helper thread: pre_plan(cloud, arena, k) -> the [P,F] cloud to plan, issued on the plan stream
+        # immediately in front of the structure work of frame k of a job (behind the wait for the arena's previous frame), so
+        # it may write per-arena buffers.  It must not synchronise, allocate per call or open a stream.  None: off.
+        self.pre_plan = pre_plan
         self.with_cov = bool(with_cov)      # False: the covariance branch is not issued (run() returns cov = None)
         self.enc = net_like.middle_feature_extractor
         if self.enc.training:
@@ -101,6 +105,9 @@ class EncoderGraphRunner:
                 with torch.cuda.stream(side):
                     if prev is not None:
                         side.wait_event(prev)               # the arena's previous frame has been consumed on the GPU
+                    if self.pre_plan is not None:
+                        a = h.slot % self.planner.n_arenas
+                        clouds = [self.pre_plan(c, a, k) for k, c in enumerate(clouds)]
                     h.job = self.planner.submit([[c] for c in clouds], with_pairs=False, slot=h.slot,
                                                 point_capacity=self.point_capacity)
             except Exception as e:      # surfaces in run()
@@ -229,10 +236,22 @@ class OdometryRunner:
       graph captured again.  A replaced parameter object, or a write through `.data` (it bumps no version counter):
       call refresh_weights(force=True).
     * Handles: the outstanding-handle rule of EncoderGraphRunner (fewer than `arenas` submitted and not yet run).
+    * Raw scans: normals="estimate" takes what a LiDAR produces, [P, 4] (x, y, z, intensity; or [P, 3], intensity 0):
+      the helper thread builds the [P, 7] cloud with capi.append_normals (csrc/normals.hip: the offline step of
+      script/create_hdf5.py:130-147 with normal_radius / normal_max_nn, plus the reader's zero_vertical rule) on the plan
+      stream immediately in front of the scan's structure work, into buffers allocated once per arena.  No stream is
+      added and nothing synchronises.  normals="input" (the default) is the path above, unchanged.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
-    def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000):
+    def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
+                 normals="input", normal_radius=0.6, normal_max_nn=30):
         from rslo_amd import synthetic
+        if normals not in ("input", "estimate"):
+            raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
+        self.normals = normals
+        self.normal_radius, self.normal_max_nn = float(normal_radius), int(normal_max_nn)
+        if normals == "estimate" and not (3 <= self.normal_max_nn <= 32 and self.normal_radius > 0):
+            raise capi.RsloHipError("OdometryRunner: normal_max_nn must be in 3..32 and normal_radius positive")
         self.net = net
         self.head = net.odom_predictor
         if net.training or self.head.training:
@@ -249,9 +268,19 @@ class OdometryRunner:
         from rslo.layers import hip_conv2d
         self.operands = hip_conv2d.EvalOperands(self.head)
         self.encoder = EncoderGraphRunner(net, synthetic.MAX_VOXELS if max_voxels is None else max_voxels, self.device,
-                                          point_capacity=point_capacity, arenas=arenas, with_cov=False)
+                                          point_capacity=point_capacity, arenas=arenas, with_cov=False,
+                                          pre_plan=self._append_normals if normals == "estimate" else None)
         self.capacity = int(capacity)
         dev = self.device
+        self._raw = []             # normals="estimate": per arena (cloud [cap,7], normals [cap,3], counts [cap], workspace)
+        if normals == "estimate":
+            cap = int(point_capacity)
+            wsb = capi.lib().rslo_normals_ws_bytes(cap)
+            for _ in range(self.encoder.planner.n_arenas):
+                self._raw.append((torch.zeros((cap, 7), dtype=torch.float32, device=dev),
+                                  torch.zeros((cap, 3), dtype=torch.float32, device=dev),
+                                  torch.zeros((cap,), dtype=torch.int32, device=dev),
+                                  torch.empty((wsb,), dtype=torch.uint8, device=dev)))
         self._state = torch.zeros((7,), dtype=torch.float64, device=dev)
         self._count = torch.zeros((1,), dtype=torch.int32, device=dev)
         self._rel = torch.zeros((self.capacity, 7), dtype=torch.float32, device=dev)
@@ -263,7 +292,24 @@ class OdometryRunner:
                       "weight_refreshes": 0}
 
     def submit(self, cloud):
+        raw = torch.is_tensor(cloud) and cloud.dim() == 2 and cloud.shape[1] in (3, 4)
+        if self.normals == "input" and raw:
+            raise capi.RsloHipError("OdometryRunner.submit: a [P, %d] scan has no normals; this runner takes [P, 7] clouds -- "
+                                    "build it with normals=\"estimate\" to feed raw scans" % cloud.shape[1])
+        if self.normals == "estimate":
+            if not (raw and cloud.is_cuda and cloud.dtype == torch.float32 and cloud.is_contiguous()):
+                raise capi.RsloHipError("OdometryRunner.submit: normals=\"estimate\" takes contiguous fp32 CUDA [P, 4] (or "
+                                        "[P, 3]) scans, got %s" % (tuple(cloud.shape) if torch.is_tensor(cloud) else type(cloud),))
+            if cloud.shape[0] > self.encoder.point_capacity:
+                raise capi.RsloHipError("OdometryRunner.submit: the scan exceeds point_capacity = %d"
+                                        % self.encoder.point_capacity)
         return self.encoder.submit(cloud)
+
+    def _append_normals(self, scan, arena, k):
+        """pre-plan hook (helper thread, plan stream): raw scan -> the arena's [P, 7] cloud"""
+        cloud, nrm, cnt, ws = self._raw[arena]
+        return capi.append_normals(scan, self.normal_radius, self.normal_max_nn, None, out=cloud, counts=cnt, ws=ws,
+                                   normals=nrm)
 
     def close(self):
         self.encoder.close()

@@ -4,6 +4,7 @@
     python scripts/odometry_stream.py --save-scans /tmp/drive.npz --scans 60 --warmup 5
     python scripts/odometry_stream.py --runner-only --load-scans /tmp/drive.npz --scans 20 --warmup 5   # under rocprofv3
     python scripts/odometry_stream.py --launches A_kernel_stats.csv B_kernel_stats.csv --scans-a 20 --scans-b 60
+    python scripts/odometry_stream.py --raw --scans 200 --warmup 20 [--out profiles/odometry_stream_raw.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -11,6 +12,10 @@ scan by scan to
       dataset builds it (kitti_dataset_hdf5.py:184-185, workload.make_example) and `net(example)` runs under no_grad;
   (b) the runner: submit one scan ahead, run, no host read.
 Both are timed with device events over --scans scans after --warmup scans; one JSON line is printed.
+--raw: a third loop feeds the same scans stripped to [P, 4] (what a LiDAR produces) to a runner built with
+normals="estimate" (csrc/normals.hip on the plan stream) and reports its ms per scan, the distance of its trajectory
+from the [P, 7] run and the median angle between the estimated and the drive's analytic normals (a report, not a
+test: the analytic normals are exact only away from edges).
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -81,6 +86,7 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--workers", type=int, default=14)
     ap.add_argument("--runner-only", action="store_true")
+    ap.add_argument("--raw", action="store_true", help="also run the runner with normals=\"estimate\" on [P, 4] scans")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -178,7 +184,46 @@ def main():
             out = net(workload.make_example(net, [[scans[i - 1], scans[i]]]))
         ref = torch.cat([out["translation_preds"][0], out["rotation_preds"][0]])
         res["last_rel_max_rel_diff"] = float((runner.relative()[-1] - ref).abs().max() / ref.abs().max())
+    traj_input, rel_input = runner.trajectory().clone(), runner.relative().clone()
     runner.close()
+    if args.raw:
+        from rslo_amd import capi
+        raw_scans = [s[:, :4].contiguous() for s in scans]
+        raw = inference.OdometryRunner(net, normals="estimate")
+        pend.clear()
+
+        def run_raw(rng):
+            rng = list(rng)
+            for k, i in enumerate(rng):
+                if i not in pend:
+                    pend[i] = raw.submit(raw_scans[i])
+                if k + 1 < len(rng) and rng[k + 1] not in pend:
+                    pend[rng[k + 1]] = raw.submit(raw_scans[rng[k + 1]])
+                raw.run(pend.pop(i))
+        res["raw_ms_per_scan"], res["raw_host_ms_per_scan"] = [round(v, 3) for v in timed(run_raw)]
+        res["raw_minus_input_ms_per_scan"] = round(res["raw_ms_per_scan"] - res["runner_ms_per_scan"], 3)
+        d = (raw.trajectory() - traj_input)[:, :3].norm(dim=1)
+        path = (traj_input[1:, :3] - traj_input[:-1, :3]).norm(dim=1).sum()
+        res["raw_traj_max_dist_m"], res["raw_traj_end_dist_m"] = float(d.max()), float(d[-1])
+        res["input_traj_path_m"] = float(path)
+        dr = (raw.relative() - rel_input).abs().max(dim=1).values / rel_input.abs().max(dim=1).values
+        res["raw_rel_diff_median"], res["raw_rel_diff_max"] = float(dr.median()), float(dr.max())
+        raw.close()
+        # normals of one scan on their own: time of the six launches, agreement with the analytic normals
+        s0 = scans[W]
+        capi.estimate_normals(raw_scans[W], zero_vertical=True)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(20):
+            est, cnt = capi.estimate_normals(raw_scans[W], zero_vertical=True)
+        e1.record()
+        e1.synchronize()
+        res["normals_alone_ms_per_scan"] = round(e0.elapsed_time(e1) / 20, 4)
+        both = (s0[:, 4:7].norm(dim=1) > 0) & (est.norm(dim=1) > 0)
+        cosang = (s0[:, 4:7] * est)[both].sum(1).abs().clamp(max=1.0)
+        res["normals_median_angle_deg"] = float(torch.rad2deg(torch.acos(cosang)).median())
+        res["normals_compared_points"] = int(both.sum())
+        res["normals_points_with_fewer_than_3_neighbours"] = int((cnt < 3).sum())
     line = json.dumps(res)
     print(line)
     if args.out:
