@@ -114,10 +114,16 @@ RSLO_API int rslo_rulebook_conv_T(const int32_t *coords_in, int64_t N, int B, co
  * Supported channel counts: 1..64 on both sides.
  * ------------------------------------------------------------------------------------ */
 /*     row_order (int32 [n_out] or NULL): the order in which the table rows are grouped into the kernels' 16/32-row tiles
- *     (rslo_rulebook_row_order).  Purely a scheduling hint: out[o] is written for every o and does not depend on it. */
+ *     (rslo_rulebook_row_order).  Purely a scheduling hint: out[o] is written for every o and does not depend on it.
+ *     n_live_dev (device int32 word or NULL = all rows; rslo_spconv_fwd and rslo_spconv_fwd_split).  Round 6, the replayed
+ *     inference pass (evaluate.py:363-408 -> rslo/models/middle.py:219-245 per frame; rslo_amd/inference.py): a
+ *     capacity-laid-out rulebook has more rows than the scan has sites, the rows past the level's count being padding rows
+ *     (rslo_plan_encoder_pad_tails), and the count lives in a device word.  Workgroups whose rows all lie at or past
+ *     *n_live_dev return at once -- their output rows are left unwritten; nothing reads a padding row.  Ignored with a row
+ *     order. */
 RSLO_API int rslo_spconv_fwd(const float *in, int cin, const float *W, const float *bias, const int32_t *nbr,
                     const int32_t *row_order, int64_t n_out, int K, int cout, int flip_k, float act_slope,
-                    float *out, void *stream);
+                    float *out, const int32_t *n_live_dev, void *stream);
 RSLO_API int rslo_spconv_dgrad(const float *dout, int cout, const float *W, const int32_t *nbrT,
                       const int32_t *row_order, int64_t n_in, int K, int cin, int flip_k, float *din, void *stream);
 /*     W [K,Cin,Cout] -> Wt [K,Cout,Cin].  rslo_spconv_fwd(dout, Cout, Wt, NULL, nbrT, ...) then equals
@@ -145,19 +151,7 @@ RSLO_API int rslo_weight_split_many(const RsloWeightSplitDesc *desc_dev, int n_l
                                     void *stream);
 RSLO_API int rslo_spconv_fwd_split(const float *in, int cin, const void *Ws, const float *bias, const int32_t *nbr,
                                    const int32_t *row_order, int64_t n_out, int K, int cout, int flip_k,
-                                   float act_slope, float *out, void *stream);
-/*     Tiling of k_spconv_v6 behind rslo_spconv_fwd_split: a tile is 16*rbw rows (rbw 1, 2, 4) and ks waves (1, 2, 4) share
- *     it, each walking 1/ks of the tile's active kernel offsets; their accumulators are added through LDS in wave order
- *     (a fixed summation order, results within fp32 rounding of the one-wave form).  0 = the library chooses per layer
- *     shape (default: 32 rows and two waves except for 32 -> 32 channels).  Same as the switches spconv_rbw / spconv_ks. */
-RSLO_API void rslo_spconv_set_tiling(int rbw, int ks);
-/*     Round 6, the replayed inference pass (evaluate.py:363-408 -> rslo/models/middle.py:219-245 per frame; rslo_amd/inference.py):
- *     a capacity-laid-out rulebook has more rows than the scan has sites, the rows past the level's count being padding rows
- *     (rslo_plan_encoder_pad_tails), and the count lives in a device word.  rslo_spconv_set_live_rows(p) hands that word to the
- *     NEXT rslo_spconv_fwd / rslo_spconv_fwd_split launch (and only that one): workgroups whose rows all lie at or past *p
- *     return at once -- their output rows are left unwritten; nothing reads a padding row.  Ignored with a row order.
- *     Per calling thread. */
-RSLO_API void rslo_spconv_set_live_rows(const int32_t *n_live_dev);
+                                   float act_slope, float *out, const int32_t *n_live_dev, void *stream);
 /*     Tuning switches of the launch code.  The library reads NO environment variable: tile shapes and kernel variants that
  *     exist for A/B measurements and for the parity tests that pin every tiling against the oracle are set through these
  *     calls (process-wide; the defaults are the measured choices).  Names (rslo_tuning_name(i), i = 0 .. until NULL):
@@ -166,7 +160,11 @@ RSLO_API void rslo_spconv_set_live_rows(const int32_t *n_live_dev);
  *     spconv_v, spconv_wgrad_split, wgrad_xcd, vfe_lds, chamfer, chamfer_segments, dense_tiled, conv1x1_split, conv2d_fwd_wl
  *     (meanings: csrc/rslo_common.h RsloTune).  Every setting
  *     computes the same products; only tiling, summation grouping and launch geometry change.  Unknown name -> RSLO_EINVAL.
- *     (The reference has no counterpart: spconv / cuDNN pick their algorithms internally.) */
+ *     (The reference has no counterpart: spconv / cuDNN pick their algorithms internally.)
+ *     spconv_rbw / spconv_ks, the tiling of k_spconv_v6 behind rslo_spconv_fwd_split: a tile is 16*rbw rows (rbw 1, 2, 4) and
+ *     ks waves (1, 2, 4) share it, each walking 1/ks of the tile's active kernel offsets; their accumulators are added
+ *     through LDS in wave order (a fixed summation order, results within fp32 rounding of the one-wave form).  0 = the
+ *     library chooses per layer shape (default: 32 rows and two waves except for 32 -> 32 channels). */
 RSLO_API int rslo_tuning_set(const char *name, int value);
 RSLO_API int rslo_tuning_get(const char *name, int *value);
 RSLO_API const char *rslo_tuning_name(int index);

@@ -34,15 +34,13 @@ SIGNATURES = {
     "rslo_conv_out_coords": (C.c_int, [_vp, _vp, _i64, _i, _vp, _vp, _i64, _vp]),
     "rslo_rulebook_conv": (C.c_int, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
     "rslo_rulebook_conv_T": (C.c_int, [_vp, _i64, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
-    "rslo_spconv_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _vp, _vp]),
+    "rslo_spconv_fwd": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _f, _vp, _vp, _vp]),
     "rslo_spconv_dgrad": (C.c_int, [_vp, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "rslo_weight_transpose": (C.c_int, [_vp, _i, _i, _i, _vp, _vp]),
     "rslo_weight_split_bytes": (_sz, [_i, _i, _i]),
     "rslo_weight_split": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "rslo_weight_split_many": (C.c_int, [_vp, _i, _i64, _vp]),
-    "rslo_spconv_fwd_split": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, C.c_float, _vp, _vp]),
-    "rslo_spconv_set_tiling": (None, [_i, _i]),
-    "rslo_spconv_set_live_rows": (None, [_vp]),
+    "rslo_spconv_fwd_split": (C.c_int, [_vp, _i, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, C.c_float, _vp, _vp, _vp]),
     "rslo_peer_create_host": (C.c_int, [C.c_char_p, _i, _i, _i, C.POINTER(C.c_void_p)]),
     "rslo_peer_host_unlink": (C.c_int, [_vp]),
     "rslo_peer_ipc_handle_bytes": (C.c_int, []),
@@ -594,11 +592,11 @@ def spconv_fwd_split(x, Ws, bias, nbr, cin, cout, flip_k=False, act_slope=1.0, o
     if x.shape[1] != cin:
         raise RsloHipError("spconv_fwd_split: shape mismatch")
     out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-    if n_live is not None and order is None:       # consumed by the launch that follows
-        lib().rslo_spconv_set_live_rows(_ptr(n_live, torch.int32, "n_live"))
     _chk(lib().rslo_spconv_fwd_split(_ptr(x, torch.float32, "x"), cin, _ptr(Ws), _ptr(bias, torch.float32, "bias"),
                                      _ptr(nbr, torch.int32, "nbr"), _ptr(order, torch.int32, "order"), n_out, K, cout,
-                                     int(flip_k), float(act_slope), _ptr(out), _stream()), "rslo_spconv_fwd_split")
+                                     int(flip_k), float(act_slope), _ptr(out),
+                                     _ptr(n_live, torch.int32, "n_live") if order is None else None, _stream()),
+         "rslo_spconv_fwd_split")
     return out
 
 
@@ -634,8 +632,8 @@ def _splittable(cin, cout):
 
 def spconv_fwd(x, W, bias, nbr, flip_k=False, act_slope=1.0, order=None, n_live=None):
     """x [Nin,Cin], W [K,Cin,Cout], nbr [Nout,K] -> [Nout,Cout].  order: optional rulebook_row_order(nbr).
-    n_live: device int32 word = how many leading rows of a capacity-laid-out table are real (rslo_spconv_set_live_rows);
-    rows past it are left unwritten."""
+    n_live: device int32 word = how many leading rows of a capacity-laid-out table are real (n_live_dev of
+    rslo_spconv_fwd / rslo_spconv_fwd_split); rows past it are left unwritten.  Ignored with an order."""
     n_out, K = nbr.shape
     Kw, cin, cout = W.shape
     if Kw != K or x.shape[1] != cin:
@@ -650,12 +648,12 @@ def spconv_fwd_direct(x, W, bias, nbr, flip_k=False, act_slope=1.0, order=None, 
     n_out, K = nbr.shape
     Kw, cin, cout = W.shape
     out = torch.empty((n_out, cout), dtype=torch.float32, device=x.device)
-    if n_live is not None and order is None:       # consumed by the launch that follows
-        lib().rslo_spconv_set_live_rows(_ptr(n_live, torch.int32, "n_live"))
     _chk(lib().rslo_spconv_fwd(_ptr(x, torch.float32, "x"), cin, _ptr(W, torch.float32, "W"),
                                _ptr(bias, torch.float32, "bias"), _ptr(nbr, torch.int32, "nbr"),
                                _ptr(order, torch.int32, "order"), n_out, K, cout,
-                               int(flip_k), float(act_slope), _ptr(out), _stream()), "rslo_spconv_fwd")
+                               int(flip_k), float(act_slope), _ptr(out),
+                               _ptr(n_live, torch.int32, "n_live") if order is None else None, _stream()),
+         "rslo_spconv_fwd")
     return out
 
 

@@ -894,6 +894,39 @@ int conv2d_wl_wanted(int B, int cin, int cout, int H, int W);
 int conv2d_wl_launch(const float *in, const void *Ws, const float *bias, const float *res, int B, int cin, int cout, int H,
                      int W, float *out, void *stream);
 
+// Geometry of a k_conv2d_fwd launch (tr-row tiles, mtw 16-channel blocks per wave); returns the grid.  The byte counts
+// feed the XCD split: input bytes count the halo re-reads of the row tiles ((tr + 2) / tr), bf16-operand weights are one
+// plane of three.
+static dim3 conv2d_fwd_geom(Conv2dFwdGeom *gm, int B, int cin, int cout, int H, int W, int tr, int mtw, double w_bytes,
+                            double in_bytes) {
+  gm->B = B; gm->cin = cin; gm->cout = cout; gm->H = H; gm->W = W;
+  gm->tiles_x = (int)rslo_cdiv(W, 16);
+  gm->tiles_y = (int)rslo_cdiv(H, tr);
+  gm->npix = B * gm->tiles_x * gm->tiles_y;
+  gm->ny = cout / (32 * mtw);
+  gm->xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_FWD_XSC, gm->ny, w_bytes, in_bytes);
+  return conv2d_xcd_grid(gm->xsc, gm->npix, gm->ny);
+}
+
+// Default variant of the 4-row / one-block-per-wave configuration; wgs4 = workgroups of the launch.
+// Two wave sets per workgroup (channel chunks alternate between them) when the launch leaves CUs empty and the chain
+// is long.  Measured (scripts/bench_conv2d_fwd.py): 256 -> 256 at 12x22 (192 workgroups, 8 chunks) 23.7 -> 19.0 us;
+// 128 -> 128 at 24x44 (288 workgroups, 4 chunks) 17.1 -> 21.4 us, 512 -> 128 at 24x44 50.9 -> 61.0 us, 48x88 and larger
+// 44 -> 62 us: every wave streams its own weight operands (27 KB per chunk) through the CU's vector L1, and a second wave
+// set doubles that traffic wherever the CUs are already occupied.
+// Maps of >= 512 workgroups (2 or more per CU): the one-tap-ahead variant at 96 registers keeps 5 workgroups resident
+// per CU instead of 2 (20 waves hide the staging chain; the 9-tap weight prefetch is not needed with them; the 32-bit
+// input offsets are what lets it fit with one spilled register).  Measured (scripts/conv2d_cfgs.sh, B = 4, the
+// 9-tap kernel -> 4 workgroups per CU at 104 registers -> 5): 128 -> 128 at 48x88 41.6 -> 38.0 -> 35.7 us, 64 -> 64 at
+// 96x176 44.1 -> 36.4 -> 35.2, 64 -> 192 at 96x176 114.8 -> 92.2 -> 87.8, 192 -> 64 103.8 -> 94.1 -> 89.7, 256 -> 64 at
+// 48x88 (576 workgroups) 47.0 -> 42.1; 128 -> 128 at 24x44 (288 workgroups) 16.5 -> 17.4 and 256 -> 256 at 12x22
+// 18.6 -> 25.0 keep the 9-tap kernel.
+enum C2fVariant { C2F_TWO_SETS, C2F_LEAN, C2F_NINE_TAP };
+static C2fVariant conv2d_fwd_default_variant(int cin, int64_t wgs4) {
+  if (cin >= 256 && wgs4 <= 200) return C2F_TWO_SETS;
+  return wgs4 >= 512 ? C2F_LEAN : C2F_NINE_TAP;
+}
+
 static int conv2d_fwd_launch(const float *in, const void *Ws, const float *bias, int B, int cin, int cout, int H, int W,
                              float *out, void *stream, bool lp, const float *res) {
   int tr, mtw;
@@ -903,47 +936,24 @@ static int conv2d_fwd_launch(const float *in, const void *Ws, const float *bias,
   if (!lp && !rslo_tune(RSLO_TUNE_CONV2D_FWD_TR) && !rslo_tune(RSLO_TUNE_CONV2D_FWD_MTW) && !g_c2f_occ &&
       !rslo_tune(RSLO_TUNE_CONV2D_FWD_KC) && rslo_tune(RSLO_TUNE_CONV2D_FWD_LEAN) < 0 && conv2d_wl_wanted(B, cin, cout, H, W))
     return conv2d_wl_launch(in, Ws, bias, res, B, cin, cout, H, W, out, stream);
+  if (lp) { tr = 4; mtw = 1; }       // bf16 operands (C4): the default tile configuration only
   Conv2dFwdGeom gm;
-  gm.B = B; gm.cin = cin; gm.cout = cout; gm.H = H; gm.W = W;
   gm.res = res;
-  gm.tiles_x = (int)rslo_cdiv(W, 16);
-  gm.tiles_y = (int)rslo_cdiv(H, tr);
-  // input bytes count the halo re-reads of the row tiles ((tr + 2) / tr); bf16-operand weights are one plane of three
-  const double w_bytes = (lp ? 1.0 : 3.0) * 18.0 * cin * cout, in_bytes = 4.0 * B * cin * H * W * 1.5;
-  gm.npix = B * gm.tiles_x * gm.tiles_y;
-  gm.ny = cout / (32 * mtw);
-  gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_FWD_XSC, gm.ny, w_bytes, in_bytes);
-  const dim3 grid = conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
+  const dim3 grid = conv2d_fwd_geom(&gm, B, cin, cout, H, W, tr, mtw, (lp ? 1.0 : 3.0) * 18.0 * cin * cout,
+                                    4.0 * B * cin * H * W * 1.5);
   hipStream_t st = (hipStream_t)stream;
   const unsigned short *ws = (const unsigned short *)Ws;
-  // two wave sets per workgroup (channel chunks alternate between them) when the launch leaves CUs empty and the chain
-  // is long (conv2d_fwd_kc = 1 | 2 forces it).  Measured (scripts/bench_conv2d_fwd.py): 256 -> 256 at 12x22 (192
-  // workgroups, 8 chunks) 23.7 -> 19.0 us; 128 -> 128 at 24x44 (288 workgroups, 4 chunks) 17.1 -> 21.4 us, 512 -> 128 at
-  // 24x44 50.9 -> 61.0 us, 48x88 and larger 44 -> 62 us: every wave streams its own weight operands (27 KB per chunk)
-  // through the CU's vector L1, and a second wave set doubles that traffic wherever the CUs are already occupied
-  const int kc_env = rslo_tune(RSLO_TUNE_CONV2D_FWD_KC);
-  const int64_t wgs4 = (int64_t)B * gm.tiles_x * rslo_cdiv(H, 4) * (cout / 32);
-  const bool kc2 = cin >= 64 && (kc_env ? kc_env == 2 : (cin >= 256 && wgs4 <= 200));
-  if (lp) {       // bf16 operands (C4): the default tile configuration only
-    gm.tiles_y = (int)rslo_cdiv(H, 4);
-    gm.npix = B * gm.tiles_x * gm.tiles_y;
-    gm.ny = cout / 32;
-    gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_FWD_XSC, gm.ny, w_bytes, in_bytes);
-    const dim3 grid1 = conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
-    if (kc2) hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, true, 2>), grid1, dim3(512), 0, st, in, ws, bias, gm, out);
-    else hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, true>), grid1, dim3(256), 0, st, in, ws, bias, gm, out);
+  // conv2d_fwd_kc = 1 | 2 forces one | two wave sets, conv2d_fwd_lean = 0 / 1 forces the lean variant off / on
+  const int kc_env = rslo_tune(RSLO_TUNE_CONV2D_FWD_KC), lean_env = rslo_tune(RSLO_TUNE_CONV2D_FWD_LEAN);
+  const C2fVariant dflt = conv2d_fwd_default_variant(cin, (int64_t)B * gm.tiles_x * rslo_cdiv(H, 4) * (cout / 32));
+  const bool kc2 = kc_env ? (kc_env == 2 && cin >= 64) : dflt == C2F_TWO_SETS;
+  if (lp) {
+    if (kc2) hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, true, 2>), grid, dim3(512), 0, st, in, ws, bias, gm, out);
+    else hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, true>), grid, dim3(256), 0, st, in, ws, bias, gm, out);
     RSLO_CHECK_LAUNCH("k_conv2d_fwd(bf16)");
     return RSLO_OK;
   }
-  // maps of >= 512 workgroups (2 or more per CU): the one-tap-ahead variant at 96 registers keeps 5 workgroups resident
-  // per CU instead of 2 (20 waves hide the staging chain; the 9-tap weight prefetch is not needed with them; the 32-bit
-  // input offsets above are what lets it fit with one spilled register).  Measured (scripts/conv2d_cfgs.sh, B = 4, the
-  // 9-tap kernel -> 4 workgroups per CU at 104 registers -> 5): 128 -> 128 at 48x88 41.6 -> 38.0 -> 35.7 us, 64 -> 64 at
-  // 96x176 44.1 -> 36.4 -> 35.2, 64 -> 192 at 96x176 114.8 -> 92.2 -> 87.8, 192 -> 64 103.8 -> 94.1 -> 89.7, 256 -> 64 at
-  // 48x88 (576 workgroups) 47.0 -> 42.1; 128 -> 128 at 24x44 (288 workgroups) 16.5 -> 17.4 and 256 -> 256 at 12x22
-  // 18.6 -> 25.0 keep the 9-tap kernel.  conv2d_fwd_lean = 0 / 1 forces it off / on.
-  const int lean_env = rslo_tune(RSLO_TUNE_CONV2D_FWD_LEAN);
-  if (tr == 4 && mtw == 1 && !kc2 && !g_c2f_occ && (lean_env < 0 ? wgs4 >= 512 : lean_env == 1)) {
+  if (tr == 4 && mtw == 1 && !kc2 && !g_c2f_occ && (lean_env < 0 ? dflt == C2F_LEAN : lean_env == 1)) {
     hipLaunchKernelGGL((k_conv2d_fwd<4, 1, false, false, 1, 5>), grid, dim3(256), 0, st, in, ws, bias, gm, out);
     RSLO_CHECK_LAUNCH("k_conv2d_fwd(lean)");
     return RSLO_OK;
@@ -951,7 +961,6 @@ static int conv2d_fwd_launch(const float *in, const void *Ws, const float *bias,
   if (tr == 4 && g_c2f_occ) {
 #define C2F_OCC(M, O) hipLaunchKernelGGL((k_conv2d_fwd<4, M, false, false, 1, O>), grid, dim3(256), 0, st, in, ws, bias, gm, out)
     if (mtw == 1 && g_c2f_occ == 3) C2F_OCC(1, 3);
-    else if (mtw == 1 && g_c2f_occ == 4) C2F_OCC(1, 4);
     else if (mtw == 1 && g_c2f_occ == 4) C2F_OCC(1, 4);
     else if (mtw == 1) C2F_OCC(1, 5);
     else if (g_c2f_occ == 4) C2F_OCC(2, 4);
@@ -971,8 +980,8 @@ static int conv2d_fwd_launch(const float *in, const void *Ws, const float *bias,
 }
 
 // Eval-mode conv -> BatchNorm (running statistics folded into scale / shift) -> (+ res) -> activation in one launch: the
-// default tile configuration of conv2d_fwd_launch (4-row tiles, one 16-channel block per wave; the lean one-tap-ahead
-// variant on maps of >= 512 workgroups, two wave sets on long chains of few workgroups), with the EP epilogue.
+// default tile configuration of conv2d_fwd_launch (4-row tiles, one 16-channel block per wave) and its default variant,
+// with the EP epilogue.
 extern "C" int rslo_conv2d_fwd_bn(const float *in, const void *Ws, const float *bias, const float *scale, const float *shift,
                                   const float *res, int B, int cin, int cout, int H, int W, int act, float slope, float *out,
                                   void *stream) {
@@ -980,23 +989,15 @@ extern "C" int rslo_conv2d_fwd_bn(const float *in, const void *Ws, const float *
   RSLO_CHECK_ARG(in && Ws && scale && shift && out && conv2d_fwd_plan(B, cin, cout, H, W, &tr, &mtw),
                  "rslo_conv2d_fwd_bn: unsupported shape cin=%d cout=%d H=%d W=%d", cin, cout, H, W);
   Conv2dFwdGeom gm;
-  gm.B = B; gm.cin = cin; gm.cout = cout; gm.H = H; gm.W = W;
   gm.res = res; gm.scale = scale; gm.shift = shift; gm.slope = slope; gm.act = act ? 1 : 0;
-  gm.tiles_x = (int)rslo_cdiv(W, 16);
-  gm.tiles_y = (int)rslo_cdiv(H, 4);
-  gm.npix = B * gm.tiles_x * gm.tiles_y;
-  gm.ny = cout / 32;
-  gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_FWD_XSC, gm.ny, 3.0 * 18.0 * cin * cout, 4.0 * B * cin * H * W * 1.5);
-  const dim3 grid = conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
+  const dim3 grid = conv2d_fwd_geom(&gm, B, cin, cout, H, W, 4, 1, 3.0 * 18.0 * cin * cout, 4.0 * B * cin * H * W * 1.5);
   hipStream_t st = (hipStream_t)stream;
   const unsigned short *ws = (const unsigned short *)Ws;
-  const int64_t wgs4 = (int64_t)gm.npix * gm.ny;
-  if (cin >= 256 && wgs4 <= 200)
-    hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, false, 2, 1, true>), grid, dim3(512), 0, st, in, ws, bias, gm, out);
-  else if (wgs4 >= 512)
-    hipLaunchKernelGGL((k_conv2d_fwd<4, 1, false, false, 1, 5, true>), grid, dim3(256), 0, st, in, ws, bias, gm, out);
-  else
-    hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, false, 1, 2, true>), grid, dim3(256), 0, st, in, ws, bias, gm, out);
+  switch (conv2d_fwd_default_variant(cin, (int64_t)gm.npix * gm.ny)) {
+  case C2F_TWO_SETS: hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, false, 2, 1, true>), grid, dim3(512), 0, st, in, ws, bias, gm, out); break;
+  case C2F_LEAN: hipLaunchKernelGGL((k_conv2d_fwd<4, 1, false, false, 1, 5, true>), grid, dim3(256), 0, st, in, ws, bias, gm, out); break;
+  case C2F_NINE_TAP: hipLaunchKernelGGL((k_conv2d_fwd<4, 1, true, false, 1, 2, true>), grid, dim3(256), 0, st, in, ws, bias, gm, out); break;
+  }
   RSLO_CHECK_LAUNCH("k_conv2d_fwd(bn)");
   return RSLO_OK;
 }
@@ -1257,38 +1258,49 @@ extern "C" int rslo_conv2d_s2_supported(int cin, int cout, int ksize) {
   return (ksize == 1 || ksize == 3) && cin > 0 && cout > 0 && cin % 32 == 0 && cout % 32 == 0;
 }
 
-// in [B,cin,H,W] -> out [B,cout,Ho,Wo], Ho = (H - 1) / 2 + 1; Ws = rslo_conv2d_wsplit_k(W, cin, cout, ksize, 0)
-extern "C" int rslo_conv2d_fwd_s2(const float *in, const void *Ws, int B, int cin, int cout, int H, int W, int ksize,
-                                  float *out, void *stream) {
-  RSLO_CHECK_ARG(in && Ws && out && B > 0 && H > 0 && W > 0 && rslo_conv2d_s2_supported(cin, cout, ksize),
-                 "rslo_conv2d_fwd_s2: unsupported shape cin=%d cout=%d ksize=%d", cin, cout, ksize);
-  Conv2dStrGeom gm = {};
+// Forward geometry of the stride-2 kernels (one class: the whole output plane; mtw 16-channel blocks per wave); returns
+// the grid
+static dim3 conv2d_s2_fwd_geom(Conv2dStrGeom *g, int B, int cin, int cout, int H, int W, int ksize, int mtw) {
+  Conv2dStrGeom &gm = *g;
+  gm = {};
   gm.B = B; gm.cin = cin; gm.cout = cout; gm.Hi = H; gm.Wi = W;
   gm.Ho = (H - 1) / 2 + 1; gm.Wo = (W - 1) / 2 + 1;
   gm.s_out = 1; gm.ntap_w = ksize * ksize; gm.n_class = gm.cls_out = 1;
   gm.tiles_x = (int)rslo_cdiv(gm.Wo, 16); gm.tiles_y = (int)rslo_cdiv(gm.Ho, 4);
   Conv2dStrClass &c = gm.cls[0];
   c.rows = gm.Ho; c.cols = gm.Wo;
+  if (ksize == 3) {
+    gm.src_stride = 1; gm.by = gm.bx = -1; c.ny = c.nx = 3;
+    for (int i = 0; i < 3; ++i) c.oy[i] = c.ox[i] = i;
+    for (int i = 0; i < 9; ++i) c.wt[i] = i;
+  } else {        // out[y][x] = W in[2y][2x]: stage only the sampled pixels
+    gm.src_stride = 2; c.ny = c.nx = 1;
+  }
+  gm.npix = B * gm.tiles_x * gm.tiles_y;
+  gm.ny = cout / (32 * mtw);
+  gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_S2_XSC, gm.ny, 6.0 * ksize * ksize * cin * cout, 4.0 * B * cin * H * W * (ksize == 3 ? 1.5 : 0.25));
+  return conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
+}
+
+// in [B,cin,H,W] -> out [B,cout,Ho,Wo], Ho = (H - 1) / 2 + 1; Ws = rslo_conv2d_wsplit_k(W, cin, cout, ksize, 0)
+extern "C" int rslo_conv2d_fwd_s2(const float *in, const void *Ws, int B, int cin, int cout, int H, int W, int ksize,
+                                  float *out, void *stream) {
+  RSLO_CHECK_ARG(in && Ws && out && B > 0 && H > 0 && W > 0 && rslo_conv2d_s2_supported(cin, cout, ksize),
+                 "rslo_conv2d_fwd_s2: unsupported shape cin=%d cout=%d ksize=%d", cin, cout, ksize);
   // two 16-channel blocks per wave (64 output channels per workgroup) when the launch still fills the chip: the staged
   // halo and its operand split are shared by twice the MFMAs (256 -> 128 at 96x176: 237 -> 218 us, its 1x1: 41 -> 31 us;
   // the smaller stages lose, 44 -> 62 us, and keep 32 channels)
   const int mtw_env = rslo_tune(RSLO_TUNE_CONV2D_S2_MTW);
   // (k_conv2d_str2 holds a chunk's weight operands in registers with ONE block per wave: 96 vs 161 us on that layer; two are opt-in)
   const int mtw = (cout % 64 == 0 && mtw_env == 2) ? 2 : 1;
-  gm.npix = B * gm.tiles_x * gm.tiles_y;
-  gm.ny = cout / (32 * mtw);
-  gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_S2_XSC, gm.ny, 6.0 * ksize * ksize * cin * cout, 4.0 * B * cin * H * W * (ksize == 3 ? 1.5 : 0.25));
-  const dim3 grid = conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
+  Conv2dStrGeom gm;
+  const dim3 grid = conv2d_s2_fwd_geom(&gm, B, cin, cout, H, W, ksize, mtw);
   hipStream_t st = (hipStream_t)stream;
   const unsigned short *ws = (const unsigned short *)Ws;
   if (ksize == 3) {
-    gm.src_stride = 1; gm.by = gm.bx = -1; c.ny = c.nx = 3;
-    for (int i = 0; i < 3; ++i) c.oy[i] = c.ox[i] = i;
-    for (int i = 0; i < 9; ++i) c.wt[i] = i;
     if (mtw == 2) hipLaunchKernelGGL((k_conv2d_str2<0, 2, 2>), grid, dim3(256), 0, st, in, ws, gm, out);
     else hipLaunchKernelGGL((k_conv2d_str2<0, 1, 2>), grid, dim3(256), 0, st, in, ws, gm, out);
-  } else {        // out[y][x] = W in[2y][2x]: stage only the sampled pixels
-    gm.src_stride = 2; c.ny = c.nx = 1;
+  } else {
     if (mtw == 2) hipLaunchKernelGGL((k_conv2d_str2<1, 2, 4>), grid, dim3(256), 0, st, in, ws, gm, out);
     else hipLaunchKernelGGL((k_conv2d_str2<1, 1, 4>), grid, dim3(256), 0, st, in, ws, gm, out);
   }
@@ -1303,29 +1315,13 @@ extern "C" int rslo_conv2d_fwd_s2_bn(const float *in, const void *Ws, const floa
                                      int act, float slope, float *out, void *stream) {
   RSLO_CHECK_ARG(in && Ws && scale && shift && out && B > 0 && H > 0 && W > 0 && rslo_conv2d_s2_supported(cin, cout, ksize),
                  "rslo_conv2d_fwd_s2_bn: unsupported shape cin=%d cout=%d ksize=%d", cin, cout, ksize);
-  Conv2dStrGeom gm = {};
-  gm.B = B; gm.cin = cin; gm.cout = cout; gm.Hi = H; gm.Wi = W;
-  gm.Ho = (H - 1) / 2 + 1; gm.Wo = (W - 1) / 2 + 1;
-  gm.s_out = 1; gm.ntap_w = ksize * ksize; gm.n_class = gm.cls_out = 1;
-  gm.tiles_x = (int)rslo_cdiv(gm.Wo, 16); gm.tiles_y = (int)rslo_cdiv(gm.Ho, 4);
+  Conv2dStrGeom gm;
+  const dim3 grid = conv2d_s2_fwd_geom(&gm, B, cin, cout, H, W, ksize, 1);
   gm.res = res; gm.bias = bias; gm.scale = scale; gm.shift = shift; gm.slope = slope; gm.act = act ? 1 : 0;
-  Conv2dStrClass &c = gm.cls[0];
-  c.rows = gm.Ho; c.cols = gm.Wo;
-  gm.npix = B * gm.tiles_x * gm.tiles_y;
-  gm.ny = cout / 32;
-  gm.xsc = conv2d_xcd_split(RSLO_TUNE_CONV2D_S2_XSC, gm.ny, 6.0 * ksize * ksize * cin * cout, 4.0 * B * cin * H * W * (ksize == 3 ? 1.5 : 0.25));
-  const dim3 grid = conv2d_xcd_grid(gm.xsc, gm.npix, gm.ny);
   hipStream_t st = (hipStream_t)stream;
   const unsigned short *ws = (const unsigned short *)Ws;
-  if (ksize == 3) {
-    gm.src_stride = 1; gm.by = gm.bx = -1; c.ny = c.nx = 3;
-    for (int i = 0; i < 3; ++i) c.oy[i] = c.ox[i] = i;
-    for (int i = 0; i < 9; ++i) c.wt[i] = i;
-    hipLaunchKernelGGL((k_conv2d_str2<0, 1, 2, true, true>), grid, dim3(256), 0, st, in, ws, gm, out);
-  } else {
-    gm.src_stride = 2; c.ny = c.nx = 1;
-    hipLaunchKernelGGL((k_conv2d_str2<1, 1, 4, true, true>), grid, dim3(256), 0, st, in, ws, gm, out);
-  }
+  if (ksize == 3) hipLaunchKernelGGL((k_conv2d_str2<0, 1, 2, true, true>), grid, dim3(256), 0, st, in, ws, gm, out);
+  else hipLaunchKernelGGL((k_conv2d_str2<1, 1, 4, true, true>), grid, dim3(256), 0, st, in, ws, gm, out);
   RSLO_CHECK_LAUNCH("k_conv2d_str2(fwd, bn)");
   return RSLO_OK;
 }

@@ -101,7 +101,7 @@ __global__ __launch_bounds__(SPC_THREADS) void k_spconv(const float *__restrict_
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int li = lane & 15, g = lane >> 4;
   const int64_t n_tiles = (n_out + TILE - 1) / TILE;
-  // (n_live: only the tiles that hold live rows of a capacity-laid-out table, rslo_spconv_set_live_rows)
+  // (n_live: only the tiles that hold live rows of a capacity-laid-out table, include/rslo_hip.h n_live_dev)
   const int64_t tile_id = n_live ? xcd_tile_live(((int64_t)*n_live + TILE - 1) / TILE) : xcd_tile(n_tiles);
   if (tile_id < 0 || tile_id >= n_tiles) return;
   const int64_t row0 = tile_id * TILE;
@@ -264,7 +264,7 @@ __global__ __launch_bounds__(SPC_THREADS) void k_spconv_v3(const float *__restri
   const int li = lane & 15, g = lane >> 4;
   const int64_t n_tiles = (n_out + ROWS - 1) / ROWS;
   const int64_t n_blocks = (n_tiles + SPC_WAVES - 1) / SPC_WAVES;
-  // (n_live: only the workgroups that hold live rows of a capacity-laid-out table, rslo_spconv_set_live_rows)
+  // (n_live: only the workgroups that hold live rows of a capacity-laid-out table, include/rslo_hip.h n_live_dev)
   const bool use_live = n_live != nullptr && order == nullptr;
   const int64_t vb = use_live ? xcd_tile_live(((int64_t)*n_live + SPC_WAVES * ROWS - 1) / (SPC_WAVES * ROWS)) : xcd_tile(n_blocks);
   if (vb < 0) return;
@@ -480,7 +480,7 @@ __global__ __launch_bounds__(SPC_THREADS, (SKIPB ? 4 : 1)) void k_spconv_v6(cons
   const int tw = wid / KS, half = wid % KS;
   const int64_t n_tiles = (n_out + ROWS - 1) / ROWS;
   const int64_t n_blocks = (n_tiles + TPB - 1) / TPB;
-  // n_live (rslo_spconv_set_live_rows: a capacity-laid-out table whose live-row count stays on the device): only the
+  // n_live (n_live_dev of rslo_spconv_fwd_split: a capacity-laid-out table whose live-row count stays on the device): only the
   // workgroups that hold live rows run, spread over the XCDs like a launch of that size; a workgroup of padding rows has
   // nothing to compute and nothing anyone reads to write
   const bool use_live = n_live != nullptr && order == nullptr;
@@ -888,7 +888,7 @@ extern "C" int rslo_spconv_fwd_bf16(const void *in, int cin, const void *Wb, con
   if (n_out == 0) return RSLO_OK;
   const unsigned short *x = (const unsigned short *)in, *w = (const unsigned short *)Wb;
   unsigned short *o = (unsigned short *)out;
-  // rslo_spconv_set_tiling applies here too.  Measured (profiles/r02_spconv_offset_split.txt): the bf16 kernel moves half
+  // The switches spconv_rbw / spconv_ks apply here too.  Measured (profiles/r02_spconv_offset_split.txt): the bf16 kernel moves half
   // the bytes per product and gains less from a second wave per tile -- 64 -> 64 level 3 35.9 -> 32.0 us (16-row tiles),
   // level 2 67.0 -> 65.8 us (32-row tiles), 32 -> 32 loses (27.4 -> 29.7 us)
   const int rbw = spc_force_rbw == 1 || spc_force_rbw == 2 ? spc_force_rbw : ((n_out >= 256 * 32 * 8) ? 2 : 1);
@@ -934,25 +934,10 @@ extern "C" int rslo_weight_split_many(const RsloWeightSplitDesc *desc_dev, int n
   return RSLO_OK;
 }
 
-// Live-row count of the NEXT forward launch (rslo_spconv_fwd / rslo_spconv_fwd_split), consumed by it: see include/rslo_hip.h
-static thread_local const int32_t *g_spc_live_rows = nullptr;      // per thread: set and consumed by the same caller
-extern "C" void rslo_spconv_set_live_rows(const int32_t *n_live_dev) { g_spc_live_rows = n_live_dev; }
-static inline const int32_t *spc_take_live() {
-  const int32_t *p = g_spc_live_rows;
-  g_spc_live_rows = nullptr;
-  return p;
-}
-
-extern "C" void rslo_spconv_set_tiling(int rbw, int ks) {
-  g_rslo_tune[RSLO_TUNE_SPCONV_RBW] = (rbw == 1 || rbw == 2 || rbw == 4) ? rbw : 0;
-  g_rslo_tune[RSLO_TUNE_SPCONV_KS] = (ks == 1 || ks == 2 || ks == 4) ? ks : 0;
-}
-
 extern "C" int rslo_spconv_fwd_split(const float *in, int cin, const void *Ws, const float *bias, const int32_t *nbr,
                                      const int32_t *row_order, int64_t n_out, int K, int cout, int flip_k,
-                                     float act_slope, float *out, void *stream) {
+                                     float act_slope, float *out, const int32_t *live, void *stream) {
   hipStream_t st = (hipStream_t)stream;
-  const int32_t *live = spc_take_live();
   RSLO_CHECK_ARG((cin == 32 || cin == 64) && (cout == 32 || cout == 64), "spconv_fwd_split: channels must be 32 or 64");
   RSLO_CHECK_ARG(K >= 1 && K <= SPC_MAXK, "spconv_fwd_split: K must be in 1..27");
   if (n_out == 0) return RSLO_OK;
@@ -1008,8 +993,7 @@ static int pad_cout(int c) { return c <= 16 ? 16 : (c <= 32 ? 32 : 64); }
 template <bool TRANS>
 static int launch_spconv(const float *in, int cin, const float *W, const float *bias, const int32_t *nbr,
                          const int32_t *order, int64_t n_out, int K, int cout, int flip_k, float slope, float *out,
-                         hipStream_t st) {
-  const int32_t *live = spc_take_live();
+                         const int32_t *live, hipStream_t st) {
   RSLO_CHECK_ARG(cin >= 1 && cin <= 64 && cout >= 1 && cout <= 64, "spconv: channels must be in 1..64");
   RSLO_CHECK_ARG(K >= 1 && K <= SPC_MAXK, "spconv: K must be in 1..27");
   RSLO_CHECK_ARG(cin <= 8 || cin % 4 == 0, "spconv: cin > 8 must be a multiple of 4");
@@ -1060,8 +1044,8 @@ static int launch_spconv(const float *in, int cin, const float *W, const float *
 
 extern "C" int rslo_spconv_fwd(const float *in, int cin, const float *W, const float *bias,
                                const int32_t *nbr, const int32_t *row_order, int64_t n_out, int K, int cout,
-                               int flip_k, float act_slope, float *out, void *stream) {
-  return launch_spconv<false>(in, cin, W, bias, nbr, row_order, n_out, K, cout, flip_k, act_slope, out,
+                               int flip_k, float act_slope, float *out, const int32_t *n_live_dev, void *stream) {
+  return launch_spconv<false>(in, cin, W, bias, nbr, row_order, n_out, K, cout, flip_k, act_slope, out, n_live_dev,
                               (hipStream_t)stream);
 }
 
@@ -1071,7 +1055,7 @@ extern "C" int rslo_spconv_dgrad(const float *dout, int cout, const float *W, co
                                  const int32_t *row_order, int64_t n_in, int K, int cin, int flip_k, float *din,
                                  void *stream) {
   RSLO_CHECK_ARG(cout <= 8 || cout % 4 == 0, "spconv_dgrad: cout > 8 must be a multiple of 4");
-  return launch_spconv<true>(dout, cout, W, nullptr, nbrT, row_order, n_in, K, cin, flip_k, 1.0f, din,
+  return launch_spconv<true>(dout, cout, W, nullptr, nbrT, row_order, n_in, K, cin, flip_k, 1.0f, din, nullptr,
                              (hipStream_t)stream);
 }
 

@@ -14,7 +14,7 @@ encoder).  Issued eagerly that pass is ~40 dependent launches on levels of 2.6 k
 
 Outputs of the VALID rows (and the whole BEV map: padding rows are never scattered) equal the eager pass bit for bit:
 same kernels, and the tilings that depend on a level's size are pinned to what the eager pass of a single scan picks
-(`rslo_spconv_set_tiling(1, 4)`: 16-row tiles shared by four waves, csrc/spconv.hip).
+(`capi.tuning(spconv_rbw=1, spconv_ks=4)`: 16-row tiles shared by four waves, csrc/spconv.hip).
 """
 import queue
 import threading

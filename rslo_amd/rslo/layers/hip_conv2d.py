@@ -55,6 +55,15 @@ def _low_precision():
     return precision.low_precision() is not None
 
 
+def current_split(w):
+    """(fwd, dgrad) split-bf16 operands that presplit() left on the parameter, or None when the weight has changed since
+    (version counter, storage)."""
+    ws = getattr(w, "_hip_split", None)      # operands refreshed for all layers in one launch (presplit())
+    if ws is None or ws[2] != w._version or ws[3] != w.data_ptr():
+        return None
+    return ws[0], ws[1]
+
+
 class _Conv3x3Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, stride, hip_fd, hip_w):
@@ -70,9 +79,7 @@ class _Conv3x3Fn(torch.autograd.Function):
         ctx.lp = lp = precision.low_precision() is not None      # C4: bf16 operands, fp32 accumulate / storage
         if hip_fd:
             from rslo_amd import capi
-            ws = getattr(w, "_hip_split", None)      # operands refreshed for all layers in one launch (presplit())
-            if ws is not None and (ws[2] != w._version or ws[3] != w.data_ptr()):
-                ws = None
+            ws = current_split(w)
             if "d" in HIP_PASSES:
                 ctx.ws_t = ws[1] if ws is not None else capi.conv2d_wsplit(w, True)
             if "f" in HIP_PASSES:
@@ -124,9 +131,7 @@ class _Conv1x1S2Fn(torch.autograd.Function):
         from rslo_amd import capi
         x = x.contiguous()
         ctx.save_for_backward(x, w)
-        ws = getattr(w, "_hip_split", None)
-        if ws is not None and (ws[2] != w._version or ws[3] != w.data_ptr()):
-            ws = None
+        ws = current_split(w)
         ctx.ws_t = ws[1] if ws is not None else capi.conv2d_wsplit_k(w, True)
         return capi.conv2d_fwd_s2(x, ws[0] if ws is not None else capi.conv2d_wsplit_k(w, False), w.shape[0], 1)
 
@@ -277,8 +282,8 @@ def conv_bn_eval(conv, bn, x, slope, residual=None):
     from rslo_amd import capi
     c = getattr(conv, "conv1", conv)
     fold = bn.__dict__.get("_eval_fold")
-    ws = getattr(c.weight, "_hip_split", None)
-    if fold is None or ws is None or ws[2] != c.weight._version or ws[3] != c.weight.data_ptr():
+    ws = current_split(c.weight)
+    if fold is None or ws is None:
         raise _rslo_error("conv_bn_eval: operands of %s are not current (EvalOperands.refresh)" % type(c).__name__)
     x = x.contiguous()
     if c.stride == (2, 2):

@@ -176,31 +176,29 @@ def test_conv_results_do_not_depend_on_row_order(hip, cin, cout):
 
 @pytest.mark.parametrize("cin,cout", [(32, 32), (64, 64), (32, 64), (64, 32)])
 def test_offset_split_tilings_agree(hip, cin, cout):
-    """rslo_spconv_set_tiling: every (rows per tile, waves per tile) form of k_spconv_v6 computes the same products; only
+    """spconv_rbw / spconv_ks: every (rows per tile, waves per tile) form of k_spconv_v6 computes the same products; only
     the order in which the per-offset sums meet differs (ks waves are added through LDS in wave order).  All forms
     against float64 within the fp32 bar of the kernel, each form run-to-run identical, ragged and tiny sizes included."""
     rng = np.random.default_rng(cin * 5 + cout)
     dims = [9, 60, 70]
-    L = hip.lib()
-    try:
-        for n in (1, 31, 5000, 8200 + 17):
-            coords = rand_sites(rng, 2, dims, n)
-            idx = hip.SiteIndex(dev(coords), 2, dims)
-            nbr = hip.rulebook_subm(idx, [3, 3, 3])
-            x = torch.randn(len(coords), cin, device="cuda")
-            W = torch.randn(27, cin, cout, device="cuda") * 0.1
-            b = torch.randn(cout, device="cuda")
-            order = hip.rulebook_row_order(nbr)
-            # float64 reference: gather-matmul per offset
-            nb = nbr.long()
-            xz = torch.cat([x.double(), torch.zeros(1, cin, dtype=torch.float64, device="cuda")])
-            ref = b.double()[None].repeat(len(coords), 1)
-            for k in range(27):
-                ref += xz[torch.where(nb[:, k] >= 0, nb[:, k], torch.full_like(nb[:, k], len(coords)))] @ W[k].double()
-            scale = ref.abs().max().item() + 1e-30
-            bf16_ref = None
-            for rbw, ks in ((1, 1), (1, 2), (1, 4), (2, 1), (2, 2), (2, 4), (4, 1), (0, 0)):
-                L.rslo_spconv_set_tiling(rbw, ks)
+    for n in (1, 31, 5000, 8200 + 17):
+        coords = rand_sites(rng, 2, dims, n)
+        idx = hip.SiteIndex(dev(coords), 2, dims)
+        nbr = hip.rulebook_subm(idx, [3, 3, 3])
+        x = torch.randn(len(coords), cin, device="cuda")
+        W = torch.randn(27, cin, cout, device="cuda") * 0.1
+        b = torch.randn(cout, device="cuda")
+        order = hip.rulebook_row_order(nbr)
+        # float64 reference: gather-matmul per offset
+        nb = nbr.long()
+        xz = torch.cat([x.double(), torch.zeros(1, cin, dtype=torch.float64, device="cuda")])
+        ref = b.double()[None].repeat(len(coords), 1)
+        for k in range(27):
+            ref += xz[torch.where(nb[:, k] >= 0, nb[:, k], torch.full_like(nb[:, k], len(coords)))] @ W[k].double()
+        scale = ref.abs().max().item() + 1e-30
+        bf16_ref = None
+        for rbw, ks in ((1, 1), (1, 2), (1, 4), (2, 1), (2, 2), (2, 4), (4, 1), (0, 0)):
+            with hip.tuning(spconv_rbw=rbw, spconv_ks=ks):
                 y = hip.spconv_fwd(x, W, b, nbr)
                 assert (y.double() - ref).abs().max().item() <= 2e-6 * scale, (rbw, ks, n)
                 assert torch.equal(hip.spconv_fwd(x, W, b, nbr), y), (rbw, ks, n)
@@ -214,8 +212,45 @@ def test_offset_split_tilings_agree(hip, cin, cout):
                     # the partial sums meet in a different order: one bf16 ulp of the rounded output at most
                     assert (yb.float() - bf16_ref.float()).abs().max().item() <= 2 ** -7 * scale, (rbw, ks, n, "bf16")
                     assert torch.equal(hip.spconv_fwd_bf16(xb, W, b, nbr), yb)
-    finally:
-        L.rslo_spconv_set_tiling(0, 0)
+
+
+@pytest.mark.parametrize("cin,cout,tiling", [(4, 16, None), (16, 16, None), (32, 32, None), (64, 64, None),
+                                             (32, 32, (2, 2)), (64, 64, (2, 2))])
+def test_spconv_live_rows_argument(hip, cin, cout, tiling):
+    """n_live_dev of rslo_spconv_fwd / rslo_spconv_fwd_split is an argument of the call it belongs to: the rows below the
+    count carry the bits of the full launch (k_spconv, k_spconv_v3, k_spconv_v6 with 16-row tiles and, forced, the 32-row
+    skipping form), a row order disables the count, and a call that raises before its launch leaves nothing behind for the
+    next forward or data gradient (whose torch.empty outputs are handed poisoned blocks here)."""
+    import contextlib
+    rng = np.random.default_rng(cin * 3 + cout)
+    dims = [9, 60, 70]
+    coords = rand_sites(rng, 2, dims, 200)
+    n = len(coords)
+    nbr = hip.rulebook_subm(hip.SiteIndex(dev(coords), 2, dims), [3, 3, 3])
+    x = torch.randn(n, cin, device="cuda")
+    W = torch.randn(27, cin, cout, device="cuda") * 0.1
+    b = torch.randn(cout, device="cuda")
+    g = torch.randn(n, cout, device="cuda")
+    with hip.tuning(spconv_rbw=tiling[0], spconv_ks=tiling[1]) if tiling else contextlib.nullcontext():
+        full = hip.spconv_fwd(x, W, b, nbr)
+        for n_live in (0, 1, 70, n):
+            live = torch.tensor([n_live], dtype=torch.int32, device="cuda")
+            y = hip.spconv_fwd(x, W, b, nbr, n_live=live)
+            assert torch.equal(y[:n_live], full[:n_live]), n_live
+        live = torch.tensor([70], dtype=torch.int32, device="cuda")
+        assert torch.equal(hip.spconv_fwd(x, W, b, nbr, order=hip.rulebook_row_order(nbr), n_live=live), full)
+        # nothing stays armed
+        zero = torch.zeros(1, dtype=torch.int32, device="cuda")
+        with pytest.raises(hip.RsloHipError):
+            hip.spconv_fwd(x, W, b.double(), nbr, n_live=zero)
+        poison = torch.full((n, cout), float("nan"), device="cuda")
+        del poison
+        y = hip.spconv_fwd(x, W, b, nbr)
+        poison = torch.full((n, cin), float("nan"), device="cuda")
+        del poison
+        d = hip.spconv_dgrad(g, W, nbr, flip_k=True)
+        assert not torch.isnan(y).any() and not torch.isnan(d).any()
+        assert torch.equal(y, full)
 
 
 def test_rulebook_empty_input(hip):
@@ -1531,6 +1566,34 @@ def test_conv2d_fwd_tile_heights_keep_the_bits(hip, B, cin, cout, H, W):
             got = [hip.conv2d_fwd(x, ws, bias, cout), hip.conv2d_fwd(x, ws, None, cout, residual=res)]
         for a, b in zip(ref, got):
             assert torch.equal(a, b), tr
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,cin,cout,H,W,ksize,stride,res", [
+    (1, 256, 32, 8, 16, 3, 1, False),       # 2 workgroups of 256 input channels: two wave sets
+    (2, 32, 64, 64, 128, 3, 1, False),      # 2 * 8 * 16 * 2 = 512 workgroups: lean
+    (1, 32, 32, 8, 16, 3, 1, False),        # 9-tap
+    (1, 256, 32, 8, 16, 3, 1, True),
+    (1, 32, 64, 9, 17, 3, 2, False),        # odd sizes: the (H - 1) / 2 + 1 edge
+    (1, 32, 64, 9, 17, 1, 2, False)])
+def test_conv2d_eval_entry_selects_training_variant(hip, B, cin, cout, H, W, ksize, stride, res):
+    """rslo_conv2d_fwd_bn / rslo_conv2d_fwd_s2_bn with identity scale, zero shift and no activation return the bits of
+    rslo_conv2d_fwd / rslo_conv2d_fwd_s2: one geometry builder and one default-variant rule per kernel family (the two
+    wave sets add their channel chunks in another order than the one-set kernels).  The epilogue computes
+    (acc + bias) * 1 + 0; torch.equal treats -0 as equal to 0."""
+    torch.manual_seed(B * cin + cout + ksize)
+    x = torch.randn(B, cin, H, W, device="cuda")
+    w = torch.randn(cout, cin, ksize, ksize, device="cuda") / (ksize * cin ** 0.5)
+    ones, zeros = torch.ones(cout, device="cuda"), torch.zeros(cout, device="cuda")
+    if stride == 2:
+        ws = hip.conv2d_wsplit_k(w, False)
+        assert torch.equal(hip.conv2d_fwd_s2_bn(x, ws, None, ones, zeros, cout, ksize), hip.conv2d_fwd_s2(x, ws, cout, ksize))
+        return
+    bias = torch.randn(cout, device="cuda")
+    r = torch.randn(B, cout, H, W, device="cuda") if res else None
+    ws = hip.conv2d_wsplit(w, False)
+    assert torch.equal(hip.conv2d_fwd_bn(x, ws, bias, ones, zeros, cout, residual=r),
+                       hip.conv2d_fwd(x, ws, bias, cout, residual=r))
 
 
 @pytest.mark.gpu
