@@ -869,6 +869,32 @@ RSLO_API int rslo_estimate_normals(const float *points, int stride_floats, int N
                                    const float *h_viewpoint3, int zero_vertical, float *normals /*[N,3]*/,
                                    int32_t *counts /*[N]*/, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Voxel down-sample of a cloud (csrc/downsample.hip).  Replaces the second offline step of script/create_hdf5.py:149-165
+ * (pcd.voxel_down_sample(size), called at :337-347 for 0.1 / 0.2 / 0.4 / 0.8 m, each from the full-resolution cloud).
+ * Open3D is not part of the reference tree: the rules are recalled from its PointCloud::VoxelDownSample, not verified
+ * against it; their float64 restatement is rslo_amd/downsample.py.  All arithmetic is double (Open3D holds doubles):
+ *   a point is valid when its three coordinates are finite; an invalid point belongs to no voxel.
+ *   minb = component-wise minimum of the valid points, vmin = minb - 0.5 * voxel_size,
+ *   cell = floor((double(p) - vmin) / voxel_size) per axis, a true IEEE division.
+ *   One output row per occupied cell: sum(p) / n, then (normals != NULL) sum(normal) / n, not renormalised; the sums
+ *   are formed in ascending input index and the row is rounded to fp32 on store.
+ * Fixed here, not by Open3D (whose order is that of an unordered_map): rows come in ascending (cx, cy, cz), cx most
+ * significant.  A cell index >= 2^21 does not fit the sort key: then counts = {0, 1} and NOTHING ELSE is written.
+ * points is read as points[i * stride_floats + 0..2], normals as normals[i * nstride_floats + 0..2] (both strides >= 3):
+ * a [P,7] cloud is read in place with points = cloud, normals = cloud + 4, both strides 7.
+ * out is [N, 6] (normals == NULL: [N, 3]); rows >= Q are untouched.  voxel_of_point [N] (may be NULL): output row of
+ * point i, -1 for an invalid point.  npts [N] (may be NULL): points per output row, rows >= Q untouched.
+ * counts [2] = {Q, flags} (flag bit 0: overflow).  N == 0 writes counts = {0, 0} and nothing else.  voxel_size <= 0 or
+ * a stride < 3 is RSLO_EINVAL.  Everything runs on `stream`, no host read, nothing allocated: capturable.  Two calls
+ * on the same input give the same bits.
+ * ------------------------------------------------------------------------------------ */
+RSLO_API size_t rslo_voxel_downsample_ws_bytes(int N);
+RSLO_API int rslo_voxel_downsample(const float *points, int stride_floats, const float *normals /*or NULL*/,
+                                   int nstride_floats, int N, double voxel_size, float *out /*[N,6] | [N,3]*/,
+                                   int32_t *voxel_of_point /*[N] or NULL*/, int32_t *npts /*[N] or NULL*/,
+                                   int32_t *counts /*[2]*/, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,8 @@ SIGNATURES = {
     "rslo_pose_chain": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
     "rslo_normals_ws_bytes": (_sz, [_i]),
     "rslo_estimate_normals": (C.c_int, [_vp, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
+    "rslo_voxel_downsample_ws_bytes": (_sz, [_i]),
+    "rslo_voxel_downsample": (C.c_int, [_vp, _i, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -1008,6 +1010,71 @@ def append_normals(points_xyzi, radius=0.6, max_nn=30, viewpoint=None, out=None,
                               counts=None if counts is None else counts[:P], ws=ws)
     cloud[:, 4:].copy_(nrm)
     return cloud
+
+
+# --------------------------------------------------------------------------------------
+# voxel down-sample of a cloud (csrc/downsample.hip)
+# --------------------------------------------------------------------------------------
+def _rows3(t, name):
+    """(pointer, row stride in floats) of an fp32 CUDA [P, >= 3] tensor or column view whose rows are read in place"""
+    if not t.is_cuda:
+        raise RsloHipError("%s must live on the GPU (the RSLO hot path has no CPU fallback)" % name)
+    if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] < 3:
+        raise RsloHipError("%s must be fp32 [P, >= 3], got %s %s" % (name, t.dtype, tuple(t.shape)))
+    if t.shape[0] > 1 and (t.stride(1) != 1 or t.stride(0) < 3):
+        raise RsloHipError("%s: rows must be unit-stride with a row stride >= 3, got strides %s" % (name, t.stride()))
+    return t.data_ptr(), (int(t.stride(0)) if t.shape[0] > 1 else max(int(t.shape[1]), 3))
+
+
+def voxel_downsample(points, normals=None, voxel_size=0.1, *, out=None, index=None, npts=None, counts=None, ws=None,
+                     sync=True):
+    """script/create_hdf5.py:149-165 (Open3D voxel_down_sample) on the current stream; rules: include/rslo_hip.h.
+    points: fp32 CUDA [P, F >= 3], read in place through its row stride.  normals: None (rows are xyz only) or [P, 3],
+    possibly a strided view such as cloud[:, 4:7].  Rows are [., 6] with normals and [., 3] without.
+    index / npts: None = not wanted, True = allocate, or a preallocated int32 [P]: the output row of every point (-1
+    for an invalid one) and the points per output row.  out [P, 6 | 3], counts int32 [2] and ws (uint8, >=
+    rslo_voxel_downsample_ws_bytes(P)) may be preallocated too.
+    sync=True reads counts once, raises RsloHipError on the overflow flag and returns out[:Q], or the tuple
+    (out[:Q], [index,] [npts[:Q]]) when index / npts were asked for.  sync=False reads nothing on the host (the form
+    to use under capture) and returns (out, index, npts, counts): capacity-sized buffers, None where not asked for, and
+    the device counts = {Q, flags}."""
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    dev = points.device
+    nsrc, nstride = None, 0
+    if normals is not None:
+        nsrc, nstride = _rows3(normals, "normals")
+        if normals.shape != (P, 3):
+            raise RsloHipError("voxel_downsample: normals must be [P, 3], got %s" % (tuple(normals.shape),))
+    width = 3 if normals is None else 6
+    if out is None:
+        out = torch.empty((P, width), dtype=torch.float32, device=dev)
+    if out.shape != (P, width):
+        raise RsloHipError("voxel_downsample: out must be [P, %d], got %s" % (width, tuple(out.shape)))
+    if index is True:
+        index = torch.empty((P,), dtype=torch.int32, device=dev)
+    if npts is True:
+        npts = torch.empty((P,), dtype=torch.int32, device=dev)
+    for name, t in (("index", index), ("npts", npts)):
+        if t is not None and t.shape != (P,):
+            raise RsloHipError("voxel_downsample: %s must be [P]" % name)
+    if counts is None:
+        counts = torch.empty((2,), dtype=torch.int32, device=dev)
+    if counts.shape != (2,):
+        raise RsloHipError("voxel_downsample: counts must be [2]")
+    if ws is None:
+        ws = _ws(lib().rslo_voxel_downsample_ws_bytes(P), dev)
+    _chk(lib().rslo_voxel_downsample(src, stride, nsrc, nstride, P, float(voxel_size), _ptr(out, torch.float32, "out"),
+                                     _ptr(index, torch.int32, "index"), _ptr(npts, torch.int32, "npts"),
+                                     _ptr(counts, torch.int32, "counts"), _ptr(ws), ws.numel() * ws.element_size(),
+                                     _stream()), "rslo_voxel_downsample")
+    if not sync:
+        return out, index, npts, counts
+    Q, flags = counts.tolist()
+    if flags & 1:
+        raise RsloHipError("voxel_downsample: the cloud spans 2^21 or more cells of %g along an axis" % float(voxel_size))
+    res = (out[:Q],) + (() if index is None else (index,)) + (() if npts is None else (npts[:Q],))
+    return res[0] if len(res) == 1 else res
 
 
 def chamfer_grad(xyz1, xyz2, graddist1, idx1, g1=None, g2=None):
