@@ -895,6 +895,68 @@ RSLO_API int rslo_voxel_downsample(const float *points, int stride_floats, const
                                    int32_t *voxel_of_point /*[N] or NULL*/, int32_t *npts /*[N] or NULL*/,
                                    int32_t *counts /*[2]*/, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * World voxel map of a streamed trajectory (csrc/map.hip): a persistent, unbounded, incrementally filled voxel hash
+ * in the frame of the trajectory (the frame of scan 0).  Nothing of the reference corresponds to it (evaluate.py:363-408
+ * writes poses only); the float64 restatement of the rules is rslo_amd/mapping.py (VoxelMapRef), and the tests compare
+ * bit for bit.  A map is a set of cubic cells of edge voxel_size (> 0); voxel_size, min_range and max_range
+ * (0 <= min_range < max_range, max_range may be +inf) are fixed by rslo_map_reset.
+ * Inserting scan number s (s = inserts since the last reset; the counter lives in the map) under pose7 = (t, q wxyz), 7
+ * DEVICE doubles (a row of rslo_pose_chain's traj), does for every point i, in IEEE double without contraction:
+ *   p = double(xyz_i).  A point with a non-finite coordinate, or whose d2 = p.x*p.x + p.y*p.y + p.z*p.z (left to right)
+ *   fails d2 >= min_range*min_range && d2 < max_range*max_range, is skipped (dropped_invalid).
+ *   w = t + (p + (2.0*b*q.w + 2.0*c)), b = v x p, c = v x b, v = (q.x, q.y, q.z), cross products as a.y*b.z - a.z*b.y, ...
+ *   -- rslo_pose_chain's arithmetic and convention (w = T_abs p); q is NOT renormalised.
+ *   cell = floor(w / voxel_size) per axis (a true division); a point with any |cell| >= 2^20 (or a non-finite w) is
+ *   dropped (dropped_range).  key = (cell + 2^20) of x, y, z in 3 x 21 bits (x most significant); all-ones = empty.
+ *   tag = (uint64(s) << 32) | i.
+ * Every occupied cell holds  tag: the SMALLEST tag of all points ever inserted into it (the earliest scan wins, inside
+ * a scan the lowest index);  hits: int32 count of all points ever inserted into it;  row: (float(w.x), float(w.y),
+ * float(w.z), intensity) of the point that owns the tag (intensity = column 3 for width >= 4, else 0).  s only grows:
+ * a cell created by an earlier scan never changes its row, later scans only raise hits.
+ * Storage: ONE caller-owned device allocation of rslo_map_bytes(capacity) bytes, capacity = slots, a power of two in
+ * 1024 .. 2^31:  header (256 bytes) | keys u64 [capacity] | tags u64 [capacity] | rows f32 [capacity, 4] | hits i32
+ * [capacity].  The header as int64 words: [0] magic, [1] capacity, [2..4] voxel_size, min_range, max_range (doubles),
+ * [RSLO_MAP_HDR_COUNTERS + 0..5] = n_scans, n_cells, n_points (accepted), dropped_invalid, dropped_range, dropped_full
+ * -- integer atomics only, so they are deterministic.  Open addressing, linear probing from a 64-bit mix of the key.
+ * Probing is BOUNDED: at most RSLO_MAP_MAX_PROBE slots are examined; a point that finds neither its key nor an empty
+ * slot among them is dropped (dropped_full).  No loop depends on the table having room: a full map costs a counter,
+ * never a hang.  Slots only fill and keys never move, so a cell is either stored with its complete, correct tag / hits /
+ * row, or ALL of its points are dropped; which cells are dropped once dropped_full > 0 depends on the race for slots
+ * and is unspecified, as is the slot a cell occupies (consumers sort by tag).  Everything else is fully specified.
+ *   rslo_map_bytes   host only; 0 for a capacity that is not a power of two in 1024 .. 2^31.
+ *   rslo_map_reset   empties the table and writes the header, in one kernel.  An argument error (capacity, map_bytes <
+ *                    rslo_map_bytes(capacity), voxel_size, ranges) is RSLO_EINVAL and writes nothing.
+ *   The calls below take the map_bytes handed to rslo_map_reset and read the capacity from the header; on an
+ *   allocation that was never reset (no magic, or a capacity the bytes cannot hold) their kernels do nothing.
+ *   rslo_map_insert  points[i*stride_floats + 0..2] are read in place (a [P,4] scan or a [P,7] cloud needs no copy),
+ *                    width >= 4 reads the intensity at column 3.  ws: rslo_map_insert_ws_bytes(N).  N == 0 still
+ *                    counts as a scan.  At most three launches: slots / tags / hits by atomics; the rows of new cells,
+ *                    written by the owner of the tag; the scan counter.  stride_floats < 3 is RSLO_EINVAL.
+ *   rslo_map_lookup  read-only, same validity rules and the same bounded probe: hits_out[i] = -1 for a skipped or
+ *                    out-of-range point, 0 for a cell that is not in the map, else the cell's hits; tags_out (may be
+ *                    NULL) = the cell's tag, all-ones where hits_out <= 0.
+ *   rslo_map_export  the cells with hits >= min_hits and, when center3 (3 device doubles) is given, with the squared
+ *                    distance of row.xyz to it (in double, summed left to right) < radius*radius.  Order unspecified.
+ *                    counts = {matching, written}: rows beyond max_rows are counted, not written (max_rows = 0: the
+ *                    outputs may be NULL).
+ * All of them: everything on `stream`, no host read, nothing allocated: capturable.
+ * ------------------------------------------------------------------------------------ */
+#define RSLO_MAP_MAX_PROBE 128
+#define RSLO_MAP_HDR_COUNTERS 8
+RSLO_API size_t rslo_map_bytes(int64_t capacity);
+RSLO_API int rslo_map_reset(void *map, size_t map_bytes, int64_t capacity, double voxel_size, double min_range,
+                            double max_range, void *stream);
+RSLO_API size_t rslo_map_insert_ws_bytes(int N);
+RSLO_API int rslo_map_insert(void *map, size_t map_bytes, const float *points, int stride_floats, int width, int N,
+                             const double *pose7, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_map_lookup(const void *map, size_t map_bytes, const float *points, int stride_floats, int N,
+                             const double *pose7, int32_t *hits_out /*[N]*/, uint64_t *tags_out /*[N] or NULL*/,
+                             void *stream);
+RSLO_API int rslo_map_export(const void *map, size_t map_bytes, int min_hits, const double *center3 /*or NULL*/,
+                             double radius, float *rows /*[max_rows,4]*/, uint64_t *tags /*[max_rows]*/,
+                             int32_t *hits /*[max_rows]*/, int64_t max_rows, int64_t *counts /*[2]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

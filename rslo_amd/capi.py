@@ -190,6 +190,12 @@ SIGNATURES = {
     "rslo_estimate_normals": (C.c_int, [_vp, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "rslo_voxel_downsample_ws_bytes": (_sz, [_i]),
     "rslo_voxel_downsample": (C.c_int, [_vp, _i, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rslo_map_bytes": (_sz, [_i64]),
+    "rslo_map_reset": (C.c_int, [_vp, _sz, _i64, C.c_double, C.c_double, C.c_double, _vp]),
+    "rslo_map_insert_ws_bytes": (_sz, [_i]),
+    "rslo_map_insert": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "rslo_map_lookup": (C.c_int, [_vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "rslo_map_export": (C.c_int, [_vp, _sz, _i, _vp, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp]),
 }
 
 
@@ -1075,6 +1081,85 @@ def voxel_downsample(points, normals=None, voxel_size=0.1, *, out=None, index=No
         raise RsloHipError("voxel_downsample: the cloud spans 2^21 or more cells of %g along an axis" % float(voxel_size))
     res = (out[:Q],) + (() if index is None else (index,)) + (() if npts is None else (npts[:Q],))
     return res[0] if len(res) == 1 else res
+
+
+# --------------------------------------------------------------------------------------
+# world voxel map of a streamed trajectory (csrc/map.hip); the owning class is rslo_amd/mapping.py VoxelMap
+# --------------------------------------------------------------------------------------
+MAP_HDR_COUNTERS = 8      # first int64 word of the six counters in a map's header (include/rslo_hip.h)
+MAP_COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full")
+
+
+def map_bytes(capacity):
+    """rslo_map_bytes: bytes of a map of `capacity` slots, 0 unless capacity is a power of two >= 1024."""
+    return int(lib().rslo_map_bytes(int(capacity)))
+
+
+def _map_buf(buf):
+    if not (torch.is_tensor(buf) and buf.is_cuda and buf.dtype == torch.int64 and buf.dim() == 1 and buf.is_contiguous()):
+        raise RsloHipError("map: the buffer must be a contiguous int64 CUDA vector of rslo_map_bytes(capacity) bytes")
+    return buf.data_ptr(), buf.numel() * 8
+
+
+def _pose7(pose, name):
+    if not (torch.is_tensor(pose) and pose.is_cuda and pose.dtype == torch.float64 and pose.numel() == 7
+            and pose.is_contiguous()):
+        raise RsloHipError("%s: pose must be 7 contiguous float64 values (t, q wxyz) on the GPU" % name)
+    return pose.data_ptr()
+
+
+def map_reset(buf, capacity, voxel_size, min_range=0.0, max_range=float("inf")):
+    """rslo_map_reset on the current stream: empties the table and writes the header (rules: include/rslo_hip.h)."""
+    ptr, nbytes = _map_buf(buf)
+    _chk(lib().rslo_map_reset(ptr, nbytes, int(capacity), float(voxel_size), float(min_range), float(max_range),
+                              _stream()), "rslo_map_reset")
+
+
+def map_insert(buf, points, pose, ws):
+    """rslo_map_insert: one scan (fp32 CUDA [P, F >= 3], read in place; F >= 4: column 3 is the intensity) under pose
+    (float64 CUDA [7]) on the current stream.  ws: uint8, >= rslo_map_insert_ws_bytes(P).  No host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    _chk(lib().rslo_map_insert(ptr, nbytes, src, stride, int(points.shape[1]), int(points.shape[0]),
+                               _pose7(pose, "map_insert"), _ptr(ws), ws.numel() * ws.element_size(), _stream()),
+         "rslo_map_insert")
+
+
+def map_lookup(buf, points, pose, hits=None, tags=None):
+    """rslo_map_lookup: hits int32 [P] (-1 skipped / out of range, 0 not in the map, else the cell's hits); tags: None =
+    not wanted, True = allocate, or an int64 [P] tensor (all-ones, i.e. -1, where hits <= 0).  Returns hits or (hits, tags)."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if hits is None:
+        hits = torch.empty((P,), dtype=torch.int32, device=points.device)
+    if tags is True:
+        tags = torch.empty((P,), dtype=torch.int64, device=points.device)
+    if hits.shape != (P,) or (tags is not None and tags.shape != (P,)):
+        raise RsloHipError("map_lookup: hits and tags must be [P]")
+    _chk(lib().rslo_map_lookup(ptr, nbytes, src, stride, P, _pose7(pose, "map_lookup"), _ptr(hits, torch.int32, "hits"),
+                               _ptr(tags, torch.int64, "tags"), _stream()), "rslo_map_lookup")
+    return hits if tags is None else (hits, tags)
+
+
+def map_export(buf, min_hits=1, center=None, radius=0.0, rows=None, tags=None, hits=None, counts=None):
+    """rslo_map_export into preallocated rows fp32 [R, 4], tags int64 [R], hits int32 [R] (all None: R = 0, count only);
+    center: None or float64 CUDA [3].  Returns counts, int64 CUDA [2] = {matching, written}.  No host read."""
+    ptr, nbytes = _map_buf(buf)
+    R = 0 if rows is None else rows.shape[0]
+    if R and (rows.shape != (R, 4) or tags is None or hits is None or tags.shape != (R,) or hits.shape != (R,)):
+        raise RsloHipError("map_export: rows [R, 4], tags [R] and hits [R] go together")
+    if center is not None and not (center.is_cuda and center.dtype == torch.float64 and center.numel() == 3
+                                   and center.is_contiguous()):
+        raise RsloHipError("map_export: center must be 3 contiguous float64 values on the GPU")
+    if counts is None:
+        counts = torch.empty((2,), dtype=torch.int64, device=buf.device)
+    _chk(lib().rslo_map_export(ptr, nbytes, int(min_hits), _dp(center), float(radius),
+                               _ptr(rows, torch.float32, "rows") if R else None,
+                               _ptr(tags, torch.int64, "tags") if R else None,
+                               _ptr(hits, torch.int32, "hits") if R else None, R,
+                               _ptr(counts, torch.int64, "counts"), _stream()), "rslo_map_export")
+    return counts
 
 
 def chamfer_grad(xyz1, xyz2, graddist1, idx1, g1=None, g2=None):

@@ -1,0 +1,339 @@
+// World voxel map of a streamed trajectory: a persistent, incrementally filled voxel hash in the frame of scan 0
+// (rules: include/rslo_hip.h "World voxel map"; float64 restatement: rslo_amd/mapping.py VoxelMapRef).  Nothing of the
+// reference corresponds to it: evaluate.py:363-408 writes poses only.
+//
+// One caller-owned allocation: header (256 bytes) | keys u64 [cap] | tags u64 [cap] | rows f32 [cap, 4] | hits i32 [cap].
+// Open addressing, linear probing from a 64-bit mix of the key, at most RSLO_MAP_MAX_PROBE slots examined: no loop here
+// depends on the table having room.  Slots only fill and keys never move.
+//
+// Visibility (eight XCDs with separate L2s): inside the insert kernel every decision rests on the return value of an
+// atomic (atomicCAS on the key, atomicMin on the tag, atomicAdd on the hits).  The non-temporal pre-reads only skip an
+// atomic that cannot change anything: a key never changes once set, so a stale read can only show "empty" (then the
+// CAS decides); a tag only decreases, so a stale read can only be too large (then the atomicMin is issued needlessly).
+// The row of a new cell is written by the owner of its tag in the NEXT kernel of the call (slot kept in the workspace),
+// the scan counter is bumped by a third kernel after every reader of it has run.
+#include "rslo_common.h"
+
+#pragma clang fp contract(off)   /* the cell of a point must not depend on FMA formation */
+
+typedef unsigned long long map_u64;
+#define MAP_KEY_NONE (~(map_u64)0)
+#define MAP_MAGIC 0x52534c4f4d415031ull /* "RSLOMAP1" */
+#define MAP_HDR_BYTES 256
+#define MAP_SLOT_BYTES 36                /* key 8 + tag 8 + row 16 + hits 4 */
+#define MAP_MAXC 1048576.0               /* 2^20: |cell| of a stored point is below it */
+#define MAP_MIN_CAP 1024
+
+struct MapHdr {                          // int64 words: 0 magic, 1 capacity, 2-4 parameters, 8-13 counters
+  map_u64 magic;
+  long long capacity;
+  double voxel, min_range, max_range;
+  long long pad_[3];
+  map_u64 n_scans, n_cells, n_points, dropped_invalid, dropped_range, dropped_full;
+};
+static_assert(sizeof(MapHdr) <= MAP_HDR_BYTES, "map header");
+
+struct MapView {
+  MapHdr *hdr;
+  map_u64 *keys, *tags;
+  float *rows;
+  int32_t *hits;
+};
+
+static inline long long map_cap_of_bytes(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
+  if (bytes < (size_t)MAP_HDR_BYTES + (size_t)MAP_SLOT_BYTES * MAP_MIN_CAP) return 0;
+  const size_t slots = (bytes - MAP_HDR_BYTES) / MAP_SLOT_BYTES;
+  long long cap = MAP_MIN_CAP;
+  while ((size_t)cap * 2 <= slots && cap < ((long long)1 << 40)) cap *= 2;
+  return cap;
+}
+
+// the sections of a map of `cap` slots (cap from the header, checked against what the allocation holds)
+__device__ __forceinline__ bool map_view(void *map, long long cap_max, MapView &v) {
+  MapHdr *h = (MapHdr *)map;
+  const long long cap = h->capacity;
+  if (h->magic != MAP_MAGIC || cap < MAP_MIN_CAP || cap > cap_max || (cap & (cap - 1))) return false;
+  unsigned char *p = (unsigned char *)map + MAP_HDR_BYTES;
+  v.hdr = h;
+  v.keys = (map_u64 *)p;
+  v.tags = (map_u64 *)(p + (size_t)cap * 8);
+  v.rows = (float *)(p + (size_t)cap * 16);
+  v.hits = (int32_t *)(p + (size_t)cap * 32);
+  return true;
+}
+
+__device__ __forceinline__ map_u64 map_mix(map_u64 x) {      // splitmix64 finaliser
+  x ^= x >> 30;
+  x *= 0xbf58476d1ce4e5b9ull;
+  x ^= x >> 27;
+  x *= 0x94d049bb133111ebull;
+  x ^= x >> 31;
+  return x;
+}
+
+__device__ __forceinline__ void map_cross(const double *a, const double *b, double *c) {
+  c[0] = a[1] * b[2] - a[2] * b[1];
+  c[1] = a[2] * b[0] - a[0] * b[2];
+  c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// 0: key and world position valid; 1: skipped (not finite, or outside the range gate); 2: cell outside +-2^20
+__device__ __forceinline__ int map_point(const float *__restrict__ p, const double *__restrict__ pose, double voxel,
+                                         double min_range, double max_range, map_u64 &key, double *w) {
+  const float fx = p[0], fy = p[1], fz = p[2];
+  const float inf = __builtin_inff();
+  if (!(fabsf(fx) < inf && fabsf(fy) < inf && fabsf(fz) < inf)) return 1;      // NaN compares false
+  const double x[3] = {(double)fx, (double)fy, (double)fz};
+  const double d2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
+  if (!(d2 >= min_range * min_range && d2 < max_range * max_range)) return 1;
+  const double t[3] = {pose[0], pose[1], pose[2]};
+  const double qw = pose[3], v[3] = {pose[4], pose[5], pose[6]};
+  double b[3], c[3];
+  map_cross(v, x, b);
+  map_cross(v, b, c);
+  map_u64 k = 0;
+  for (int a = 0; a < 3; ++a) {
+    w[a] = t[a] + (x[a] + (2.0 * b[a] * qw + 2.0 * c[a]));       // k_pose_chain's arithmetic, not renormalised
+    const double cell = floor(w[a] / voxel);
+    if (!(fabs(cell) < MAP_MAXC)) return 2;                      // also a NaN or infinite world coordinate
+    k = (k << 21) | (map_u64)((long long)cell + 1048576);
+  }
+  key = k;
+  return 0;
+}
+
+// filled in one launch: the header by thread 0, the sections by everybody
+__global__ __launch_bounds__(256) void k_map_reset(void *map, long long cap, double voxel, double min_range,
+                                                   double max_range) {
+  unsigned char *p = (unsigned char *)map + MAP_HDR_BYTES;
+  map_u64 *keys = (map_u64 *)p, *tags = (map_u64 *)(p + (size_t)cap * 8);
+  float4 *rows = (float4 *)(p + (size_t)cap * 16);
+  int32_t *hits = (int32_t *)(p + (size_t)cap * 32);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    MapHdr *h = (MapHdr *)map;
+    h->magic = MAP_MAGIC;
+    h->capacity = cap;
+    h->voxel = voxel;
+    h->min_range = min_range;
+    h->max_range = max_range;
+    h->pad_[0] = h->pad_[1] = h->pad_[2] = 0;
+    h->n_scans = h->n_cells = h->n_points = h->dropped_invalid = h->dropped_range = h->dropped_full = 0;
+  }
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    keys[s] = MAP_KEY_NONE;
+    tags[s] = MAP_KEY_NONE;
+    rows[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+    hits[s] = 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_map_insert(void *map, long long cap_max, const float *__restrict__ points,
+                                                    int stride, int N, const double *__restrict__ pose,
+                                                    int32_t *__restrict__ slot_of) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  MapView m;
+  if (!map_view(map, cap_max, m)) {
+    slot_of[i] = -1;
+    return;
+  }
+  map_u64 key;
+  double w[3];
+  const int why = map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w);
+  if (why) {
+    // both adds by every dropped lane, each to ONE address: the compiler then folds an add into one per wave.  (Given
+    // `if (why == 1) add(a, 1); else add(b, 1);` it merges the two into one add whose address differs per lane, which
+    // is issued lane by lane: 1.4 ms for a scan whose points are all dropped.)
+    atomicAdd(&m.hdr->dropped_invalid, (map_u64)(why == 1));
+    atomicAdd(&m.hdr->dropped_range, (map_u64)(why == 2));
+    slot_of[i] = -1;
+    return;
+  }
+  const map_u64 mask = (map_u64)m.hdr->capacity - 1;
+  map_u64 s = map_mix(key) & mask;
+  int found = 0;
+  for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
+    map_u64 prev = __builtin_nontemporal_load(&m.keys[s]);
+    if (prev == MAP_KEY_NONE) {
+      prev = atomicCAS(&m.keys[s], MAP_KEY_NONE, key);
+      if (prev == MAP_KEY_NONE) {
+        atomicAdd(&m.hdr->n_cells, (map_u64)1);
+        prev = key;
+      }
+    }
+    if (prev == key) {
+      found = 1;
+      break;
+    }
+    s = (s + 1) & mask;
+  }
+  if (!found) {
+    atomicAdd(&m.hdr->dropped_full, (map_u64)1);
+    slot_of[i] = -1;
+    return;
+  }
+  const map_u64 tag = (m.hdr->n_scans << 32) | (map_u64)(uint32_t)i;
+  if (__builtin_nontemporal_load(&m.tags[s]) > tag) atomicMin(&m.tags[s], tag);
+  atomicAdd(&m.hits[s], 1);
+  atomicAdd(&m.hdr->n_points, (map_u64)1);
+  slot_of[i] = (int32_t)s;      // capacity <= 2^31 slots (rslo_map_bytes)
+}
+
+// behind the kernel boundary the tags are final for this scan: the owner of a cell's tag writes its row
+__global__ __launch_bounds__(256) void k_map_rows(void *map, long long cap_max, const float *__restrict__ points,
+                                                  int stride, int width, int N, const double *__restrict__ pose,
+                                                  const int32_t *__restrict__ slot_of) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  const int32_t s = slot_of[i];
+  MapView m;
+  if (s < 0 || !map_view(map, cap_max, m)) return;
+  const map_u64 tag = (m.hdr->n_scans << 32) | (map_u64)(uint32_t)i;
+  if (m.tags[s] != tag) return;
+  const float *p = points + (int64_t)i * stride;
+  map_u64 key;
+  double w[3];
+  if (map_point(p, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w)) return;
+  *(float4 *)(m.rows + (size_t)s * 4) = make_float4((float)w[0], (float)w[1], (float)w[2], width >= 4 ? p[3] : 0.f);
+}
+
+__global__ void k_map_scan_done(void *map, long long cap_max) {
+  MapView m;
+  if (threadIdx.x == 0 && map_view(map, cap_max, m)) m.hdr->n_scans = m.hdr->n_scans + 1;
+}
+
+__global__ __launch_bounds__(256) void k_map_lookup(void *map, long long cap_max, const float *__restrict__ points,
+                                                    int stride, int N, const double *__restrict__ pose,
+                                                    int32_t *__restrict__ hits_out, map_u64 *__restrict__ tags_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  MapView m;
+  int32_t h = -1;
+  map_u64 tag = MAP_KEY_NONE;
+  map_u64 key;
+  double w[3];
+  if (map_view(map, cap_max, m) &&
+      !map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w)) {
+    const map_u64 mask = (map_u64)m.hdr->capacity - 1;
+    map_u64 s = map_mix(key) & mask;
+    h = 0;
+    for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
+      const map_u64 k = m.keys[s];
+      if (k == key) {
+        h = m.hits[s];
+        tag = m.tags[s];
+        break;
+      }
+      if (k == MAP_KEY_NONE) break;
+      s = (s + 1) & mask;
+    }
+  }
+  hits_out[i] = h;
+  if (tags_out) tags_out[i] = tag;
+}
+
+__global__ __launch_bounds__(256) void k_map_export(void *map, long long cap_max, int min_hits,
+                                                    const double *__restrict__ center, double radius,
+                                                    float *__restrict__ rows, map_u64 *__restrict__ tags,
+                                                    int32_t *__restrict__ hits, long long max_rows,
+                                                    map_u64 *__restrict__ counts) {
+  MapView m;
+  if (!map_view(map, cap_max, m)) return;
+  const long long cap = m.hdr->capacity;
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    if (m.keys[s] == MAP_KEY_NONE) continue;
+    const int32_t h = m.hits[s];
+    if (h < min_hits) continue;
+    const float4 r = *(const float4 *)(m.rows + (size_t)s * 4);
+    if (center) {
+      const double dx = (double)r.x - center[0], dy = (double)r.y - center[1], dz = (double)r.z - center[2];
+      if (!(dx * dx + dy * dy + dz * dz < radius * radius)) continue;
+    }
+    const map_u64 o = atomicAdd(&counts[0], (map_u64)1);
+    if ((long long)o < max_rows) {
+      atomicAdd(&counts[1], (map_u64)1);
+      *(float4 *)(rows + (size_t)o * 4) = r;
+      tags[o] = m.tags[s];
+      hits[o] = h;
+    }
+  }
+}
+
+extern "C" size_t rslo_map_bytes(int64_t capacity) {
+  if (capacity < MAP_MIN_CAP || capacity > ((int64_t)1 << 31) || (capacity & (capacity - 1))) return 0;
+  return (size_t)MAP_HDR_BYTES + (size_t)MAP_SLOT_BYTES * (size_t)capacity;
+}
+
+extern "C" int rslo_map_reset(void *map, size_t map_bytes, int64_t capacity, double voxel_size, double min_range,
+                              double max_range, void *stream) {
+  RSLO_CHECK_ARG(map, "map_reset: map is null");
+  RSLO_CHECK_ARG(rslo_map_bytes(capacity) != 0, "map_reset: capacity must be a power of two in 1024 .. 2^31");
+  RSLO_CHECK_ARG(map_bytes >= rslo_map_bytes(capacity), "map_reset: map_bytes is smaller than rslo_map_bytes(capacity)");
+  RSLO_CHECK_ARG(voxel_size > 0.0 && voxel_size < (double)__builtin_inff(),
+                 "map_reset: voxel_size must be positive and finite");
+  RSLO_CHECK_ARG(min_range >= 0.0 && min_range < max_range, "map_reset: need 0 <= min_range < max_range");
+  const unsigned nb = (unsigned)(capacity / 256 < 4096 ? capacity / 256 : 4096);
+  hipLaunchKernelGGL(k_map_reset, dim3(nb), dim3(256), 0, (hipStream_t)stream, map, (long long)capacity, voxel_size,
+                     min_range, max_range);
+  RSLO_CHECK_LAUNCH("map_reset");
+  return RSLO_OK;
+}
+
+extern "C" size_t rslo_map_insert_ws_bytes(int N) { return 256 + (N > 0 ? ((size_t)N * 4 + 255) / 256 * 256 : 0); }
+
+extern "C" int rslo_map_insert(void *map, size_t map_bytes, const float *points, int stride_floats, int width, int N,
+                               const double *pose7, void *ws, size_t ws_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = map_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "map_insert: no map (map_bytes below rslo_map_bytes(1024))");
+  RSLO_CHECK_ARG(N >= 0, "map_insert: N < 0");
+  RSLO_CHECK_ARG(stride_floats >= 3 && width >= 3 && (width < 4 || stride_floats >= 4),
+                 "map_insert: stride_floats and width must be >= 3 (>= 4 to read an intensity)");
+  RSLO_CHECK_ARG(pose7, "map_insert: pose7 is null");
+  if (N > 0) {
+    RSLO_CHECK_ARG(points && ws, "map_insert: null pointer");
+    if (ws_bytes < rslo_map_insert_ws_bytes(N)) {
+      rslo_set_error("map_insert: workspace too small");
+      return RSLO_EWS;
+    }
+    int32_t *slot_of = (int32_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    const unsigned nb = (unsigned)rslo_cdiv(N, 256);
+    hipLaunchKernelGGL(k_map_insert, dim3(nb), dim3(256), 0, s, map, cap_max, points, stride_floats, N, pose7, slot_of);
+    hipLaunchKernelGGL(k_map_rows, dim3(nb), dim3(256), 0, s, map, cap_max, points, stride_floats, width, N, pose7,
+                       (const int32_t *)slot_of);
+  }
+  hipLaunchKernelGGL(k_map_scan_done, dim3(1), dim3(64), 0, s, map, cap_max);      // N == 0 still counts as a scan
+  RSLO_CHECK_LAUNCH("map_insert");
+  return RSLO_OK;
+}
+
+extern "C" int rslo_map_lookup(const void *map, size_t map_bytes, const float *points, int stride_floats, int N,
+                               const double *pose7, int32_t *hits_out, uint64_t *tags_out, void *stream) {
+  const long long cap_max = map_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "map_lookup: no map (map_bytes below rslo_map_bytes(1024))");
+  RSLO_CHECK_ARG(N >= 0 && stride_floats >= 3, "map_lookup: N < 0 or stride_floats < 3");
+  RSLO_CHECK_ARG(pose7, "map_lookup: pose7 is null");
+  if (N == 0) return RSLO_OK;
+  RSLO_CHECK_ARG(points && hits_out, "map_lookup: null pointer");
+  hipLaunchKernelGGL(k_map_lookup, dim3((unsigned)rslo_cdiv(N, 256)), dim3(256), 0, (hipStream_t)stream, (void *)map,
+                     cap_max, points, stride_floats, N, pose7, hits_out, (map_u64 *)tags_out);
+  RSLO_CHECK_LAUNCH("map_lookup");
+  return RSLO_OK;
+}
+
+extern "C" int rslo_map_export(const void *map, size_t map_bytes, int min_hits, const double *center3, double radius,
+                               float *rows, uint64_t *tags, int32_t *hits, int64_t max_rows, int64_t *counts,
+                               void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = map_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "map_export: no map (map_bytes below rslo_map_bytes(1024))");
+  RSLO_CHECK_ARG(counts && max_rows >= 0, "map_export: counts is null or max_rows < 0");
+  RSLO_CHECK_ARG(max_rows == 0 || (rows && tags && hits), "map_export: null output");
+  RSLO_CHECK_ARG(!center3 || radius >= 0.0, "map_export: radius must be >= 0 (NaN is refused)");
+  RSLO_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s));
+  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  hipLaunchKernelGGL(k_map_export, dim3(nb), dim3(256), 0, s, (void *)map, cap_max, min_hits, center3, radius, rows,
+                     (map_u64 *)tags, hits, (long long)max_rows, (map_u64 *)counts);
+  RSLO_CHECK_LAUNCH("map_export");
+  return RSLO_OK;
+}

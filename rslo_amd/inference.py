@@ -26,10 +26,11 @@ from rslo_amd.plan import EncoderPlanner
 
 
 class _Handle:
-    __slots__ = ("slot", "job", "error", "issued")
+    __slots__ = ("slot", "job", "error", "issued", "source")
 
     def __init__(self, slot):
         self.slot, self.job, self.error, self.issued = slot, None, None, threading.Event()
+        self.source = None      # OdometryRunner with a voxel map: the tensor the caller passed to submit()
 
 
 class EncoderGraphRunner:
@@ -241,10 +242,17 @@ class OdometryRunner:
       script/create_hdf5.py:130-147 with normal_radius / normal_max_nn, plus the reader's zero_vertical rule) on the plan
       stream immediately in front of the scan's structure work, into buffers allocated once per arena.  No stream is
       added and nothing synchronises.  normals="input" (the default) is the path above, unchanged.
+    * World map: voxel_map=VoxelMap(...) (rslo_amd/mapping.py, csrc/map.hip) registers every scan: run() inserts the tensor
+      the caller passed to submit() (its first four columns are x, y, z, intensity in both input forms) under row n of
+      the trajectory, on the caller's stream behind the head and pose chain of that scan: at most three launches, no
+      synchronisation.  The encoder job's cloud is NOT read: with normals="estimate" it is an arena buffer the helper
+      thread may overwrite as soon as the event recorded by EncoderGraphRunner.run has passed.  The caller keeps the
+      submitted tensor unmodified until run() of its handle has been consumed on the device.  reset() also resets the
+      map (a new sequence has a new frame); its figures come from voxel_map.stats().  None (the default): no map.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
-                 normals="input", normal_radius=0.6, normal_max_nn=30):
+                 normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -288,6 +296,11 @@ class OdometryRunner:
         self._pair = None          # [1, 2C, H, W] static input of the head graph
         self._graph = None
         self._n = 0                # scans of the current sequence (host mirror of the device counter)
+        self.voxel_map = voxel_map
+        if voxel_map is not None:
+            if voxel_map.device != dev:
+                raise capi.RsloHipError("OdometryRunner: the voxel map lives on %s, the runner on %s" % (voxel_map.device, dev))
+            voxel_map.reserve(int(point_capacity))      # run() must not allocate
         self.stats = {"scans": 0, "encoder_runs": 0, "head_replays": 0, "head_eager": 0, "captures": 0,
                       "weight_refreshes": 0}
 
@@ -303,7 +316,12 @@ class OdometryRunner:
             if cloud.shape[0] > self.encoder.point_capacity:
                 raise capi.RsloHipError("OdometryRunner.submit: the scan exceeds point_capacity = %d"
                                         % self.encoder.point_capacity)
-        return self.encoder.submit(cloud)
+        if self.voxel_map is not None and not (torch.is_tensor(cloud) and cloud.is_cuda and cloud.dtype == torch.float32
+                                               and cloud.dim() == 2):
+            raise capi.RsloHipError("OdometryRunner.submit: a runner with a voxel map takes one fp32 CUDA [P, F] tensor")
+        h = self.encoder.submit(cloud)
+        h.source = cloud if self.voxel_map is not None else None
+        return h
 
     def _append_normals(self, scan, arena, k):
         """pre-plan hook (helper thread, plan stream): raw scan -> the arena's [P, 7] cloud"""
@@ -318,6 +336,8 @@ class OdometryRunner:
         """A new sequence: the next scan is paired with itself and seeds a new trajectory."""
         self._count.zero_()
         self._n = 0
+        if self.voxel_map is not None:
+            self.voxel_map.reset()
 
     def trajectory(self):
         return self._traj[:min(self._n, self.capacity)]
@@ -377,6 +397,8 @@ class OdometryRunner:
             self._head_and_chain()
             self.stats["head_eager"] += 1
         n = self._n
+        if self.voxel_map is not None:      # behind the pose chain that wrote row n, on this stream
+            self.voxel_map.insert(handle.source, self._traj[n])
         self._n += 1
         self.stats["scans"] += 1
         return self._rel[n], self._traj[n]

@@ -121,10 +121,23 @@ def sequence_scan(i, seed=0, n_el=64, n_az=2083):
     """Scan i of a synthetic drive through one world (streaming odometry, scripts/odometry_stream.py): the sensor
     advances 0.8-1.2 m per scan with a slowly varying heading (a few tenths of a degree per scan, from `seed`), so
     consecutive scans overlap like a KITTI sequence at 10 Hz."""
+    x, y, yaw = _sequence_xy_yaw(i, seed)
+    return scan(n_az, n_el, (x, y), yaw, scan_seed=7 * seed + 3 * i + 1)
+
+
+def _sequence_xy_yaw(i, seed):
+    """sensor position and heading of scan i of the drive of `seed`"""
     r = np.random.default_rng(5000 + seed)
     steps = r.uniform(0.8, 1.2, i + 1)
     dyaw = np.deg2rad(r.uniform(-0.4, 0.4, i + 1))
     yaw = np.cumsum(dyaw) - dyaw[0]
     x = float(np.sum(steps[1:] * np.cos(yaw[1:]))) if i > 0 else 0.0
     y = float(np.sum(steps[1:] * np.sin(yaw[1:]))) if i > 0 else 0.0
-    return scan(n_az, n_el, (x, y), float(yaw[i]), scan_seed=7 * seed + 3 * i + 1)
+    return x, y, float(yaw[i])
+
+
+def sequence_pose(i, seed=0):
+    """The pose sequence_scan(i, seed) is taken from, as [7] float64 (t, q wxyz) in the frame of scan 0: t = (x, y, 0), a
+    rotation by yaw about z.  world = T p (the convention of rslo_pose_chain / geometric.odom_to_abs_pose)."""
+    x, y, yaw = _sequence_xy_yaw(i, seed)
+    return np.array([x, y, 0.0, np.cos(0.5 * yaw), 0.0, 0.0, np.sin(0.5 * yaw)], np.float64)

@@ -5,6 +5,7 @@
     python scripts/odometry_stream.py --runner-only --load-scans /tmp/drive.npz --scans 20 --warmup 5   # under rocprofv3
     python scripts/odometry_stream.py --launches A_kernel_stats.csv B_kernel_stats.csv --scans-a 20 --scans-b 60
     python scripts/odometry_stream.py --raw --scans 200 --warmup 20 [--out profiles/odometry_stream_raw.json]
+    python scripts/odometry_stream.py --map --scans 200 --warmup 20 [--map-out map.ply] [--out profiles/odometry_stream_map.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -16,6 +17,11 @@ Both are timed with device events over --scans scans after --warmup scans; one J
 normals="estimate" (csrc/normals.hip on the plan stream) and reports its ms per scan, the distance of its trajectory
 from the [P, 7] run and the median angle between the estimated and the drive's analytic normals (a report, not a
 test: the analytic normals are exact only away from edges).
+--map: one more runner loop with a world voxel map attached (rslo_amd.mapping.VoxelMap, csrc/map.hip: every run() inserts
+its scan under its absolute pose): ms per scan with the map beside the plain runner's, the inserts alone (the same scans
+under the same trajectory rows into a second map, device events over the timed scans), the map's counters, the mean
+overlap of each scan with the map before its insertion, and --map-out FILE.ply.  The same figures under the drive's own
+poses (synthetic.sequence_pose; --seed must be the drive's): with random weights the runner's trajectory is not a drive.
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -87,6 +93,10 @@ def main():
     ap.add_argument("--workers", type=int, default=14)
     ap.add_argument("--runner-only", action="store_true")
     ap.add_argument("--raw", action="store_true", help="also run the runner with normals=\"estimate\" on [P, 4] scans")
+    ap.add_argument("--map", action="store_true", help="also run the runner with a world voxel map attached")
+    ap.add_argument("--map-voxel", type=float, default=0.2)
+    ap.add_argument("--map-capacity", type=int, default=1 << 22, help="slots of the map's table (a power of two)")
+    ap.add_argument("--map-out", default=None, help="write the map as a binary PLY")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -224,6 +234,65 @@ def main():
         res["normals_median_angle_deg"] = float(torch.rad2deg(torch.acos(cosang)).median())
         res["normals_compared_points"] = int(both.sum())
         res["normals_points_with_fewer_than_3_neighbours"] = int((cnt < 3).sum())
+    if args.map:
+        from rslo_amd import mapping
+        vmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+        mapped = inference.OdometryRunner(net, voxel_map=vmap)
+        pend.clear()
+
+        def run_map(rng):
+            rng = list(rng)
+            for k, i in enumerate(rng):
+                if i not in pend:
+                    pend[i] = mapped.submit(scans[i])
+                if k + 1 < len(rng) and rng[k + 1] not in pend:
+                    pend[rng[k + 1]] = mapped.submit(scans[rng[k + 1]])
+                mapped.run(pend.pop(i))
+        res["map_ms_per_scan"], res["map_host_ms_per_scan"] = [round(v, 3) for v in timed(run_map)]
+        res["map_minus_runner_ms_per_scan"] = round(res["map_ms_per_scan"] - res["runner_ms_per_scan"], 3)
+        traj = mapped.trajectory().clone()
+        res["map_traj_equals_runner"] = bool(torch.equal(traj.view(torch.int64), traj_input.view(torch.int64)))      # bits: a NaN equals itself
+        res["map_stats"] = vmap.stats()
+        res["map_voxel"], res["map_capacity"] = args.map_voxel, args.map_capacity
+        res["map_load"] = round(res["map_stats"]["n_cells"] / float(args.map_capacity), 4)
+        mapped.close()
+        # the inserts alone: the same scans into a second map, under the runner's trajectory rows and under the drive's own
+        # poses (synthetic.sequence_pose: the registered cloud a trained network would approach)
+        alone = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+        alone.reserve(max(s.shape[0] for s in scans))
+
+        def insert_pass(poses):
+            """(ms per timed insert, counters, mean overlap of a scan with the map before its insertion)"""
+            alone.reset()
+            for i in range(W):
+                alone.insert(scans[i], poses[i])
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(W, W + N):
+                alone.insert(scans[i], poses[i])
+            e1.record()
+            e1.synchronize()
+            stats = alone.stats()
+            alone.reset()
+            ov = torch.zeros((), dtype=torch.float32, device=dev)      # one host read at the end
+            for i in range(W + N):
+                if i > 0:
+                    ov += alone.overlap(scans[i], poses[i])
+                alone.insert(scans[i], poses[i])
+            return round(e0.elapsed_time(e1) / N, 4), stats, round(float(ov) / (W + N - 1), 4)
+
+        res["map_insert_alone_ms_per_scan"], stats, res["map_mean_overlap_before_insert"] = insert_pass(traj)
+        res["map_insert_alone_stats_equal"] = stats == res["map_stats"]
+        if True:      # (--load-scans: the file must hold the drive of --seed)
+            from rslo_amd import synthetic
+            true = [torch.from_numpy(synthetic.sequence_pose(i, args.seed)).to(dev) for i in range(W + N)]
+            (res["map_true_pose_insert_ms_per_scan"], res["map_true_pose_stats"],
+             res["map_true_pose_mean_overlap_before_insert"]) = insert_pass(true)
+            res["map_true_pose_load"] = round(res["map_true_pose_stats"]["n_cells"] / float(args.map_capacity), 4)
+        if args.map_out:
+            vmap.save_ply(args.map_out)
+            res["map_ply_bytes"] = os.path.getsize(args.map_out)
     line = json.dumps(res)
     print(line)
     if args.out:
