@@ -957,6 +957,65 @@ RSLO_API int rslo_map_export(const void *map, size_t map_bytes, int min_hits, co
                              double radius, float *rows /*[max_rows,4]*/, uint64_t *tags /*[max_rows]*/,
                              int32_t *hits /*[max_rows]*/, int64_t max_rows, int64_t *counts /*[2]*/, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Scan-to-map registration (csrc/mapreg.hip): the world voxel map as a registration target.  Read-only on the map;
+ * the float64 restatement is rslo_amd/mapping.py (VoxelMapRef.nearest / normal_equations / register).  All arithmetic
+ * is IEEE double without contraction, in the order written here.  Every call takes the map_bytes AND the voxel_size
+ * handed to rslo_map_reset: the host checks max_dist against that voxel_size, the kernels check it against the
+ * header and treat a map whose cell edge differs like a map that was never reset (no match anywhere).
+ * rslo_map_params reads {voxel_size, min_range, max_range} of a map into HOST memory (it synchronises `stream`; not
+ * capturable) for a caller that did not keep them.
+ *
+ * Nearest (rslo_map_nearest).  For point i the map's own function gives the status, the world position w and the cell
+ * c, with the validity rules of rslo_map_lookup.  Candidates are the 27 cells c + {-1,0,1}^3; a neighbour with any
+ * |cell| >= 2^20 is skipped.  Each candidate is found with the bounded probe of rslo_map_lookup and must have
+ * hits >= min_hits.  With m = double(row.xyz) of a candidate: d = w - m, d2 = d.x*d.x + d.y*d.y + d.z*d.z (left to
+ * right).  The winner has the smallest d2, ties go to the smallest tag; it is accepted only if d2 < max_dist*max_dist.
+ * tags_out int64 [N]: the winner's tag, -1 without a match or for an invalid point; d2_out double [N]: -1.0 without a
+ * match; rows_out float [N,4] (may be NULL): the matched row, zeros without a match.  0 < max_dist <= voxel_size,
+ * anything else (NaN included) is RSLO_EINVAL: under that condition the 27 cells hold every stored row within
+ * max_dist of w, so the result is the exact nearest stored point.  One launch, capturable.
+ *
+ * Normal equations (rslo_map_normal_eq) at pose7 for metric 0 (point) or 1 (plane).  Every matched point (the match
+ * of rslo_map_nearest under the same max_dist / min_hits) adds to 28 double sums and a pair count, with d = w - m:
+ *   plane term, when metric == 1 and the scan normal n_s = double(columns 4..6) has n_s.n_s >= 0.25 (summed left to
+ *     right; a zeroed or NaN normal fails it): n = n_s + (2.0*b*q.w + 2.0*c), b = v x n_s, c = v x b (the rotation of
+ *     the map's w, not renormalised), r = n.x*d.x + n.y*d.y + n.z*d.z, a = (n, w x n):
+ *     H(i,j) += a_i*a_j, g_i += a_i*r, cost += r*r.  (n is held fixed over a step.)
+ *   point term, every other matched point: J = [I | -[w]x] (3 x 6, rows J0 J1 J2):
+ *     H(i,j) += J0_i*J0_j + J1_i*J1_j + J2_i*J2_j, g_i += J0_i*d.x + J1_i*d.y + J2_i*d.z, cost += d.x*d.x + d.y*d.y + d.z*d.z.
+ *   metric == 1 needs width >= 7 and stride_floats >= 7, else RSLO_EINVAL.
+ * out29 = the upper triangle of H row by row (21), g (6), cost, then the pair count as a double.  The reduction is
+ * bit-reproducible: no floating-point atomics; inside a block of 256 points a fixed shuffle tree per wave, then the
+ * waves in order; the block partials are summed in block order by a second launch.  ws: rslo_map_register_ws_bytes(N),
+ * 8-byte aligned.  Two launches, capturable.
+ *
+ * Register (rslo_map_register): `iters` (1..32) Gauss-Newton iterations on the device, pose7 updated in place.  Per
+ * iteration: the normal equations at the current pose; M = H + damping*I factored by plain row-by-row 6 x 6 Cholesky
+ * (fails when a pivot is <= 0 or not finite); delta = -M^-1 g = (dt, dtheta), a world-frame increment;
+ * theta = |dtheta|; dq = (1, dtheta/2) when theta < 1e-12, else (cos(theta/2), sin(theta/2)/theta * dtheta);
+ * q' = (dq (x) q) / sqrt(sum of squares); t' = dt + rotate(dq, t) with rslo_pose_chain's rotate formula.
+ * info double [iters, 8], row = {status, pairs, cost, |dt|, theta, 0, 0, 0}; status 0: step taken; 1: pairs <
+ * min_pairs, pose untouched; 2: not positive definite (or a step that is not finite), pose untouched; 3: skipped
+ * because an earlier iteration had |dt| < tol_t and theta < tol_r (the row is {3, 0, ...}).  tol_t = tol_r = 0 never
+ * skips.  The "converged" flag lives in the workspace; later iterations exit early.  No host read; 2 launches per
+ * iteration whatever happens (1 for N == 0), so the call is capturable.  iters outside 1..32, a negative or NaN
+ * tolerance: RSLO_EINVAL; a short workspace: RSLO_EWS; an argument error writes nothing.
+ * ------------------------------------------------------------------------------------ */
+RSLO_API int rslo_map_params(const void *map, size_t map_bytes, double *params3_host, void *stream);
+RSLO_API int rslo_map_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                              int stride_floats, int N, const double *pose7, double max_dist, int min_hits,
+                              int64_t *tags_out /*[N]*/, double *d2_out /*[N]*/, float *rows_out /*[N,4] or NULL*/,
+                              void *stream);
+RSLO_API size_t rslo_map_register_ws_bytes(int N);
+RSLO_API int rslo_map_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                int stride_floats, int width, int N, const double *pose7, int metric, double max_dist,
+                                int min_hits, double *out29, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_map_register(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                               int stride_floats, int width, int N, double *pose7, int iters, int metric,
+                               double max_dist, int min_hits, double damping, int min_pairs, double tol_t, double tol_r,
+                               double *info /*[iters,8]*/, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

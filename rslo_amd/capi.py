@@ -196,6 +196,12 @@ SIGNATURES = {
     "rslo_map_insert": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "rslo_map_lookup": (C.c_int, [_vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "rslo_map_export": (C.c_int, [_vp, _sz, _i, _vp, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "rslo_map_params": (C.c_int, [_vp, _sz, _vp, _vp]),
+    "rslo_map_nearest": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, _i, _vp, _vp, _vp, _vp]),
+    "rslo_map_register_ws_bytes": (_sz, [_i]),
+    "rslo_map_normal_eq": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _i, _vp, _i, C.c_double, _i, _vp, _vp, _sz, _vp]),
+    "rslo_map_register": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, _i, C.c_double, _i,
+                                    C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -1160,6 +1166,107 @@ def map_export(buf, min_hits=1, center=None, radius=0.0, rows=None, tags=None, h
                                _ptr(hits, torch.int32, "hits") if R else None, R,
                                _ptr(counts, torch.int64, "counts"), _stream()), "rslo_map_export")
     return counts
+
+
+# scan-to-map registration (csrc/mapreg.hip; rules: include/rslo_hip.h "Scan-to-map registration")
+MAP_METRICS = {"point": 0, "plane": 1}
+
+
+def map_params(buf):
+    """rslo_map_params: (voxel_size, min_range, max_range) of a map, read on the host (synchronises the current stream)."""
+    ptr, nbytes = _map_buf(buf)
+    out = (C.c_double * 3)()
+    _chk(lib().rslo_map_params(ptr, nbytes, out, _stream()), "rslo_map_params")
+    return tuple(out)
+
+
+def _map_metric(metric):
+    if metric not in MAP_METRICS:
+        raise RsloHipError("map: metric must be \"point\" or \"plane\", got %r" % (metric,))
+    return MAP_METRICS[metric]
+
+
+def map_nearest(buf, points, pose, voxel_size=None, max_dist=None, min_hits=1, rows=None, tags=None, d2=None):
+    """rslo_map_nearest: the exact nearest stored point of every point (fp32 CUDA [P, F >= 3], read in place) under pose
+    (float64 CUDA [7]) within max_dist (None: voxel_size; voxel_size None: read from the map, one host read).  Returns
+    (tags int64 [P], d2 float64 [P]) -- -1 / -1.0 without a match -- and, with rows=True or an fp32 [P, 4] tensor, the
+    matched rows (zeros without a match).  Read-only, no host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if voxel_size is None:
+        voxel_size = map_params(buf)[0]
+    if tags is None:
+        tags = torch.empty((P,), dtype=torch.int64, device=points.device)
+    if d2 is None:
+        d2 = torch.empty((P,), dtype=torch.float64, device=points.device)
+    if rows is True:
+        rows = torch.empty((P, 4), dtype=torch.float32, device=points.device)
+    if tags.shape != (P,) or d2.shape != (P,) or (rows is not None and rows.shape != (P, 4)):
+        raise RsloHipError("map_nearest: tags and d2 must be [P], rows [P, 4]")
+    _chk(lib().rslo_map_nearest(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "map_nearest"),
+                                float(voxel_size if max_dist is None else max_dist), int(min_hits),
+                                _ptr(tags, torch.int64, "tags"), _ptr(d2, torch.float64, "d2"),
+                                _ptr(rows, torch.float32, "rows"), _stream()), "rslo_map_nearest")
+    return (tags, d2) if rows is None else (tags, d2, rows)
+
+
+def map_register_ws(n_points, device):
+    """a workspace for map_normal_eq / map_register over up to n_points points"""
+    return torch.empty((int(lib().rslo_map_register_ws_bytes(int(n_points))) // 8,), dtype=torch.int64, device=device)
+
+
+def _map_ws(ws, P, device):
+    if ws is None:
+        return map_register_ws(P, device)
+    if not (ws.is_cuda and ws.is_contiguous()):
+        raise RsloHipError("map: the workspace must be a contiguous CUDA tensor")
+    return ws
+
+
+def map_normal_eq(buf, points, pose, voxel_size=None, metric="plane", max_dist=None, min_hits=1, out=None, ws=None):
+    """rslo_map_normal_eq: out float64 CUDA [29] = the upper triangle of H (21), g (6), cost, pairs at pose, over the
+    matches of map_nearest.  metric "plane" reads the normals at columns 4..6 of points.  No host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if voxel_size is None:
+        voxel_size = map_params(buf)[0]
+    if out is None:
+        out = torch.empty((29,), dtype=torch.float64, device=points.device)
+    if out.shape != (29,):
+        raise RsloHipError("map_normal_eq: out must be [29]")
+    ws = _map_ws(ws, P, points.device)
+    _chk(lib().rslo_map_normal_eq(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
+                                  _pose7(pose, "map_normal_eq"), _map_metric(metric),
+                                  float(voxel_size if max_dist is None else max_dist), int(min_hits),
+                                  _ptr(out, torch.float64, "out"), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+         "rslo_map_normal_eq")
+    return out
+
+
+def map_register(buf, points, pose, voxel_size=None, iters=5, metric="plane", max_dist=None, min_hits=1, damping=0.0,
+                 min_pairs=50, tol_t=0.0, tol_r=0.0, info=None, ws=None):
+    """rslo_map_register: `iters` Gauss-Newton iterations of points against the map; pose (float64 CUDA [7]) is updated
+    IN PLACE.  Returns info float64 CUDA [iters, 8]: rows {status, pairs, cost, |dt|, theta, 0, 0, 0}, status 0 step taken, 1
+    too few pairs, 2 not positive definite, 3 skipped after convergence.  No host read, a fixed number of launches: capturable."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    iters = int(iters)
+    if voxel_size is None:
+        voxel_size = map_params(buf)[0]
+    if info is None:
+        info = torch.empty((max(iters, 0), 8), dtype=torch.float64, device=points.device)
+    if info.shape != (iters, 8):
+        raise RsloHipError("map_register: info must be [iters, 8]")
+    ws = _map_ws(ws, P, points.device)
+    _chk(lib().rslo_map_register(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
+                                 _pose7(pose, "map_register"), iters, _map_metric(metric),
+                                 float(voxel_size if max_dist is None else max_dist), int(min_hits), float(damping),
+                                 int(min_pairs), float(tol_t), float(tol_r), _ptr(info, torch.float64, "info"),
+                                 ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_map_register")
+    return info
 
 
 def chamfer_grad(xyz1, xyz2, graddist1, idx1, g1=None, g2=None):

@@ -13,32 +13,11 @@
 // The row of a new cell is written by the owner of its tag in the NEXT kernel of the call (slot kept in the workspace),
 // the scan counter is bumped by a third kernel after every reader of it has run.
 #include "rslo_common.h"
+#include "map_table.h"
 
 #pragma clang fp contract(off)   /* the cell of a point must not depend on FMA formation */
 
-typedef unsigned long long map_u64;
-#define MAP_KEY_NONE (~(map_u64)0)
-#define MAP_MAGIC 0x52534c4f4d415031ull /* "RSLOMAP1" */
-#define MAP_HDR_BYTES 256
 #define MAP_SLOT_BYTES 36                /* key 8 + tag 8 + row 16 + hits 4 */
-#define MAP_MAXC 1048576.0               /* 2^20: |cell| of a stored point is below it */
-#define MAP_MIN_CAP 1024
-
-struct MapHdr {                          // int64 words: 0 magic, 1 capacity, 2-4 parameters, 8-13 counters
-  map_u64 magic;
-  long long capacity;
-  double voxel, min_range, max_range;
-  long long pad_[3];
-  map_u64 n_scans, n_cells, n_points, dropped_invalid, dropped_range, dropped_full;
-};
-static_assert(sizeof(MapHdr) <= MAP_HDR_BYTES, "map header");
-
-struct MapView {
-  MapHdr *hdr;
-  map_u64 *keys, *tags;
-  float *rows;
-  int32_t *hits;
-};
 
 static inline long long map_cap_of_bytes(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
   if (bytes < (size_t)MAP_HDR_BYTES + (size_t)MAP_SLOT_BYTES * MAP_MIN_CAP) return 0;
@@ -46,60 +25,6 @@ static inline long long map_cap_of_bytes(size_t bytes) {      // the largest cap
   long long cap = MAP_MIN_CAP;
   while ((size_t)cap * 2 <= slots && cap < ((long long)1 << 40)) cap *= 2;
   return cap;
-}
-
-// the sections of a map of `cap` slots (cap from the header, checked against what the allocation holds)
-__device__ __forceinline__ bool map_view(void *map, long long cap_max, MapView &v) {
-  MapHdr *h = (MapHdr *)map;
-  const long long cap = h->capacity;
-  if (h->magic != MAP_MAGIC || cap < MAP_MIN_CAP || cap > cap_max || (cap & (cap - 1))) return false;
-  unsigned char *p = (unsigned char *)map + MAP_HDR_BYTES;
-  v.hdr = h;
-  v.keys = (map_u64 *)p;
-  v.tags = (map_u64 *)(p + (size_t)cap * 8);
-  v.rows = (float *)(p + (size_t)cap * 16);
-  v.hits = (int32_t *)(p + (size_t)cap * 32);
-  return true;
-}
-
-__device__ __forceinline__ map_u64 map_mix(map_u64 x) {      // splitmix64 finaliser
-  x ^= x >> 30;
-  x *= 0xbf58476d1ce4e5b9ull;
-  x ^= x >> 27;
-  x *= 0x94d049bb133111ebull;
-  x ^= x >> 31;
-  return x;
-}
-
-__device__ __forceinline__ void map_cross(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-// 0: key and world position valid; 1: skipped (not finite, or outside the range gate); 2: cell outside +-2^20
-__device__ __forceinline__ int map_point(const float *__restrict__ p, const double *__restrict__ pose, double voxel,
-                                         double min_range, double max_range, map_u64 &key, double *w) {
-  const float fx = p[0], fy = p[1], fz = p[2];
-  const float inf = __builtin_inff();
-  if (!(fabsf(fx) < inf && fabsf(fy) < inf && fabsf(fz) < inf)) return 1;      // NaN compares false
-  const double x[3] = {(double)fx, (double)fy, (double)fz};
-  const double d2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
-  if (!(d2 >= min_range * min_range && d2 < max_range * max_range)) return 1;
-  const double t[3] = {pose[0], pose[1], pose[2]};
-  const double qw = pose[3], v[3] = {pose[4], pose[5], pose[6]};
-  double b[3], c[3];
-  map_cross(v, x, b);
-  map_cross(v, b, c);
-  map_u64 k = 0;
-  for (int a = 0; a < 3; ++a) {
-    w[a] = t[a] + (x[a] + (2.0 * b[a] * qw + 2.0 * c[a]));       // k_pose_chain's arithmetic, not renormalised
-    const double cell = floor(w[a] / voxel);
-    if (!(fabs(cell) < MAP_MAXC)) return 2;                      // also a NaN or infinite world coordinate
-    k = (k << 21) | (map_u64)((long long)cell + 1048576);
-  }
-  key = k;
-  return 0;
 }
 
 // filled in one launch: the header by thread 0, the sections by everybody

@@ -1,0 +1,414 @@
+// Scan-to-map registration against the world voxel map (rules: include/rslo_hip.h "Scan-to-map registration"; float64
+// restatement: rslo_amd/mapping.py VoxelMapRef.nearest / normal_equations / register): the exact nearest stored point of
+// every scan point among the 27 cells around it, the 6 x 6 normal equations of a point-to-point / point-to-plane
+// cost over the matched pairs, and Gauss-Newton iterations that stay on the device.  Everything here only READS the map.
+//
+// Nearest: one thread per point.  The 27 probe chains of a point are independent 8-byte gathers into a table far larger
+// than L2, so the first-slot keys of all 27 are loaded before any of them is examined (27 loads in flight per lane); a
+// chain goes on alone only when its first slot held another cell's key.  Rows, hits and tags are read for matching
+// cells only, a tag only to break a tie on d2.
+//
+// Sums: 28 doubles and the pair count per point, reduced in a fixed order -- a shuffle tree inside each wave, the four
+// waves of a block in wave order, the blocks in block order by the second stage (one wave; lane j owns sum j).  No
+// floating-point atomic anywhere: two runs give the same bits.
+#include "rslo_common.h"
+#include "map_table.h"
+
+#include <math.h>
+#include <string.h>
+
+#pragma clang fp contract(off)   /* the sums are specified operation by operation */
+
+#define MR_NSUM 29                       /* 21 H (upper triangle, row-major) + 6 g + cost + pairs */
+#define MR_BLOCK 256
+#define MR_WS_HDR 256                    /* int32 word 0: the "converged" flag of rslo_map_register */
+#define MR_MAX_ITERS 32
+
+static long long mr_cap_max(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
+  long long cap = 0;
+  for (long long c = MAP_MIN_CAP; c <= ((long long)1 << 31) && rslo_map_bytes(c) <= bytes; c *= 2) cap = c;
+  return cap;
+}
+
+// The stored point nearest to w among the cells key + {-1,0,1}^3: slot and d2 of the winner (smallest d2, then smallest
+// tag), its position in mm.  False when no candidate cell is stored with hits >= min_hits.
+__device__ __forceinline__ bool mr_nearest(const MapView &m, map_u64 key, const double *w, int min_hits, uint32_t &bslot,
+                                           double &bd2, double *mm) {
+  const uint32_t mask = (uint32_t)((map_u64)m.hdr->capacity - 1);      // capacity <= 2^31
+  const int c[3] = {(int)(key >> 42) & 0x1fffff, (int)(key >> 21) & 0x1fffff, (int)key & 0x1fffff};
+  map_u64 k0[27];
+  uint32_t s0[27];
+#pragma unroll
+  for (int j = 0; j < 27; ++j) {
+    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
+    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
+    s0[j] = (uint32_t)map_mix(nk) & mask;      // (a neighbour outside the key space is not examined below; its slot is in range)
+    k0[j] = m.keys[s0[j]];
+  }
+  bool found = false;
+#pragma unroll
+  for (int j = 0; j < 27; ++j) {
+    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
+    if (x < 1 || x > 0x1fffff || y < 1 || y > 0x1fffff || z < 1 || z > 0x1fffff) continue;      // |cell| >= 2^20
+    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
+    map_u64 k = k0[j];
+    uint32_t s = s0[j];
+    for (int probe = 1; k != nk && k != MAP_KEY_NONE && probe < RSLO_MAP_MAX_PROBE; ++probe) {
+      s = (s + 1) & mask;
+      k = m.keys[s];
+    }
+    if (k != nk) continue;
+    if (min_hits > 1 && m.hits[s] < min_hits) continue;      // a stored cell has hits >= 1
+    const float4 r = *(const float4 *)(m.rows + (size_t)s * 4);
+    const double p[3] = {(double)r.x, (double)r.y, (double)r.z};
+    const double dx = w[0] - p[0], dy = w[1] - p[1], dz = w[2] - p[2];
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    if (!found || d2 < bd2 || (d2 == bd2 && m.tags[s] < m.tags[bslot])) {
+      found = true;
+      bslot = s;
+      bd2 = d2;
+      mm[0] = p[0];
+      mm[1] = p[1];
+      mm[2] = p[2];
+    }
+  }
+  return found;
+}
+
+// the map as the registration calls accept it: reset, and with the cell edge the caller was checked against
+__device__ __forceinline__ bool mr_view(const void *map, long long cap_max, double voxel, MapView &m) {
+  return map_view((void *)map, cap_max, m) && m.hdr->voxel == voxel;
+}
+
+__global__ __launch_bounds__(MR_BLOCK) void k_map_nearest(const void *map, long long cap_max, double voxel,
+                                                          const float *__restrict__ points, int stride, int N,
+                                                          const double *__restrict__ pose, double max_dist, int min_hits,
+                                                          long long *__restrict__ tags_out, double *__restrict__ d2_out,
+                                                          float *__restrict__ rows_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  MapView m;
+  long long tag = -1;
+  double d2 = -1.0;
+  float4 row = make_float4(0.f, 0.f, 0.f, 0.f);
+  map_u64 key;
+  double w[3], mm[3], bd2;
+  uint32_t s;
+  if (mr_view(map, cap_max, voxel, m) &&
+      !map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
+      mr_nearest(m, key, w, min_hits, s, bd2, mm) && bd2 < max_dist * max_dist) {
+    tag = (long long)m.tags[s];
+    d2 = bd2;
+    row = *(const float4 *)(m.rows + (size_t)s * 4);
+  }
+  tags_out[i] = tag;
+  d2_out[i] = d2;
+  if (rows_out) *(float4 *)(rows_out + (size_t)i * 4) = row;
+}
+
+// block partial [MR_NSUM] of the addends of points blockIdx.x * 256 .. + 255 at the pose in pose7
+__global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long long cap_max, double voxel,
+                                                           const float *__restrict__ points, int stride, int width, int N,
+                                                           const double *__restrict__ pose, int metric, double max_dist,
+                                                           int min_hits, int iter, const int32_t *__restrict__ flag,
+                                                           double *__restrict__ partials) {
+  if (iter > 0 && *flag) return;      // converged in an earlier iteration: the second stage does not read the partials
+  __shared__ double part[MR_BLOCK / 64][MR_NSUM];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double acc[MR_NSUM];
+#pragma unroll
+  for (int k = 0; k < MR_NSUM; ++k) acc[k] = 0.0;
+  MapView m;
+  map_u64 key;
+  double w[3], mm[3], bd2;
+  uint32_t s;
+  if (i < N && mr_view(map, cap_max, voxel, m)) {
+    const float *p = points + (int64_t)i * stride;
+    if (!map_point(p, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
+        mr_nearest(m, key, w, min_hits, s, bd2, mm) && bd2 < max_dist * max_dist) {
+      const double d[3] = {w[0] - mm[0], w[1] - mm[1], w[2] - mm[2]};
+      // the rows of the residual's Jacobian with respect to the world-frame twist (dt, dtheta): one for a plane term,
+      // three for a point term; addend of H(a, b) = J0[a]*J0[b] + J1[a]*J1[b] + J2[a]*J2[b], left to right
+      double J[3][6], r[3];
+      int rows = 3;
+      if (metric == 1) {
+        const double ns[3] = {(double)p[4], (double)p[5], (double)p[6]};
+        if (ns[0] * ns[0] + ns[1] * ns[1] + ns[2] * ns[2] >= 0.25) {      // false for a NaN normal as well
+          const double v[3] = {pose[4], pose[5], pose[6]};
+          double b[3], c[3], n[3], wn[3];
+          map_cross(v, ns, b);
+          map_cross(v, b, c);
+          for (int a = 0; a < 3; ++a) n[a] = ns[a] + (2.0 * b[a] * pose[3] + 2.0 * c[a]);
+          map_cross(w, n, wn);
+          for (int a = 0; a < 3; ++a) {
+            J[0][a] = n[a];
+            J[0][3 + a] = wn[a];
+          }
+          r[0] = n[0] * d[0] + n[1] * d[1] + n[2] * d[2];
+          rows = 1;
+        }
+      }
+      if (rows == 3) {      // J = [I | -[w]x]
+        for (int a = 0; a < 3; ++a) {
+          for (int b = 0; b < 3; ++b) J[a][b] = a == b ? 1.0 : 0.0;
+          r[a] = d[a];
+        }
+        J[0][3] = 0.0, J[0][4] = w[2], J[0][5] = -w[1];
+        J[1][3] = -w[2], J[1][4] = 0.0, J[1][5] = w[0];
+        J[2][3] = w[1], J[2][4] = -w[0], J[2][5] = 0.0;
+      }
+      int o = 0;
+      if (rows == 1) {
+        for (int a = 0; a < 6; ++a)
+          for (int b = a; b < 6; ++b) acc[o++] = J[0][a] * J[0][b];
+        for (int a = 0; a < 6; ++a) acc[o++] = J[0][a] * r[0];
+        acc[o++] = r[0] * r[0];
+      } else {
+        for (int a = 0; a < 6; ++a)
+          for (int b = a; b < 6; ++b) acc[o++] = J[0][a] * J[0][b] + J[1][a] * J[1][b] + J[2][a] * J[2][b];
+        for (int a = 0; a < 6; ++a) acc[o++] = J[0][a] * r[0] + J[1][a] * r[1] + J[2][a] * r[2];
+        acc[o++] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
+      }
+      acc[o] = 1.0;
+    }
+  }
+  // fixed order: lane l takes l + 32, then + 16, ... inside its wave; then the waves 0..3 in turn
+#pragma unroll
+  for (int k = 0; k < MR_NSUM; ++k) {
+    double v = acc[k];
+    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
+    acc[k] = v;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < MR_NSUM; ++k) part[wave][k] = acc[k];
+  }
+  __syncthreads();
+  if (threadIdx.x < MR_NSUM) {
+    double v = part[0][threadIdx.x];
+    for (int q = 1; q < MR_BLOCK / 64; ++q) v = v + part[q][threadIdx.x];
+    partials[(size_t)blockIdx.x * MR_NSUM + threadIdx.x] = v;
+  }
+}
+
+struct MrSolve {
+  int iters, min_pairs;
+  double damping, tol_t, tol_r;
+};
+
+// Second stage, one wave: lane j sums partial j of the blocks in block order.  out29 (rslo_map_normal_eq) receives the
+// sums; with pose7 (rslo_map_register) lane 0 then takes the Gauss-Newton step of iteration `iter` and writes its info row.
+__global__ __launch_bounds__(64) void k_mapreg_finish(const double *__restrict__ partials, int n_blocks,
+                                                      double *__restrict__ out29, double *__restrict__ pose7, int iter,
+                                                      MrSolve sp, int32_t *__restrict__ flag, double *__restrict__ info) {
+  __shared__ double tot[MR_NSUM];
+  double *row = info ? info + (size_t)iter * 8 : nullptr;
+  if (pose7 && iter > 0 && *flag) {
+    if (threadIdx.x < 8) row[threadIdx.x] = threadIdx.x == 0 ? 3.0 : 0.0;
+    return;
+  }
+  if (threadIdx.x < MR_NSUM) {
+    double v = 0.0;
+    for (int b = 0; b < n_blocks; ++b) v = v + partials[(size_t)b * MR_NSUM + threadIdx.x];
+    tot[threadIdx.x] = v;
+    if (out29) out29[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (!pose7 || threadIdx.x != 0) return;
+  int status = 0;
+  double nt = 0.0, th = 0.0;
+  const double pairs = tot[28], cost = tot[27];
+  if (pairs < (double)sp.min_pairs) {
+    status = 1;
+  } else {
+    // M = H + damping * I = L L^T, row by row
+    double M[6][6], L[6][6], y[6], x[6];
+    int o = 0;
+    for (int a = 0; a < 6; ++a)
+      for (int b = a; b < 6; ++b) M[a][b] = M[b][a] = tot[o++];
+    for (int a = 0; a < 6; ++a) M[a][a] = M[a][a] + sp.damping;
+    for (int a = 0; a < 6 && !status; ++a) {
+      for (int b = 0; b <= a; ++b) {
+        double sum = M[a][b];
+        for (int k = 0; k < b; ++k) sum = sum - L[a][k] * L[b][k];
+        if (a == b) {
+          if (!(sum > 0.0 && sum < (double)__builtin_inff())) {
+            status = 2;
+            break;
+          }
+          L[a][a] = sqrt(sum);
+        } else {
+          L[a][b] = sum / L[b][b];
+        }
+      }
+    }
+    if (!status) {
+      for (int a = 0; a < 6; ++a) {      // L y = g
+        double sum = tot[21 + a];
+        for (int k = 0; k < a; ++k) sum = sum - L[a][k] * y[k];
+        y[a] = sum / L[a][a];
+      }
+      for (int a = 5; a >= 0; --a) {     // L^T x = y
+        double sum = y[a];
+        for (int k = a + 1; k < 6; ++k) sum = sum - L[k][a] * x[k];
+        x[a] = sum / L[a][a];
+      }
+      const double dt[3] = {-x[0], -x[1], -x[2]}, dr[3] = {-x[3], -x[4], -x[5]};
+      nt = sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);
+      th = sqrt(dr[0] * dr[0] + dr[1] * dr[1] + dr[2] * dr[2]);
+      if (!(nt < (double)__builtin_inff() && th < (double)__builtin_inff())) {
+        status = 2;      // an overflowed step is no step
+        nt = th = 0.0;
+      } else {
+        double dq[4];
+        if (th < 1e-12) {
+          dq[0] = 1.0;
+          for (int a = 0; a < 3; ++a) dq[1 + a] = dr[a] / 2.0;
+        } else {
+          const double f = sin(th / 2.0) / th;
+          dq[0] = cos(th / 2.0);
+          for (int a = 0; a < 3; ++a) dq[1 + a] = f * dr[a];
+        }
+        double t[3], q[4], b[3], c[3], vx[3], r[4];
+        for (int a = 0; a < 3; ++a) t[a] = pose7[a];
+        for (int a = 0; a < 4; ++a) q[a] = pose7[3 + a];
+        map_cross(dq + 1, t, b);
+        map_cross(dq + 1, b, c);
+        for (int a = 0; a < 3; ++a) pose7[a] = dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]);
+        map_cross(dq + 1, q + 1, vx);
+        r[0] = dq[0] * q[0] - (dq[1] * q[1] + dq[2] * q[2] + dq[3] * q[3]);
+        for (int a = 0; a < 3; ++a) r[1 + a] = dq[1 + a] * q[0] + q[1 + a] * dq[0] + vx[a];
+        const double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
+        for (int a = 0; a < 4; ++a) pose7[3 + a] = r[a] / nr;
+      }
+    }
+  }
+  *flag = (status == 0 && nt < sp.tol_t && th < sp.tol_r) ? 1 : 0;
+  row[0] = (double)status;
+  row[1] = pairs;
+  row[2] = cost;
+  row[3] = nt;
+  row[4] = th;
+  row[5] = row[6] = row[7] = 0.0;
+}
+
+extern "C" int rslo_map_params(const void *map, size_t map_bytes, double *params3_host, void *stream) {
+  RSLO_CHECK_ARG(map && mr_cap_max(map_bytes) > 0, "map_params: no map (map_bytes below rslo_map_bytes(1024))");
+  RSLO_CHECK_ARG(params3_host, "map_params: params3_host is null");
+  long long words[5];
+  RSLO_HIP(hipMemcpyAsync(words, map, sizeof(words), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  RSLO_HIP(hipStreamSynchronize((hipStream_t)stream));
+  RSLO_CHECK_ARG((map_u64)words[0] == MAP_MAGIC, "map_params: the allocation holds no map (never reset)");
+  for (int a = 0; a < 3; ++a) memcpy(&params3_host[a], &words[2 + a], sizeof(double));
+  return RSLO_OK;
+}
+
+static int mr_check(const char *name, const void *map, long long cap_max, double voxel, int stride, int N,
+                    const double *pose7, double max_dist) {
+  char msg[160];
+#define MR_ARG(cond, text)                         \
+  do {                                             \
+    if (!(cond)) {                                 \
+      snprintf(msg, sizeof(msg), "%s: " text, name); \
+      rslo_set_error("%s", msg);                   \
+      return RSLO_EINVAL;                          \
+    }                                              \
+  } while (0)
+  MR_ARG(map && cap_max > 0, "no map (map_bytes below rslo_map_bytes(1024))");
+  MR_ARG(N >= 0 && stride >= 3, "N < 0 or stride_floats < 3");
+  MR_ARG(pose7, "pose7 is null");
+  MR_ARG(voxel > 0.0 && voxel < (double)__builtin_inff(), "voxel_size must be positive and finite");
+  MR_ARG(max_dist > 0.0 && max_dist <= voxel, "need 0 < max_dist <= voxel_size (NaN is refused)");
+#undef MR_ARG
+  return RSLO_OK;
+}
+
+extern "C" int rslo_map_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                int stride_floats, int N, const double *pose7, double max_dist, int min_hits,
+                                int64_t *tags_out, double *d2_out, float *rows_out, void *stream) {
+  const long long cap_max = mr_cap_max(map_bytes);
+  const int rc = mr_check("map_nearest", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  if (N == 0) return RSLO_OK;
+  RSLO_CHECK_ARG(points && tags_out && d2_out, "map_nearest: null pointer");
+  hipLaunchKernelGGL(k_map_nearest, dim3((unsigned)rslo_cdiv(N, MR_BLOCK)), dim3(MR_BLOCK), 0, (hipStream_t)stream, map,
+                     cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, min_hits, (long long *)tags_out,
+                     d2_out, rows_out);
+  RSLO_CHECK_LAUNCH("map_nearest");
+  return RSLO_OK;
+}
+
+extern "C" size_t rslo_map_register_ws_bytes(int N) {
+  const size_t nb = N > 0 ? (size_t)rslo_cdiv(N, MR_BLOCK) : 1;
+  return MR_WS_HDR + (nb * MR_NSUM * sizeof(double) + 255) / 256 * 256;
+}
+
+// the launches of one evaluation of the normal equations (+ the step of iteration `iter` when pose_rw is given)
+static int mr_launch(const void *map, long long cap_max, double voxel, const float *points, int stride, int width, int N,
+                     const double *pose, int metric, double max_dist, int min_hits, double *out29, double *pose_rw,
+                     int iter, const MrSolve &sp, double *info, void *ws, hipStream_t s) {
+  int32_t *flag = (int32_t *)ws;
+  double *partials = (double *)((unsigned char *)ws + MR_WS_HDR);
+  const int nb = (int)rslo_cdiv(N, MR_BLOCK);
+  if (nb > 0)
+    hipLaunchKernelGGL(k_mapreg_accum, dim3((unsigned)nb), dim3(MR_BLOCK), 0, s, map, cap_max, voxel, points, stride, width,
+                       N, pose, metric, max_dist, min_hits, iter, (const int32_t *)flag, partials);
+  hipLaunchKernelGGL(k_mapreg_finish, dim3(1), dim3(64), 0, s, (const double *)partials, nb, out29, pose_rw, iter, sp, flag,
+                     info);
+  return RSLO_OK;
+}
+
+static int mr_check_sums(const char *name, const float *points, int stride, int width, int N, int metric, void *ws,
+                         size_t ws_bytes) {
+  if (!(metric == 0 || metric == 1) || width < 3 || (metric == 1 && (width < 7 || stride < 7))) {
+    rslo_set_error("%s: metric must be 0 (point) or 1 (plane); the plane metric reads normals at columns 4..6 "
+                   "(width and stride_floats >= 7)", name);
+    return RSLO_EINVAL;
+  }
+  if (!ws || ((uintptr_t)ws & 7) || (N > 0 && !points)) {
+    rslo_set_error("%s: null pointer, or a workspace that is not 8-byte aligned", name);
+    return RSLO_EINVAL;
+  }
+  if (ws_bytes < rslo_map_register_ws_bytes(N)) {
+    rslo_set_error("%s: workspace too small", name);
+    return RSLO_EWS;
+  }
+  return RSLO_OK;
+}
+
+extern "C" int rslo_map_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                  int stride_floats, int width, int N, const double *pose7, int metric, double max_dist,
+                                  int min_hits, double *out29, void *ws, size_t ws_bytes, void *stream) {
+  const long long cap_max = mr_cap_max(map_bytes);
+  int rc = mr_check("map_normal_eq", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(out29, "map_normal_eq: out29 is null");
+  rc = mr_check_sums("map_normal_eq", points, stride_floats, width, N, metric, ws, ws_bytes);
+  if (rc) return rc;
+  const MrSolve sp = {0, 0, 0.0, 0.0, 0.0};
+  mr_launch(map, cap_max, voxel_size, points, stride_floats, width, N, pose7, metric, max_dist, min_hits, out29, nullptr, 0,
+            sp, nullptr, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH("map_normal_eq");
+  return RSLO_OK;
+}
+
+extern "C" int rslo_map_register(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                 int stride_floats, int width, int N, double *pose7, int iters, int metric,
+                                 double max_dist, int min_hits, double damping, int min_pairs, double tol_t, double tol_r,
+                                 double *info, void *ws, size_t ws_bytes, void *stream) {
+  const long long cap_max = mr_cap_max(map_bytes);
+  int rc = mr_check("map_register", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(iters >= 1 && iters <= MR_MAX_ITERS, "map_register: iters must be in 1 .. 32");
+  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "map_register: tol_t and tol_r must be >= 0 (NaN is refused)");
+  RSLO_CHECK_ARG(info, "map_register: info is null");
+  rc = mr_check_sums("map_register", points, stride_floats, width, N, metric, ws, ws_bytes);
+  if (rc) return rc;
+  const MrSolve sp = {iters, min_pairs, damping, tol_t, tol_r};
+  for (int it = 0; it < iters; ++it)
+    mr_launch(map, cap_max, voxel_size, points, stride_floats, width, N, pose7, metric, max_dist, min_hits, nullptr, pose7,
+              it, sp, info, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH("map_register");
+  return RSLO_OK;
+}

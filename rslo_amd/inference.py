@@ -249,10 +249,19 @@ class OdometryRunner:
       thread may overwrite as soon as the event recorded by EncoderGraphRunner.run has passed.  The caller keeps the
       submitted tensor unmodified until run() of its handle has been consumed on the device.  reset() also resets the
       map (a new sequence has a new frame); its figures come from voxel_map.stats().  None (the default): no map.
+    * Refinement: refine=dict(iters=3, ...) (keyword arguments of VoxelMap.register except metric; needs voxel_map)
+      registers every scan against the map before inserting it (csrc/mapreg.hip).  The runner then keeps a SECOND chain
+      beside the open-loop one, driven by the same rslo_pose_chain outside the head graph: behind the head replay,
+      pose_chain(rel[n]) on it writes the prediction refined[n-1] o rel[n] into row n, voxel_map.register corrects that
+      row in place (metric "plane" for [P, >= 7] input, "point" for raw scans), the chain's state is set to the
+      corrected row so that the next scan composes onto it, and the scan is inserted under it.  trajectory() and
+      relative() stay the open-loop chain, bit for bit; refined_trajectory() is the second chain and refine_info() the
+      [n, iters, 8] info rows of register, both on the device.  A fixed number of launches per scan, no
+      synchronisation, no stream.  None (the default): today's behaviour to the bit.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
-                 normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None):
+                 normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -301,6 +310,22 @@ class OdometryRunner:
             if voxel_map.device != dev:
                 raise capi.RsloHipError("OdometryRunner: the voxel map lives on %s, the runner on %s" % (voxel_map.device, dev))
             voxel_map.reserve(int(point_capacity))      # run() must not allocate
+        self.refine = None
+        if refine is not None:
+            if voxel_map is None:
+                raise capi.RsloHipError("OdometryRunner: refine needs a voxel_map to register against")
+            refine = dict(refine)
+            unknown = set(refine) - {"iters", "max_dist", "min_hits", "damping", "min_pairs", "tol_t", "tol_r"}
+            if unknown:
+                raise capi.RsloHipError("OdometryRunner: refine takes the keyword arguments of VoxelMap.register except "
+                                        "metric (chosen by the input's width) and info; got %s" % sorted(unknown))
+            refine.setdefault("iters", 5)
+            self.refine = refine
+            self._state2 = torch.zeros((7,), dtype=torch.float64, device=dev)
+            self._count2 = torch.zeros((1,), dtype=torch.int32, device=dev)
+            self._rel2 = torch.zeros((self.capacity, 7), dtype=torch.float32, device=dev)
+            self._traj2 = torch.zeros((self.capacity, 7), dtype=torch.float64, device=dev)
+            self._info2 = torch.zeros((self.capacity, int(refine["iters"]), 8), dtype=torch.float64, device=dev)
         self.stats = {"scans": 0, "encoder_runs": 0, "head_replays": 0, "head_eager": 0, "captures": 0,
                       "weight_refreshes": 0}
 
@@ -338,6 +363,20 @@ class OdometryRunner:
         self._n = 0
         if self.voxel_map is not None:
             self.voxel_map.reset()
+        if self.refine is not None:
+            self._count2.zero_()
+
+    def refined_trajectory(self):
+        """[n, 7] fp64 device rows of the refined chain (refine=...): row i = register(refined[i-1] o rel[i])."""
+        if self.refine is None:
+            raise capi.RsloHipError("OdometryRunner.refined_trajectory: the runner was built without refine")
+        return self._traj2[:min(self._n, self.capacity)]
+
+    def refine_info(self):
+        """[n, iters, 8] fp64 device rows: VoxelMap.register's info of every scan."""
+        if self.refine is None:
+            raise capi.RsloHipError("OdometryRunner.refine_info: the runner was built without refine")
+        return self._info2[:min(self._n, self.capacity)]
 
     def trajectory(self):
         return self._traj[:min(self._n, self.capacity)]
@@ -397,7 +436,13 @@ class OdometryRunner:
             self._head_and_chain()
             self.stats["head_eager"] += 1
         n = self._n
-        if self.voxel_map is not None:      # behind the pose chain that wrote row n, on this stream
+        if self.refine is not None:         # the second chain: predict from the refined pose, register, compose onto the result
+            rel = self._rel[n]
+            capi.pose_chain(rel[:3], rel[3:], self._state2, self._count2, self._rel2, self._traj2)
+            self.voxel_map.register(handle.source, self._traj2[n], info=self._info2[n], **self.refine)
+            self._state2.copy_(self._traj2[n])
+            self.voxel_map.insert(handle.source, self._traj2[n])
+        elif self.voxel_map is not None:    # behind the pose chain that wrote row n, on this stream
             self.voxel_map.insert(handle.source, self._traj[n])
         self._n += 1
         self.stats["scans"] += 1

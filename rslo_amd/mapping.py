@@ -20,6 +20,27 @@ the same rules on host arrays and the arbiter of the tests, which compare bit fo
   * the device map probes at most 128 slots: a point that finds neither its cell nor an empty slot is dropped
     (dropped_full) -- a cell is stored completely or not at all.  VoxelMapRef has no capacity: it specifies a map that
     did not overflow.
+
+Scan-to-map registration (csrc/mapreg.hip; rules: include/rslo_hip.h "Scan-to-map registration") reads the map back, on
+both classes:
+
+    tags, d2 = vmap.nearest(scan, pose, max_dist=0.3)          # the exact nearest stored point within max_dist <= voxel_size
+    pose, info = vmap.register(scan, pose, iters=5)            # Gauss-Newton on the device, pose (a trajectory row) in place
+
+  * nearest: the candidates of a point are the stored cells c + {-1,0,1}^3 around its cell with hits >= min_hits;
+    d2 = |w - float64(row.xyz)|^2 summed left to right; the smallest d2 wins, then the smallest tag; accepted when
+    d2 < max_dist^2.  max_dist <= voxel_size makes the 27 cells sufficient, so this is the exact nearest stored point;
+  * normal_equations -> [29]: the upper triangle of H (21), g (6), cost, pairs of the matched points at a pose, for the
+    world-frame twist (dt, dtheta).  metric "plane": a point whose scan normal (columns 4..6) has n.n >= 0.25
+    contributes one row a = (n, w x n), r = n . (w - m), n = the normal rotated by the pose (held fixed over the
+    step); every other matched point -- and every point under metric "point" -- contributes the three rows of
+    J = [I | -[w]x] with residual w - m.  The fallback matters: the reader zeroes exactly vertical normals, and a
+    world whose ground is level would otherwise leave z, roll and pitch unobserved;
+  * register: per iteration M = H + damping * I by row-by-row Cholesky, delta = -M^-1 g, q' = normalize(dq (x) q),
+    t' = dt + rotate(dq, t); info rows {status, pairs, cost, |dt|, theta, 0, 0, 0}, status 0 step, 1 fewer than
+    min_pairs pairs, 2 not positive definite, 3 skipped after an iteration with |dt| < tol_t and theta < tol_r.
+The device sums run in a fixed order but not in numpy's: the sums agree within the bound of a reordered float64 sum,
+the matches and the pair count exactly.
 """
 import numpy as np
 
@@ -51,6 +72,92 @@ def _check_params(voxel_size, min_range, max_range):
     if not (0.0 <= min_range < max_range):
         raise ValueError("need 0 <= min_range < max_range")
     return voxel_size, min_range, max_range
+
+
+def _metric_of(metric, width):
+    """None: "plane" for a cloud that carries normals (>= 7 columns), else "point" """
+    if metric is None:
+        metric = "plane" if width >= 7 else "point"
+    if metric not in ("point", "plane"):
+        raise ValueError("metric must be \"point\" or \"plane\", got %r" % (metric,))
+    if metric == "plane" and width < 7:
+        raise ValueError("metric \"plane\" reads the normals at columns 4..6: the points have %d columns" % width)
+    return metric
+
+
+def _max_dist_of(max_dist, voxel_size):
+    md = voxel_size if max_dist is None else float(max_dist)
+    if not (0.0 < md <= voxel_size):
+        raise ValueError("need 0 < max_dist <= voxel_size = %g, got %r" % (voxel_size, max_dist))
+    return md
+
+
+def _check_register(iters, tol_t, tol_r):
+    if not 1 <= int(iters) <= 32:
+        raise ValueError("register: iters must be in 1 .. 32")
+    if not (float(tol_t) >= 0.0 and float(tol_r) >= 0.0):
+        raise ValueError("register: tol_t and tol_r must be >= 0")
+
+
+def _cross3(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def gauss_newton_step(sums, pose, damping=0.0):
+    """The step of register from the 28 sums (H upper triangle, g, cost) at pose [7]: -> (new pose [7], |dt|, theta), or
+    None when M = H + damping * I is not positive definite.  Scalar float64 in the order of the device's one thread."""
+    import math
+    f = [float(v) for v in sums]
+    M = [[0.0] * 6 for _ in range(6)]
+    o = 0
+    for a in range(6):
+        for b in range(a, 6):
+            M[a][b] = M[b][a] = f[o]
+            o += 1
+    for a in range(6):
+        M[a][a] = M[a][a] + float(damping)
+    L = [[0.0] * 6 for _ in range(6)]
+    for a in range(6):
+        for b in range(a + 1):
+            acc = M[a][b]
+            for k in range(b):
+                acc = acc - L[a][k] * L[b][k]
+            if a == b:
+                if not (0.0 < acc < float("inf")):
+                    return None
+                L[a][a] = math.sqrt(acc)
+            else:
+                L[a][b] = acc / L[b][b]
+    y, x = [0.0] * 6, [0.0] * 6
+    for a in range(6):
+        acc = f[21 + a]
+        for k in range(a):
+            acc = acc - L[a][k] * y[k]
+        y[a] = acc / L[a][a]
+    for a in range(5, -1, -1):
+        acc = y[a]
+        for k in range(a + 1, 6):
+            acc = acc - L[k][a] * x[k]
+        x[a] = acc / L[a][a]
+    dt, dr = [-x[0], -x[1], -x[2]], [-x[3], -x[4], -x[5]]
+    nt = math.sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2])
+    th = math.sqrt(dr[0] * dr[0] + dr[1] * dr[1] + dr[2] * dr[2])
+    if not (nt < float("inf") and th < float("inf")):
+        return None
+    if th < 1e-12:
+        dq = [1.0] + [v / 2.0 for v in dr]
+    else:
+        fac = math.sin(th / 2.0) / th
+        dq = [math.cos(th / 2.0)] + [fac * v for v in dr]
+    t, q = [float(v) for v in pose[:3]], [float(v) for v in pose[3:7]]
+    b = _cross3(dq[1:], t)
+    c = _cross3(dq[1:], b)
+    tn = [dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]) for a in range(3)]
+    vx = _cross3(dq[1:], q[1:])
+    r = [dq[0] * q[0] - (dq[1] * q[1] + dq[2] * q[2] + dq[3] * q[3])]
+    r += [dq[1 + a] * q[0] + q[1 + a] * dq[0] + vx[a] for a in range(3)]
+    nr = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3])
+    return np.array(tn + [v / nr for v in r], np.float64), nt, th
 
 
 class VoxelMapRef:
@@ -161,6 +268,129 @@ class VoxelMapRef:
             idx = idx[np.argsort(self.tags[idx], kind="stable")]
         return self.rows[idx], self.tags[idx], self.hits[idx]
 
+    def _match(self, points, pose, max_dist, min_hits):
+        """-> (world [P, 3] float64, index [P] into the cell arrays (-1: no match), d2 [P] (-1.0: no match))"""
+        md = _max_dist_of(max_dist, self.voxel_size)
+        status, key, w = self._cells(points, pose)
+        P = len(status)
+        best = np.full((P,), -1, np.int64)
+        bd2 = np.full((P,), np.inf, np.float64)
+        btag = np.full((P,), np.iinfo(np.int64).max, np.int64)
+        if len(self.keys):
+            ok = status == 0
+            c = [(key >> 42) & 0x1fffff, (key >> 21) & 0x1fffff, key & 0x1fffff]
+            last = len(self.keys) - 1
+            with np.errstate(all="ignore"):
+                for dx in (-1, 0, 1):
+                    for dy in (-1, 0, 1):
+                        for dz in (-1, 0, 1):
+                            x, y, z = c[0] + dx, c[1] + dy, c[2] + dz
+                            valid = ok & (x >= 1) & (x <= 0x1fffff) & (y >= 1) & (y <= 0x1fffff) & (z >= 1) & (z <= 0x1fffff)
+                            nk = (x << 42) | (y << 21) | z
+                            pos = np.minimum(np.searchsorted(self.keys, nk), last)
+                            hit = valid & (self.keys[pos] == nk) & (self.hits[pos] >= min_hits)
+                            m = self.rows[pos, :3].astype(np.float64)
+                            d = w - m
+                            d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+                            tag = self.tags[pos]
+                            better = hit & ((d2 < bd2) | ((d2 == bd2) & (tag < btag)))
+                            best[better], bd2[better], btag[better] = pos[better], d2[better], tag[better]
+        acc = (best >= 0) & (bd2 < md * md)
+        return w, np.where(acc, best, -1), np.where(acc, bd2, -1.0)
+
+    def nearest(self, points, pose=None, max_dist=None, min_hits=1, return_rows=False):
+        """(tags int64 [P], d2 float64 [P][, rows fp32 [P, 4]]) of the nearest stored point within max_dist (None:
+        voxel_size) of every point; -1 / -1.0 / zeros without a match or for a skipped point."""
+        _, idx, d2 = self._match(points, pose, max_dist, min_hits)
+        got = idx >= 0
+        tags = np.full((len(idx),), -1, np.int64)
+        tags[got] = self.tags[idx[got]]
+        if not return_rows:
+            return tags, d2
+        rows = np.zeros((len(idx), 4), np.float32)
+        rows[got] = self.rows[idx[got]]
+        return tags, d2, rows
+
+    def _pair_terms(self, points, pose, metric="plane", max_dist=None, min_hits=1, return_plane=False):
+        """The addends of normal_equations, one row per matched point in input order: [K, 28] = H upper triangle (21),
+        g (6), cost; return_plane=True adds the bool [K] of the rows that are plane terms."""
+        pts = np.asarray(points)
+        metric = _metric_of(metric, pts.shape[1] if pts.ndim == 2 else 0)
+        posev = np.asarray([0, 0, 0, 1, 0, 0, 0] if pose is None else pose, dtype=np.float64).reshape(7)
+        w, idx, _ = self._match(pts, posev, max_dist, min_hits)
+        sel = np.nonzero(idx >= 0)[0]
+        K = len(sel)
+        w = w[sel]
+        d = w - self.rows[idx[sel], :3].astype(np.float64)
+        J = np.zeros((K, 3, 6), np.float64)            # rows of the Jacobian; a plane term uses row 0 only
+        r = np.zeros((K, 3), np.float64)
+        for a in range(3):
+            J[:, a, a] = 1.0
+        J[:, 0, 4], J[:, 0, 5] = w[:, 2], -w[:, 1]
+        J[:, 1, 3], J[:, 1, 5] = -w[:, 2], w[:, 0]
+        J[:, 2, 3], J[:, 2, 4] = w[:, 1], -w[:, 0]
+        r[:] = d
+        plane = np.zeros((K,), bool)
+        if metric == "plane":
+            with np.errstate(all="ignore"):
+                ns = pts[sel, 4:7].astype(np.float64)
+                plane = (ns[:, 0] * ns[:, 0] + ns[:, 1] * ns[:, 1] + ns[:, 2] * ns[:, 2]) >= 0.25
+            ns, wp, dp = ns[plane], w[plane], d[plane]
+            qw, v = posev[3], posev[4:7]
+
+            def cross(a, b):
+                a = np.broadcast_to(a, b.shape)
+                return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
+                                 a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
+            b = cross(v, ns)
+            c = cross(v, b)
+            n = ns + (2.0 * b * qw + 2.0 * c)
+            J[plane] = 0.0
+            J[plane, 0, :3], J[plane, 0, 3:] = n, cross(wp, n)
+            r[plane] = 0.0
+            r[plane, 0] = n[:, 0] * dp[:, 0] + n[:, 1] * dp[:, 1] + n[:, 2] * dp[:, 2]
+        terms = np.zeros((K, 28), np.float64)
+        o = 0
+        for a in range(6):
+            for b in range(a, 6):
+                terms[:, o] = J[:, 0, a] * J[:, 0, b] + J[:, 1, a] * J[:, 1, b] + J[:, 2, a] * J[:, 2, b]
+                o += 1
+        for a in range(6):
+            terms[:, 21 + a] = J[:, 0, a] * r[:, 0] + J[:, 1, a] * r[:, 1] + J[:, 2, a] * r[:, 2]
+        terms[:, 27] = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2]
+        return (terms, plane) if return_plane else terms
+
+    def normal_equations(self, points, pose, metric="plane", max_dist=None, min_hits=1):
+        """[29] float64: the column sums of _pair_terms, then the number of pairs."""
+        terms = self._pair_terms(points, pose, metric, max_dist, min_hits)
+        return np.concatenate([terms.sum(axis=0), [float(len(terms))]])
+
+    def register(self, points, pose, iters=5, metric=None, max_dist=None, min_hits=1, damping=0.0, min_pairs=50,
+                 tol_t=0.0, tol_r=0.0):
+        """-> (pose [7] float64, info [iters, 8]); metric None: "plane" for points with normals, else "point"."""
+        _check_register(iters, tol_t, tol_r)
+        pts = np.asarray(points)
+        metric = _metric_of(metric, pts.shape[1] if pts.ndim == 2 else 0)
+        pose = np.array(pose, dtype=np.float64).reshape(7)
+        info = np.zeros((int(iters), 8), np.float64)
+        done = False
+        for it in range(int(iters)):
+            if done:
+                info[it, 0] = 3.0
+                continue
+            sums = self.normal_equations(pts, pose, metric, max_dist, min_hits)
+            info[it, 1], info[it, 2] = sums[28], sums[27]
+            if sums[28] < min_pairs:
+                info[it, 0] = 1.0
+                continue
+            step = gauss_newton_step(sums[:28], pose, damping)
+            if step is None:
+                info[it, 0] = 2.0
+                continue
+            pose, info[it, 3], info[it, 4] = step
+            done = bool(info[it, 3] < tol_t and info[it, 4] < tol_r)
+        return pose, info
+
     def stats(self):
         return dict(self.counters, dropped_full=0)
 
@@ -170,9 +400,9 @@ class VoxelMapRef:
 
 
 class VoxelMap:
-    """The device map: owns the table (one allocation of rslo_map_bytes(capacity) bytes) and an insert workspace that
-    grows only when a larger scan arrives.  insert / lookup / overlap enqueue on the current stream and read nothing on
-    the host; points() and stats() make one host read each."""
+    """The device map: owns the table (one allocation of rslo_map_bytes(capacity) bytes) and the insert and registration
+    workspaces, which grow only when a larger scan arrives.  insert / lookup / overlap / nearest / normal_equations /
+    register enqueue on the current stream and read nothing on the host; points() and stats() make one host read each."""
 
     def __init__(self, voxel_size=0.2, capacity=1 << 22, device="cuda", min_range=0.0, max_range=float("inf")):
         import torch
@@ -204,6 +434,7 @@ class VoxelMap:
         if n_points > self._ws_points:
             self._ws = torch.empty((capi.lib().rslo_map_insert_ws_bytes(int(n_points)),), dtype=torch.uint8,
                                    device=self.device)
+            self._reg_ws = capi.map_register_ws(int(n_points), self.device)      # normal_equations / register
             self._ws_points = int(n_points)
 
     def _pose(self, pose):
@@ -230,6 +461,38 @@ class VoxelMap:
         """Share of the scan's valid points that fall into occupied cells: a device scalar, no host read."""
         hits = self.lookup(points, pose)
         return (hits > 0).sum() / (hits >= 0).sum()
+
+    def nearest(self, points, pose=None, max_dist=None, min_hits=1, return_rows=False):
+        """(tags int64 [P], d2 float64 [P][, rows fp32 [P, 4]]) on the device: the exact nearest stored point within
+        max_dist (None: voxel_size; at most voxel_size) of every point; -1 / -1.0 / zeros without a match."""
+        from rslo_amd import capi
+        md = _max_dist_of(max_dist, self.voxel_size)
+        return capi.map_nearest(self._buf, points, self._pose(pose), self.voxel_size, md, min_hits,
+                                rows=True if return_rows else None)
+
+    def normal_equations(self, points, pose, metric="plane", max_dist=None, min_hits=1):
+        """float64 CUDA [29]: the upper triangle of H (21), g (6), cost, pairs of the matched points at pose."""
+        from rslo_amd import capi
+        md = _max_dist_of(max_dist, self.voxel_size)
+        self.reserve(points.shape[0])
+        return capi.map_normal_eq(self._buf, points, self._pose(pose), self.voxel_size, _metric_of(metric, points.shape[1]),
+                                  md, min_hits, ws=self._reg_ws)
+
+    def register(self, points, pose, iters=5, metric=None, max_dist=None, min_hits=1, damping=0.0, min_pairs=50,
+                 tol_t=0.0, tol_r=0.0, info=None):
+        """`iters` Gauss-Newton iterations of points (fp32 CUDA [P, F], read in place) against the map, on the device.
+        pose: a float64 CUDA [7] tensor (a trajectory row) is updated IN PLACE and returned; anything else is copied to
+        the device first.  -> (pose [7], info [iters, 8]) device tensors; info may be preallocated.  metric None:
+        "plane" for points with normals (F >= 7), else "point".  No host read, nothing allocated after a reserve()
+        when info is given."""
+        from rslo_amd import capi
+        _check_register(iters, tol_t, tol_r)
+        md = _max_dist_of(max_dist, self.voxel_size)
+        self.reserve(points.shape[0])
+        pose = self._identity.clone() if pose is None else self._pose(pose)
+        info = capi.map_register(self._buf, points, pose, self.voxel_size, iters, _metric_of(metric, points.shape[1]), md,
+                                 min_hits, damping, min_pairs, tol_t, tol_r, info=info, ws=self._reg_ws)
+        return pose, info
 
     def points(self, min_hits=1, center=None, radius=None, sort=True):
         """(rows [M, 4] fp32, tags [M] int64, hits [M] int32) of the cells with hits >= min_hits, and within radius of

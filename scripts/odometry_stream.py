@@ -6,6 +6,7 @@
     python scripts/odometry_stream.py --launches A_kernel_stats.csv B_kernel_stats.csv --scans-a 20 --scans-b 60
     python scripts/odometry_stream.py --raw --scans 200 --warmup 20 [--out profiles/odometry_stream_raw.json]
     python scripts/odometry_stream.py --map --scans 200 --warmup 20 [--map-out map.ply] [--out profiles/odometry_stream_map.json]
+    python scripts/odometry_stream.py --refine --scans 200 --warmup 20 [--refine-iters 3] [--out profiles/odometry_stream_refine.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -22,6 +23,11 @@ its scan under its absolute pose): ms per scan with the map beside the plain run
 under the same trajectory rows into a second map, device events over the timed scans), the map's counters, the mean
 overlap of each scan with the map before its insertion, and --map-out FILE.ply.  The same figures under the drive's own
 poses (synthetic.sequence_pose; --seed must be the drive's): with random weights the runner's trajectory is not a drive.
+--refine (implies --map): one more runner loop with refine=dict(iters=--refine-iters) (csrc/mapreg.hip: every scan is
+registered against the map before it is inserted), timed beside the --map loop of the same run, and a "registration
+alone" pass on the drive: the prediction of scan i is refined[i-1] o (true relative motion o a fixed seeded error of
+about 5 cm and 0.1 degrees); pose error against synthetic.sequence_pose before and after VoxelMap.register, pairs per
+scan and ms per register call from device events (--seed must be the drive's).
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -97,6 +103,8 @@ def main():
     ap.add_argument("--map-voxel", type=float, default=0.2)
     ap.add_argument("--map-capacity", type=int, default=1 << 22, help="slots of the map's table (a power of two)")
     ap.add_argument("--map-out", default=None, help="write the map as a binary PLY")
+    ap.add_argument("--refine", action="store_true", help="also run the runner with scan-to-map refinement (implies --map)")
+    ap.add_argument("--refine-iters", type=int, default=3, help="Gauss-Newton iterations per scan")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -104,6 +112,7 @@ def main():
     ap.add_argument("--save-scans", default=None, help="write the drive's scans to this .npz and stop")
     ap.add_argument("--load-scans", default=None, help="read the scans from a --save-scans file (profiled runs)")
     args = ap.parse_args()
+    args.map = args.map or args.refine
     if args.launches:
         res = launches(args.launches[0], args.launches[1], args.scans_a, args.scans_b)
         line = json.dumps(res)
@@ -293,11 +302,109 @@ def main():
         if args.map_out:
             vmap.save_ply(args.map_out)
             res["map_ply_bytes"] = os.path.getsize(args.map_out)
+    if args.refine:
+        res.update(refine_report(args, net, scans, timed, res["map_ms_per_scan"]))
     line = json.dumps(res)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def _rot(q, v):
+    import numpy as np
+    b = np.cross(q[1:], v)
+    return v + 2.0 * q[0] * b + 2.0 * np.cross(q[1:], b)
+
+
+def _compose(a, b):
+    """a o b of two poses [7] (t, q wxyz), float64"""
+    import numpy as np
+    qa, qb = a[3:], b[3:]
+    q = np.concatenate([[qa[0] * qb[0] - qa[1:] @ qb[1:]], qa[0] * qb[1:] + qb[0] * qa[1:] + np.cross(qa[1:], qb[1:])])
+    return np.concatenate([a[:3] + _rot(qa, b[:3]), q / np.linalg.norm(q)])
+
+
+def _inverse(a):
+    import numpy as np
+    qi = a[3:] * np.array([1.0, -1.0, -1.0, -1.0])
+    return np.concatenate([-_rot(qi, a[:3]), qi])
+
+
+def _pose_error(a, b):
+    """(metres, degrees) between two poses"""
+    import numpy as np
+    d = _compose(_inverse(b), a)
+    return float(np.linalg.norm(a[:3] - b[:3])), float(np.rad2deg(2.0 * np.arcsin(min(1.0, np.linalg.norm(d[4:])))))
+
+
+def refine_report(args, net, scans, timed, map_ms):
+    import numpy as np
+    import torch
+    from rslo_amd import inference, mapping, synthetic
+    dev = scans[0].device
+    W, N, K = args.warmup, args.scans, args.refine_iters
+    out = {"refine_iters": K}
+    rmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+    runner = inference.OdometryRunner(net, voxel_map=rmap, refine=dict(iters=K))
+    pend = {}
+
+    def run(rng):
+        rng = list(rng)
+        for k, i in enumerate(rng):
+            if i not in pend:
+                pend[i] = runner.submit(scans[i])
+            if k + 1 < len(rng) and rng[k + 1] not in pend:
+                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
+            runner.run(pend.pop(i))
+    out["refine_ms_per_scan"], out["refine_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+    out["refine_minus_map_ms_per_scan"] = round(out["refine_ms_per_scan"] - map_ms, 3)
+    info = runner.refine_info().cpu().numpy()
+    out["refine_runner_status_counts"] = [int((info[:, :, 0] == k).sum()) for k in range(4)]
+    out["refine_runner_mean_pairs"] = round(float(info[1:, 0, 1].mean()), 1)
+    out["refine_map_stats"] = rmap.stats()
+    runner.close()
+    # registration alone: the drive's own motion, disturbed by a fixed seeded error, corrected against the map so far
+    true = [synthetic.sequence_pose(i, args.seed) for i in range(W + N)]
+    rng = np.random.default_rng(777)
+    rmap.reset()
+    rmap.reserve(max(s.shape[0] for s in scans))
+    pose = torch.zeros((7,), dtype=torch.float64, device=dev)
+    refined = true[0].copy()
+    rmap.insert(scans[0], refined)
+    before, after, pairs, status, ms = [], [], [], [], []
+    for i in range(1, W + N):
+        axis = rng.normal(size=3)
+        ang = np.deg2rad(0.1) * rng.uniform(0.5, 1.5)
+        err = np.concatenate([0.05 * rng.normal(size=3) * [1.0, 1.0, 0.3], [np.cos(ang / 2)],
+                              np.sin(ang / 2) * axis / np.linalg.norm(axis)])
+        pred = _compose(refined, _compose(_compose(_inverse(true[i - 1]), true[i]), err))
+        pose.copy_(torch.from_numpy(pred))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        _, info = rmap.register(scans[i], pose, iters=K)
+        e1.record()
+        refined = pose.cpu().numpy()                # (a host read per scan: this pass times register alone)
+        rmap.insert(scans[i], pose)
+        before.append(_pose_error(pred, true[i]))
+        after.append(_pose_error(refined, true[i]))
+        info = info.cpu().numpy()
+        pairs.append(float(info[0, 1]))
+        status.append(info[:, 0].tolist())
+        if i >= W:
+            ms.append(e0.elapsed_time(e1))
+    before, after = np.array(before), np.array(after)
+    out["register_alone_ms_per_call"] = round(float(np.mean(ms)), 4)
+    out["register_alone_ms_per_iteration"] = round(float(np.mean(ms)) / K, 4)
+    out["register_alone_pairs_per_scan"] = round(float(np.mean(pairs)), 1)
+    out["register_alone_status_counts"] = [int((np.array(status) == k).sum()) for k in range(4)]
+    for name, e in (("before", before), ("after", after)):
+        out["register_alone_%s_trans_m_mean" % name] = round(float(e[:, 0].mean()), 5)
+        out["register_alone_%s_trans_m_max" % name] = round(float(e[:, 0].max()), 5)
+        out["register_alone_%s_rot_deg_mean" % name] = round(float(e[:, 1].mean()), 5)
+        out["register_alone_%s_rot_deg_max" % name] = round(float(e[:, 1].max()), 5)
+    out["register_alone_map_stats"] = rmap.stats()
+    return out
 
 
 if __name__ == "__main__":
