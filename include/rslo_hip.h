@@ -917,13 +917,15 @@ RSLO_API int rslo_voxel_downsample(const float *points, int stride_floats, const
  * Storage: ONE caller-owned device allocation of rslo_map_bytes(capacity) bytes, capacity = slots, a power of two in
  * 1024 .. 2^31:  header (256 bytes) | keys u64 [capacity] | tags u64 [capacity] | rows f32 [capacity, 4] | hits i32
  * [capacity].  The header as int64 words: [0] magic, [1] capacity, [2..4] voxel_size, min_range, max_range (doubles),
- * [RSLO_MAP_HDR_COUNTERS + 0..5] = n_scans, n_cells, n_points (accepted), dropped_invalid, dropped_range, dropped_full
+ * [RSLO_MAP_HDR_COUNTERS + 0..5] = n_scans, n_cells, n_points (accepted), dropped_invalid, dropped_range, dropped_full,
+ * [RSLO_MAP_HDR_PRUNE + 0..2] = n_prunes, n_evicted, n_lost ("Rolling local map" below)
  * -- integer atomics only, so they are deterministic.  Open addressing, linear probing from a 64-bit mix of the key.
  * Probing is BOUNDED: at most RSLO_MAP_MAX_PROBE slots are examined; a point that finds neither its key nor an empty
  * slot among them is dropped (dropped_full).  No loop depends on the table having room: a full map costs a counter,
- * never a hang.  Slots only fill and keys never move, so a cell is either stored with its complete, correct tag / hits /
- * row, or ALL of its points are dropped; which cells are dropped once dropped_full > 0 depends on the race for slots
- * and is unspecified, as is the slot a cell occupies (consumers sort by tag).  Everything else is fully specified.
+ * never a hang.  Between two prunes (below) slots only fill and keys never move, so a cell is either stored with its
+ * complete, correct tag / hits / row, or ALL of its points are dropped; which cells are dropped once dropped_full > 0
+ * depends on the race for slots and is unspecified, as is the slot a cell occupies (consumers sort by tag).  Everything
+ * else is fully specified.
  *   rslo_map_bytes   host only; 0 for a capacity that is not a power of two in 1024 .. 2^31.
  *   rslo_map_reset   empties the table and writes the header, in one kernel.  An argument error (capacity, map_bytes <
  *                    rslo_map_bytes(capacity), voxel_size, ranges) is RSLO_EINVAL and writes nothing.
@@ -941,9 +943,37 @@ RSLO_API int rslo_voxel_downsample(const float *points, int stride_floats, const
  *                    counts = {matching, written}: rows beyond max_rows are counted, not written (max_rows = 0: the
  *                    outputs may be NULL).
  * All of them: everything on `stream`, no host read, nothing allocated: capturable.
+ *
+ * Rolling local map (rslo_map_prune): the one call that removes cells.  S = n_scans at the time of the call.  A stored
+ * cell with row (x, y, z, .), tag and hits is KEPT iff both hold:
+ *   1. near:  center3 is NULL, or d2 < radius*radius with dx = double(x) - c[0], dy, dz likewise and
+ *      d2 = dx*dx + dy*dy + dz*dz summed left to right, IEEE double without contraction -- the test of rslo_map_export.
+ *      A comparison that is false evicts (a NaN centre coordinate, radius == 0); radius = +inf keeps every cell.
+ *   2. not sparse:  hits >= min_hits, or S - 1 - (tag >> 32) < grace (the cell was created fewer than `grace` scans
+ *      ago: it is still young).  min_hits >= 1, grace >= 0; with min_hits = 1 nothing is sparse.
+ * Every other cell is EVICTED: its key, tag, row and hits are gone, rslo_map_lookup reads 0 for it, rslo_map_nearest
+ * does not see it, and a later insert into it creates it afresh (new tag, hits counted from zero).  Kept cells keep
+ * tag, row and hits to the bit.  n_cells becomes the number of kept cells; n_scans, n_points and the dropped_*
+ * counters are cumulative and do not change.  Header words [RSLO_MAP_HDR_PRUNE + 0..2] = n_prunes (calls), n_evicted
+ * (cumulative), n_lost (below); rslo_map_reset zeroes them.
+ * The table is REBUILT, in place (`map` and its layout do not change): the kept records are staged in the caller-owned
+ * workspace of rslo_map_prune_ws_bytes(capacity) bytes (36 per slot plus a control block), every slot is emptied, and
+ * the records are inserted again under the same bounded probe.  A record that finds no empty slot among
+ * RSLO_MAP_MAX_PROBE is dropped whole and counted in n_lost (n_cells excludes it): this cannot happen while the
+ * longest run of occupied slots of the survivors, wrap-around included, is below RSLO_MAP_MAX_PROBE, whatever the
+ * thread order, because the occupied set of a linear-probing table does not depend on the insertion order; beyond
+ * that the surviving set is unspecified, like the stored set once dropped_full > 0.  A call that evicts nothing
+ * leaves every slot as it is, to the byte, and only counts itself in n_prunes.
+ *   rslo_map_prune_ws_bytes  host only; 0 for a capacity rslo_map_bytes refuses.
+ *   rslo_map_prune   center3: 3 DEVICE doubles (a row of rslo_pose_chain's traj will do: its first three are t), or
+ *                    NULL (rule 2 alone; the radius is then ignored).  radius < 0 or NaN with a centre,
+ *                    min_hits < 1, grace < 0, a null or misaligned (16 bytes) workspace: RSLO_EINVAL; ws_bytes below
+ *                    rslo_map_prune_ws_bytes of the capacity map_bytes can hold: RSLO_EWS.  Neither writes anything.
+ *                    Five launches whatever the data; no host read, nothing allocated: capturable.
  * ------------------------------------------------------------------------------------ */
 #define RSLO_MAP_MAX_PROBE 128
 #define RSLO_MAP_HDR_COUNTERS 8
+#define RSLO_MAP_HDR_PRUNE 5
 RSLO_API size_t rslo_map_bytes(int64_t capacity);
 RSLO_API int rslo_map_reset(void *map, size_t map_bytes, int64_t capacity, double voxel_size, double min_range,
                             double max_range, void *stream);
@@ -956,6 +986,9 @@ RSLO_API int rslo_map_lookup(const void *map, size_t map_bytes, const float *poi
 RSLO_API int rslo_map_export(const void *map, size_t map_bytes, int min_hits, const double *center3 /*or NULL*/,
                              double radius, float *rows /*[max_rows,4]*/, uint64_t *tags /*[max_rows]*/,
                              int32_t *hits /*[max_rows]*/, int64_t max_rows, int64_t *counts /*[2]*/, void *stream);
+RSLO_API size_t rslo_map_prune_ws_bytes(int64_t capacity);
+RSLO_API int rslo_map_prune(void *map, size_t map_bytes, const double *center3 /*device, or NULL*/, double radius,
+                            int min_hits, int grace, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Scan-to-map registration (csrc/mapreg.hip): the world voxel map as a registration target.  Read-only on the map;

@@ -196,6 +196,8 @@ SIGNATURES = {
     "rslo_map_insert": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "rslo_map_lookup": (C.c_int, [_vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "rslo_map_export": (C.c_int, [_vp, _sz, _i, _vp, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "rslo_map_prune_ws_bytes": (_sz, [_i64]),
+    "rslo_map_prune": (C.c_int, [_vp, _sz, _vp, C.c_double, _i, _i, _vp, _sz, _vp]),
     "rslo_map_params": (C.c_int, [_vp, _sz, _vp, _vp]),
     "rslo_map_nearest": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "rslo_map_register_ws_bytes": (_sz, [_i]),
@@ -1166,6 +1168,32 @@ def map_export(buf, min_hits=1, center=None, radius=0.0, rows=None, tags=None, h
                                _ptr(hits, torch.int32, "hits") if R else None, R,
                                _ptr(counts, torch.int64, "counts"), _stream()), "rslo_map_export")
     return counts
+
+
+MAP_HDR_PRUNE = 5         # first int64 word of n_prunes, n_evicted, n_lost in a map's header
+MAP_PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
+
+
+def map_prune_ws(capacity, device):
+    """a workspace for map_prune on a map of `capacity` slots: rslo_map_prune_ws_bytes(capacity) bytes"""
+    nbytes = int(lib().rslo_map_prune_ws_bytes(int(capacity)))
+    if nbytes == 0:
+        raise RsloHipError("map_prune_ws: capacity must be a power of two >= 1024, got %r" % (capacity,))
+    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+
+
+def map_prune(buf, ws, center=None, radius=0.0, min_hits=1, grace=0):
+    """rslo_map_prune on the current stream: evict the cells that are not within radius of center (None: no such test;
+    else float64 CUDA, contiguous, >= 3 elements, read in place: a [7] trajectory row will do) or that have fewer than
+    min_hits hits and are at least `grace` scans old, by rebuilding the table through ws (map_prune_ws).  No host read."""
+    ptr, nbytes = _map_buf(buf)
+    if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64
+                                   and center.numel() >= 3 and center.is_contiguous()):
+        raise RsloHipError("map_prune: center must be >= 3 contiguous float64 values on the GPU")
+    if not (torch.is_tensor(ws) and ws.is_cuda and ws.is_contiguous()):
+        raise RsloHipError("map_prune: ws must be a contiguous CUDA tensor (map_prune_ws)")
+    _chk(lib().rslo_map_prune(ptr, nbytes, None if center is None else center.data_ptr(), float(radius), int(min_hits),
+                              int(grace), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_map_prune")
 
 
 # scan-to-map registration (csrc/mapreg.hip; rules: include/rslo_hip.h "Scan-to-map registration")

@@ -4,14 +4,21 @@
 //
 // One caller-owned allocation: header (256 bytes) | keys u64 [cap] | tags u64 [cap] | rows f32 [cap, 4] | hits i32 [cap].
 // Open addressing, linear probing from a 64-bit mix of the key, at most RSLO_MAP_MAX_PROBE slots examined: no loop here
-// depends on the table having room.  Slots only fill and keys never move.
+// depends on the table having room.  Between two prunes slots only fill and keys never move; rslo_map_prune (below)
+// is the one call that removes cells, and it does so by REBUILDING the table in launches of its own.
 //
 // Visibility (eight XCDs with separate L2s): inside the insert kernel every decision rests on the return value of an
 // atomic (atomicCAS on the key, atomicMin on the tag, atomicAdd on the hits).  The non-temporal pre-reads only skip an
-// atomic that cannot change anything: a key never changes once set, so a stale read can only show "empty" (then the
-// CAS decides); a tag only decreases, so a stale read can only be too large (then the atomicMin is issued needlessly).
-// The row of a new cell is written by the owner of its tag in the NEXT kernel of the call (slot kept in the workspace),
-// the scan counter is bumped by a third kernel after every reader of it has run.
+// atomic that cannot change anything: inside that kernel a key never changes once set, so a stale read can only show
+// "empty" (then the CAS decides); a tag only decreases, so a stale read can only be too large (then the atomicMin is
+// issued needlessly).  The row of a new cell is written by the owner of its tag in the NEXT kernel of the call (slot
+// kept in the workspace), the scan counter is bumped by a third kernel after every reader of it has run.
+// Keys DO change in a prune, but only in prune's own launches, each of which is a kernel boundary away from every other
+// user of the table: one launch reads the table and stages the kept records (the cursor is an atomic whose return value
+// is the record's place), the next empties every slot, the next re-inserts the staged records -- there, again, a key
+// only goes from empty to set, by atomicCAS, and the CAS winner alone writes tag / row / hits of its slot -- and the
+// last one writes the header.  Nothing here communicates across workgroups except through atomics and kernel
+// boundaries.
 #include "rslo_common.h"
 #include "map_table.h"
 
@@ -41,7 +48,7 @@ __global__ __launch_bounds__(256) void k_map_reset(void *map, long long cap, dou
     h->voxel = voxel;
     h->min_range = min_range;
     h->max_range = max_range;
-    h->pad_[0] = h->pad_[1] = h->pad_[2] = 0;
+    h->n_prunes = h->n_evicted = h->n_lost = 0;
     h->n_scans = h->n_cells = h->n_points = h->dropped_invalid = h->dropped_range = h->dropped_full = 0;
   }
   for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
@@ -184,6 +191,134 @@ __global__ __launch_bounds__(256) void k_map_export(void *map, long long cap_max
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// rslo_map_prune: evict far and sparse cells by rebuilding the table (rules: include/rslo_hip.h "Rolling local map").
+// Workspace: control block (256 bytes, zeroed by the first, one-thread launch) | staged keys u64 [cap] |
+// tags u64 [cap] | rows f32 [cap, 4] | hits i32 [cap] -- the map's own section layout.
+// ---------------------------------------------------------------------------------------------------------------------
+#define PRUNE_CTL_BYTES 256
+struct PruneCtl {
+  map_u64 kept, evicted, lost;
+};
+
+struct PruneStage {
+  PruneCtl *ctl;
+  map_u64 *keys, *tags;
+  float4 *rows;
+  int32_t *hits;
+};
+
+__device__ __forceinline__ PruneStage prune_stage(void *ws, long long cap) {
+  unsigned char *p = (unsigned char *)ws + PRUNE_CTL_BYTES;
+  PruneStage st;
+  st.ctl = (PruneCtl *)ws;
+  st.keys = (map_u64 *)p;
+  st.tags = (map_u64 *)(p + (size_t)cap * 8);
+  st.rows = (float4 *)(p + (size_t)cap * 16);
+  st.hits = (int32_t *)(p + (size_t)cap * 32);
+  return st;
+}
+
+// the control block starts every call at zero
+__global__ void k_map_prune_begin(void *ws) {
+  if (threadIdx.x == 0) {
+    PruneCtl *ctl = (PruneCtl *)ws;
+    ctl->kept = ctl->evicted = ctl->lost = 0;
+  }
+}
+
+// pass 1: keep or evict every stored cell; the kept records go to the staging area through one cursor
+__global__ __launch_bounds__(256) void k_map_prune_scan(void *map, long long cap_max, const double *__restrict__ center,
+                                                        double radius, int min_hits, int grace, void *ws) {
+  MapView m;
+  if (!map_view(map, cap_max, m)) return;
+  const long long cap = m.hdr->capacity;
+  const PruneStage st = prune_stage(ws, cap);
+  const long long last_scan = (long long)m.hdr->n_scans - 1;
+  double c[3] = {0.0, 0.0, 0.0};
+  if (center) c[0] = center[0], c[1] = center[1], c[2] = center[2];
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    const map_u64 key = m.keys[s];
+    if (key == MAP_KEY_NONE) continue;
+    const int32_t h = m.hits[s];
+    const map_u64 tag = m.tags[s];
+    const float4 r = *(const float4 *)(m.rows + (size_t)s * 4);
+    bool keep = h >= min_hits || last_scan - (long long)(tag >> 32) < (long long)grace;
+    if (center) {      // the test of k_map_export, character for character: a comparison that is false evicts
+      const double dx = (double)r.x - c[0], dy = (double)r.y - c[1], dz = (double)r.z - c[2];
+      if (!(dx * dx + dy * dy + dz * dz < radius * radius)) keep = false;
+    }
+    // both adds to ONE address each, the first by every lane of an occupied slot (see k_map_insert): one add per wave
+    atomicAdd(&st.ctl->evicted, (map_u64)(!keep));
+    if (keep) {
+      const map_u64 o = atomicAdd(&st.ctl->kept, (map_u64)1);
+      if (o < (map_u64)cap) {      // always: one record per slot at most, and the cursor starts at 0
+        st.keys[o] = key;
+        st.tags[o] = tag;
+        st.rows[o] = r;
+        st.hits[o] = h;
+      }
+    }
+  }
+}
+
+// pass 2: the state k_map_reset leaves in the sections.  Nothing evicted: the table stays as it is, to the byte.
+__global__ __launch_bounds__(256) void k_map_prune_clear(void *map, long long cap_max, const void *ws) {
+  MapView m;
+  if (!map_view(map, cap_max, m)) return;
+  if (((const PruneCtl *)ws)->evicted == 0) return;
+  const long long cap = m.hdr->capacity;
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    m.keys[s] = MAP_KEY_NONE;
+    m.tags[s] = MAP_KEY_NONE;
+    *(float4 *)(m.rows + (size_t)s * 4) = make_float4(0.f, 0.f, 0.f, 0.f);
+    m.hits[s] = 0;
+  }
+}
+
+// pass 3: the staged keys are distinct, so whoever wins the CAS on a slot owns it and writes the rest with plain
+// stores; the kernel boundary publishes them.  The same bounded probe as the insert: a record without a slot is lost whole.
+__global__ __launch_bounds__(256) void k_map_prune_reinsert(void *map, long long cap_max, void *ws) {
+  MapView m;
+  if (!map_view(map, cap_max, m)) return;
+  const long long cap = m.hdr->capacity;
+  const PruneStage st = prune_stage(ws, cap);
+  if (st.ctl->evicted == 0) return;
+  const long long n = (long long)st.ctl->kept < cap ? (long long)st.ctl->kept : cap;
+  const map_u64 mask = (map_u64)cap - 1;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const map_u64 key = st.keys[i];
+    map_u64 s = map_mix(key) & mask;
+    bool found = false;
+    for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
+      // a stale read can only show "empty": in this launch a key goes from empty to set and never back
+      if (__builtin_nontemporal_load(&m.keys[s]) == MAP_KEY_NONE &&
+          atomicCAS(&m.keys[s], MAP_KEY_NONE, key) == MAP_KEY_NONE) {
+        found = true;
+        break;
+      }
+      s = (s + 1) & mask;
+    }
+    if (found) {
+      m.tags[s] = st.tags[i];
+      *(float4 *)(m.rows + (size_t)s * 4) = st.rows[i];
+      m.hits[s] = st.hits[i];
+    }
+    atomicAdd(&st.ctl->lost, (map_u64)(!found));
+  }
+}
+
+__global__ void k_map_prune_done(void *map, long long cap_max, const void *ws) {
+  MapView m;
+  if (threadIdx.x != 0 || !map_view(map, cap_max, m)) return;
+  const PruneCtl *ctl = (const PruneCtl *)ws;
+  m.hdr->n_prunes = m.hdr->n_prunes + 1;
+  if (ctl->evicted == 0) return;
+  m.hdr->n_cells = ctl->kept - ctl->lost;
+  m.hdr->n_evicted = m.hdr->n_evicted + ctl->evicted;
+  m.hdr->n_lost = m.hdr->n_lost + ctl->lost;
+}
+
 extern "C" size_t rslo_map_bytes(int64_t capacity) {
   if (capacity < MAP_MIN_CAP || capacity > ((int64_t)1 << 31) || (capacity & (capacity - 1))) return 0;
   return (size_t)MAP_HDR_BYTES + (size_t)MAP_SLOT_BYTES * (size_t)capacity;
@@ -260,5 +395,32 @@ extern "C" int rslo_map_export(const void *map, size_t map_bytes, int min_hits, 
   hipLaunchKernelGGL(k_map_export, dim3(nb), dim3(256), 0, s, (void *)map, cap_max, min_hits, center3, radius, rows,
                      (map_u64 *)tags, hits, (long long)max_rows, (map_u64 *)counts);
   RSLO_CHECK_LAUNCH("map_export");
+  return RSLO_OK;
+}
+
+extern "C" size_t rslo_map_prune_ws_bytes(int64_t capacity) {
+  if (rslo_map_bytes(capacity) == 0) return 0;
+  return (size_t)PRUNE_CTL_BYTES + (size_t)MAP_SLOT_BYTES * (size_t)capacity;
+}
+
+extern "C" int rslo_map_prune(void *map, size_t map_bytes, const double *center3, double radius, int min_hits, int grace,
+                              void *ws, size_t ws_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = map_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "map_prune: no map (map_bytes below rslo_map_bytes(1024))");
+  RSLO_CHECK_ARG(!center3 || radius >= 0.0, "map_prune: radius must be >= 0 (NaN is refused)");
+  RSLO_CHECK_ARG(min_hits >= 1 && grace >= 0, "map_prune: need min_hits >= 1 and grace >= 0");
+  RSLO_CHECK_ARG(ws && ((uintptr_t)ws & 15) == 0, "map_prune: the workspace is null or not 16-byte aligned");
+  if (ws_bytes < rslo_map_prune_ws_bytes(cap_max)) {      // the header's capacity is at most cap_max
+    rslo_set_error("map_prune: workspace too small");
+    return RSLO_EWS;
+  }
+  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  hipLaunchKernelGGL(k_map_prune_begin, dim3(1), dim3(64), 0, s, ws);
+  hipLaunchKernelGGL(k_map_prune_scan, dim3(nb), dim3(256), 0, s, map, cap_max, center3, radius, min_hits, grace, ws);
+  hipLaunchKernelGGL(k_map_prune_clear, dim3(nb), dim3(256), 0, s, map, cap_max, (const void *)ws);
+  hipLaunchKernelGGL(k_map_prune_reinsert, dim3(nb), dim3(256), 0, s, map, cap_max, ws);
+  hipLaunchKernelGGL(k_map_prune_done, dim3(1), dim3(64), 0, s, map, cap_max, (const void *)ws);
+  RSLO_CHECK_LAUNCH("map_prune");
   return RSLO_OK;
 }

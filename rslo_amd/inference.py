@@ -258,10 +258,16 @@ class OdometryRunner:
       relative() stay the open-loop chain, bit for bit; refined_trajectory() is the second chain and refine_info() the
       [n, iters, 8] info rows of register, both on the device.  A fixed number of launches per scan, no
       synchronisation, no stream.  None (the default): today's behaviour to the bit.
+    * Rolling local map: local_map=dict(radius=R, every=K, min_hits=1, grace=0) (needs voxel_map) keeps the map near the
+      sensor: behind the insert of scan n (counted from 0 since reset()), when (n + 1) % K == 0, run() calls
+      voxel_map.prune(center=row n of the chain that fed the insert, radius=R, min_hits=, grace=) -- the refined chain
+      with refine, else the open-loop one (VoxelMap.prune; include/rslo_hip.h "Rolling local map").  The decision is
+      the host's own scan count: no device read.  The workspace (about one more table) is reserved here, so run()
+      allocates nothing.  trajectory() / relative() are untouched.  None (the default): the map only grows.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
-                 normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None):
+                 normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -326,6 +332,27 @@ class OdometryRunner:
             self._rel2 = torch.zeros((self.capacity, 7), dtype=torch.float32, device=dev)
             self._traj2 = torch.zeros((self.capacity, 7), dtype=torch.float64, device=dev)
             self._info2 = torch.zeros((self.capacity, int(refine["iters"]), 8), dtype=torch.float64, device=dev)
+        self.local_map = None
+        if local_map is not None:
+            if voxel_map is None:
+                raise capi.RsloHipError("OdometryRunner: local_map needs a voxel_map to prune")
+            local_map = dict(local_map)
+            unknown = set(local_map) - {"radius", "every", "min_hits", "grace"}
+            if unknown:
+                raise capi.RsloHipError("OdometryRunner: local_map takes radius, every, min_hits and grace; got %s"
+                                        % sorted(unknown))
+            if "radius" not in local_map:
+                raise capi.RsloHipError("OdometryRunner: local_map needs a radius")
+            every = local_map.get("every", 1)
+            if int(every) != every or every < 1:
+                raise capi.RsloHipError("OdometryRunner: local_map every must be an integer >= 1, got %r" % (every,))
+            from rslo_amd import mapping
+            radius = mapping.check_prune(None, local_map["radius"], local_map.get("min_hits", 1), local_map.get("grace", 0),
+                                         has_center=True)
+            local_map = dict(radius=radius, every=int(every), min_hits=int(local_map.get("min_hits", 1)),
+                             grace=int(local_map.get("grace", 0)))
+            self.local_map = local_map
+            voxel_map.reserve_prune()                   # run() must not allocate
         self.stats = {"scans": 0, "encoder_runs": 0, "head_replays": 0, "head_eager": 0, "captures": 0,
                       "weight_refreshes": 0}
 
@@ -444,6 +471,10 @@ class OdometryRunner:
             self.voxel_map.insert(handle.source, self._traj2[n])
         elif self.voxel_map is not None:    # behind the pose chain that wrote row n, on this stream
             self.voxel_map.insert(handle.source, self._traj[n])
+        if self.local_map is not None and (n + 1) % self.local_map["every"] == 0:
+            lm = self.local_map
+            self.voxel_map.prune((self._traj if self.refine is None else self._traj2)[n], lm["radius"], lm["min_hits"],
+                                 lm["grace"])
         self._n += 1
         self.stats["scans"] += 1
         return self._rel[n], self._traj[n]

@@ -21,6 +21,27 @@ the same rules on host arrays and the arbiter of the tests, which compare bit fo
     (dropped_full) -- a cell is stored completely or not at all.  VoxelMapRef has no capacity: it specifies a map that
     did not overflow.
 
+Rolling local map (rules: include/rslo_hip.h "Rolling local map"), on both classes:
+
+    vmap.prune(center=pose, radius=100.0)                      # forget what is not within 100 m of the sensor
+    vmap.prune(min_hits=2, grace=5)                            # forget cells hit once that are at least 5 scans old
+    runner = inference.OdometryRunner(net, voxel_map=vmap, local_map=dict(radius=100.0, every=10))
+
+  * prune(center=None, radius=None, min_hits=1, grace=0), S = n_scans at the time of the call.  A stored cell with row
+    (x, y, z, .), tag and hits is KEPT iff both hold.  Near: center is None, or d2 < radius*radius with
+    dx = float64(x) - c[0], dy, dz likewise, d2 = dx*dx + dy*dy + dz*dz summed left to right -- the test of
+    points(center=, radius=); a comparison that is false evicts (a NaN centre coordinate, radius == 0), radius = +inf
+    keeps every cell; radius < 0 or NaN (here even without a center, where rslo_map_prune ignores the radius), or a
+    center without a radius, is a ValueError and writes nothing.  Not sparse:
+    hits >= min_hits, or S - 1 - (tag >> 32) < grace (created fewer than `grace` scans ago: still young);
+    min_hits >= 1 and grace >= 0 are integers, with min_hits = 1 nothing is sparse;
+  * every other cell is EVICTED: key, tag, row and hits are gone, lookup reads 0, nearest does not see it, a later
+    insert creates it afresh (new tag, hits from zero).  Kept cells keep tag, row and hits to the bit.  n_cells becomes
+    the number of kept cells, the other five counters of stats() are cumulative and do not change;
+  * prune_stats() -> {n_prunes, n_evicted, n_lost}: calls, cells evicted so far, and -- device map only -- kept cells
+    that found no slot within 128 probes when the table was rebuilt (dropped whole; impossible while the survivors'
+    longest run of occupied slots is below 128; VoxelMapRef has no capacity: always 0).  reset() zeroes them.
+
 Scan-to-map registration (csrc/mapreg.hip; rules: include/rslo_hip.h "Scan-to-map registration") reads the map back, on
 both classes:
 
@@ -45,6 +66,7 @@ the matches and the pair count exactly.
 import numpy as np
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full")
+PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
 _MAXC = 1 << 20
 
 
@@ -90,6 +112,23 @@ def _max_dist_of(max_dist, voxel_size):
     if not (0.0 < md <= voxel_size):
         raise ValueError("need 0 < max_dist <= voxel_size = %g, got %r" % (voxel_size, max_dist))
     return md
+
+
+def check_prune(center, radius, min_hits, grace, has_center=None):
+    """The argument errors of prune (ValueError), raised before anything is written; -> radius as a float (0.0 when
+    None).  has_center: whether a centre will be given, for callers that validate before they have one (default:
+    center is not None).  Stricter than rslo_map_prune in one point: a negative or NaN radius is refused without a
+    centre too, where the C call ignores the radius."""
+    if has_center is None:
+        has_center = center is not None
+    if has_center and radius is None:
+        raise ValueError("prune: a center needs a radius")
+    r = 0.0 if radius is None else float(radius)
+    if not r >= 0.0:
+        raise ValueError("prune: radius must be >= 0 (NaN is refused), got %r" % (radius,))
+    if int(min_hits) != min_hits or int(grace) != grace or min_hits < 1 or grace < 0:
+        raise ValueError("prune: min_hits >= 1 and grace >= 0 must be integers, got %r and %r" % (min_hits, grace))
+    return r
 
 
 def _check_register(iters, tol_t, tol_r):
@@ -174,6 +213,7 @@ class VoxelMapRef:
         self.hits = np.zeros((0,), np.int32)
         self.rows = np.zeros((0, 4), np.float32)
         self.counters = dict.fromkeys(COUNTERS, 0)
+        self.prune_counters = dict.fromkeys(PRUNE_COUNTERS, 0)
 
     def _cells(self, points, pose):
         """-> (status [P]: 0 accepted, 1 skipped, 2 out of range; key [P] int64; world [P, 3] float64)"""
@@ -267,6 +307,24 @@ class VoxelMapRef:
         if sort:
             idx = idx[np.argsort(self.tags[idx], kind="stable")]
         return self.rows[idx], self.tags[idx], self.hits[idx]
+
+    def prune(self, center=None, radius=None, min_hits=1, grace=0):
+        """Evict the cells that are not near or that are sparse (module docstring): the sorted arrays are filtered."""
+        r = check_prune(center, radius, min_hits, grace)
+        young = (self.counters["n_scans"] - 1 - (self.tags >> 32)) < int(grace)
+        keep = (self.hits >= int(min_hits)) | young
+        if center is not None:
+            c = np.asarray(center, dtype=np.float64).reshape(-1)[:3]
+            with np.errstate(all="ignore"):
+                d = self.rows[:, :3].astype(np.float64) - c[None, :]
+                keep &= (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]) < r * r
+        self.prune_counters["n_prunes"] += 1
+        self.prune_counters["n_evicted"] += int((~keep).sum())
+        self.keys, self.tags, self.hits, self.rows = self.keys[keep], self.tags[keep], self.hits[keep], self.rows[keep]
+        self.counters["n_cells"] = len(self.keys)
+
+    def prune_stats(self):
+        return dict(self.prune_counters)
 
     def _match(self, points, pose, max_dist, min_hits):
         """-> (world [P, 3] float64, index [P] into the cell arrays (-1: no match), d2 [P] (-1.0: no match))"""
@@ -401,8 +459,10 @@ class VoxelMapRef:
 
 class VoxelMap:
     """The device map: owns the table (one allocation of rslo_map_bytes(capacity) bytes) and the insert and registration
-    workspaces, which grow only when a larger scan arrives.  insert / lookup / overlap / nearest / normal_equations /
-    register enqueue on the current stream and read nothing on the host; points() and stats() make one host read each."""
+    workspaces, which grow only when a larger scan arrives, and prune's workspace (about one more table), allocated by
+    the first prune() or by reserve_prune().  insert / lookup / overlap / nearest / normal_equations / register / prune
+    enqueue on the current stream and read nothing on the host; points(), stats() and prune_stats() make one host read
+    each."""
 
     def __init__(self, voxel_size=0.2, capacity=1 << 22, device="cuda", min_range=0.0, max_range=float("inf")):
         import torch
@@ -418,6 +478,7 @@ class VoxelMap:
         self._buf = torch.empty((nbytes // 8,), dtype=torch.int64, device=self.device)
         self._ws = None
         self._ws_points = -1
+        self._prune_ws = None
         self._identity = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float64, device=self.device)
         self.reserve(0)
         self.reset()
@@ -493,6 +554,31 @@ class VoxelMap:
         info = capi.map_register(self._buf, points, pose, self.voxel_size, iters, _metric_of(metric, points.shape[1]), md,
                                  min_hits, damping, min_pairs, tol_t, tol_r, info=info, ws=self._reg_ws)
         return pose, info
+
+    def reserve_prune(self):
+        """Allocate prune's workspace (about one more table) now, so that a later prune() allocates nothing."""
+        from rslo_amd import capi
+        if self._prune_ws is None:
+            self._prune_ws = capi.map_prune_ws(self.capacity, self.device)
+
+    def prune(self, center=None, radius=None, min_hits=1, grace=0):
+        """Evict the cells that are not within radius of center, or that have fewer than min_hits hits and were created
+        at least `grace` scans ago (module docstring).  center: None, a sequence, or a float64 CUDA tensor of >= 3
+        elements that is read in place (a [7] trajectory row).  Enqueued on the current stream; no host read, and
+        nothing allocated after reserve_prune() when center is a device tensor (or None): capturable."""
+        import torch
+        from rslo_amd import capi
+        r = check_prune(center, radius, min_hits, grace)
+        if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
+            center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(-1)[:3].copy()).to(self.device)
+        self.reserve_prune()
+        capi.map_prune(self._buf, self._prune_ws, center, r, int(min_hits), int(grace))
+
+    def prune_stats(self):
+        """{n_prunes, n_evicted, n_lost} of the map's header (one host read)."""
+        from rslo_amd import capi
+        vals = self._buf[capi.MAP_HDR_PRUNE:capi.MAP_HDR_PRUNE + len(PRUNE_COUNTERS)].tolist()
+        return dict(zip(PRUNE_COUNTERS, (int(v) for v in vals)))
 
     def points(self, min_hits=1, center=None, radius=None, sort=True):
         """(rows [M, 4] fp32, tags [M] int64, hits [M] int32) of the cells with hits >= min_hits, and within radius of

@@ -7,6 +7,7 @@
     python scripts/odometry_stream.py --raw --scans 200 --warmup 20 [--out profiles/odometry_stream_raw.json]
     python scripts/odometry_stream.py --map --scans 200 --warmup 20 [--map-out map.ply] [--out profiles/odometry_stream_map.json]
     python scripts/odometry_stream.py --refine --scans 200 --warmup 20 [--refine-iters 3] [--out profiles/odometry_stream_refine.json]
+    python scripts/odometry_stream.py --map --local-map-radius 100 --local-map-every 10 --scans 200 --warmup 20 [--out profiles/odometry_stream_local_map.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -28,6 +29,11 @@ registered against the map before it is inserted), timed beside the --map loop o
 alone" pass on the drive: the prediction of scan i is refined[i-1] o (true relative motion o a fixed seeded error of
 about 5 cm and 0.1 degrees); pose error against synthetic.sequence_pose before and after VoxelMap.register, pairs per
 scan and ms per register call from device events (--seed must be the drive's).
+--local-map-radius R [--local-map-every K] (implies --map): the --map loop, the --refine loop when given, and the
+inserts alone under the drive's own poses once more with the rolling local map (VoxelMap.prune about the scan's pose
+every K scans; rslo_map_prune in csrc/map.hip), each beside the same loop without pruning in this process: ms per scan,
+prune_stats, the largest n_cells seen, dropped_full, ms per prune call from device events (and of a call that evicts
+nothing), and the insert time over the last 200 scans.
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -105,6 +111,9 @@ def main():
     ap.add_argument("--map-out", default=None, help="write the map as a binary PLY")
     ap.add_argument("--refine", action="store_true", help="also run the runner with scan-to-map refinement (implies --map)")
     ap.add_argument("--refine-iters", type=int, default=3, help="Gauss-Newton iterations per scan")
+    ap.add_argument("--local-map-radius", type=float, default=None,
+                    help="also run the map loops with a rolling local map of this radius in metres (implies --map)")
+    ap.add_argument("--local-map-every", type=int, default=10, help="prune every K scans")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -112,7 +121,7 @@ def main():
     ap.add_argument("--save-scans", default=None, help="write the drive's scans to this .npz and stop")
     ap.add_argument("--load-scans", default=None, help="read the scans from a --save-scans file (profiled runs)")
     args = ap.parse_args()
-    args.map = args.map or args.refine
+    args.map = args.map or args.refine or args.local_map_radius is not None
     if args.launches:
         res = launches(args.launches[0], args.launches[1], args.scans_a, args.scans_b)
         line = json.dumps(res)
@@ -304,11 +313,129 @@ def main():
             res["map_ply_bytes"] = os.path.getsize(args.map_out)
     if args.refine:
         res.update(refine_report(args, net, scans, timed, res["map_ms_per_scan"]))
+    if args.local_map_radius is not None:
+        res.update(local_map_report(args, net, scans, timed, res))
     line = json.dumps(res)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def local_map_report(args, net, scans, timed, res):
+    """The map loops with a rolling local map beside the figures of the same loops without one (already in `res`, or
+    measured here in the same way)."""
+    import torch
+    from rslo_amd import inference, mapping, synthetic
+    dev = scans[0].device
+    W, N = args.warmup, args.scans
+    lm = dict(radius=args.local_map_radius, every=args.local_map_every)
+    out = {"local_map": lm}
+
+    def runner_loop(name, base, **kw):
+        vmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+        runner = inference.OdometryRunner(net, voxel_map=vmap, local_map=lm, **kw)
+        pend = {}
+
+        def run(rng):
+            rng = list(rng)
+            for k, i in enumerate(rng):
+                if i not in pend:
+                    pend[i] = runner.submit(scans[i])
+                if k + 1 < len(rng) and rng[k + 1] not in pend:
+                    pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
+                runner.run(pend.pop(i))
+        out[name + "_ms_per_scan"], out[name + "_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+        out[name + "_minus_%s_ms_per_scan" % base] = round(out[name + "_ms_per_scan"] - res[base + "_ms_per_scan"], 3)
+        out[name + "_stats"], out[name + "_prune_stats"] = vmap.stats(), vmap.prune_stats()
+        # once more, untimed, for the largest n_cells: behind a run() that pruned, the cells in front of that prune are
+        # the cells now plus what the prune evicted or lost (two host reads per prune, hence not in the timed loop)
+        runner.reset()
+        peak, gone = 0, 0
+        for i in range(W + N):
+            run([i])
+            if (i + 1) % lm["every"] == 0 or i == W + N - 1:
+                ps = vmap.prune_stats()
+                peak = max(peak, vmap.stats()["n_cells"] + ps["n_evicted"] + ps["n_lost"] - gone)
+                gone = ps["n_evicted"] + ps["n_lost"]
+        out[name + "_largest_n_cells"] = peak
+        out[name + "_largest_load"] = round(peak / float(args.map_capacity), 4)
+        out[name + "_dropped_full"] = vmap.stats()["dropped_full"]
+        runner.close()
+
+    runner_loop("local_map", "map")
+    if args.refine:
+        runner_loop("local_refine", "refine", refine=dict(iters=args.refine_iters))
+    # the inserts alone under the drive's own poses, without and with pruning
+    true = [torch.from_numpy(synthetic.sequence_pose(i, args.seed)).to(dev) for i in range(W + N)]
+    alone = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+    alone.reserve(max(s.shape[0] for s in scans))
+    alone.reserve_prune()
+    K, R = lm["every"], lm["radius"]
+    tail = min(200, N)
+
+    def drive(prune):
+        """Three passes over the drive: timed as a whole (no event inside the loop, so nothing but the calls themselves
+        is charged); every prune call between two events of its own; n_cells read where it peaks."""
+        alone.reset()
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        for i in range(W + N):
+            if i == W:
+                torch.cuda.synchronize()
+                ev[0].record()
+            if i == W + N - tail:
+                ev[1].record()
+            alone.insert(scans[i], true[i])
+            if prune and (i + 1) % K == 0:
+                alone.prune(true[i], R)
+        ev[2].record()
+        ev[2].synchronize()
+        r = {"ms_per_scan": round(ev[0].elapsed_time(ev[2]) / N, 4),
+             "last_%d_ms_per_scan" % tail: round(ev[1].elapsed_time(ev[2]) / tail, 4),
+             "stats": alone.stats(), "prune_stats": alone.prune_stats()}
+        # once more: n_cells in front of every prune (without pruning it only grows), each prune call timed on its own
+        alone.reset()
+        peak, calls = 0, []
+        for i in range(W + N):
+            alone.insert(scans[i], true[i])
+            if (i + 1) % K == 0 or i == W + N - 1:
+                n_cells = alone.stats()["n_cells"]
+                peak = max(peak, n_cells)
+                if prune and (i + 1) % K == 0:
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    alone.prune(true[i], R)
+                    b.record()
+                    calls.append((i, n_cells, a, b))
+        torch.cuda.synchronize()
+        r["largest_n_cells"] = peak
+        r["largest_load"] = round(peak / float(args.map_capacity), 4)
+        if calls:
+            ms = [a.elapsed_time(b) for i, n, a, b in calls if i >= W]
+            evicting = [i for i, n, a, b in calls if i >= W]
+            r["prune_calls_timed"] = len(ms)
+            if ms:
+                r["prune_ms_per_call_mean"] = round(sum(ms) / len(ms), 4)
+                r["prune_ms_per_call_min"], r["prune_ms_per_call_max"] = round(min(ms), 4), round(max(ms), 4)
+                r["prune_ms_per_scan"] = round(sum(ms) / N, 4)
+                loads = [n / float(args.map_capacity) for i, n, a, b in calls if i >= W]
+                r["prune_load_min"], r["prune_load_max"] = round(min(loads), 4), round(max(loads), 4)
+                r["prune_last_calls"] = [[evicting[k], round(loads[k], 4), round(ms[k], 4)] for k in range(max(0, len(ms) - 5), len(ms))]
+        return r
+
+    out["true_pose_plain"] = drive(False)
+    out["true_pose_local_map"] = drive(True)
+    # a call that evicts nothing, on the map the pruned pass left
+    out["prune_load_at_no_evict_calls"] = round(alone.stats()["n_cells"] / float(args.map_capacity), 4)
+    alone.prune(true[-1], float("inf"))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(20):
+        alone.prune(true[-1], float("inf"))
+    e1.record()
+    e1.synchronize()
+    out["prune_no_evict_ms_per_call"] = round(e0.elapsed_time(e1) / 20, 4)
+    return out
 
 
 def _rot(q, v):
