@@ -1034,6 +1034,30 @@ RSLO_API int rslo_map_prune(void *map, size_t map_bytes, const double *center3 /
  * skips.  The "converged" flag lives in the workspace; later iterations exit early.  No host read; 2 launches per
  * iteration whatever happens (1 for N == 0), so the call is capturable.  iters outside 1..32, a negative or NaN
  * tolerance: RSLO_EINVAL; a short workspace: RSLO_EWS; an argument error writes nothing.
+ *
+ * Robust weight (rslo_map_normal_eq_w, rslo_map_register_w: the calls above plus robust_scale).  A matched point whose
+ * term -- plane or point, chosen exactly as above -- has the cost addend e (r*r, or d.x*d.x + d.y*d.y + d.z*d.z) gets
+ * the Geman-McClure weight  s2 = scale*scale, u = s2 / (s2 + e), rho = u*u,  and every one of its 28 addends is the
+ * addend above multiplied by rho: rho * (a_i*a_j), rho * (a_i*r), rho * (r*r), ...  The pair count stays the
+ * unweighted count of matched points, `cost` becomes the weighted cost.  scale == 0 means "no weights": the sums are
+ * the bits of rslo_map_normal_eq / rslo_map_register (the same kernel).  scale < 0, NaN or inf is RSLO_EINVAL, and so
+ * is a positive scale whose square is not a positive finite double (|scale| below about 1.5e-162 or above 1.3e154):
+ * u would be 0/0 for e == 0, or inf/inf.  Same reduction, same order, no floating-point atomics: bit-reproducible.
+ * Launch counts as above (2 per iteration, 1 for N == 0): capturable.
+ *
+ * Scheduled register (rslo_map_register_sched): coarse-to-fine registration over several maps of the same scans with
+ * different cell edges.  maps / map_bytes / voxel_sizes are HOST arrays of n_levels (1..8) entries, stages a HOST array
+ * [n_stages, 4] of rows {level, iters, max_dist, robust_scale}; all are read at enqueue time.  The stages run in order
+ * on the one pose7, in place; inside a stage the rules of rslo_map_register_w hold against maps[level], including
+ * 0 < max_dist <= voxel_sizes[level].  The "converged" flag is cleared at the start of every stage by the stage's
+ * first launches (its first iteration does not read the flag, and rewrites it), not by a host write: a met tolerance
+ * skips the rest of that stage only (status 3), the next stage runs.  info double [sum of iters, 8], rows in order of
+ * execution: {status, pairs, cost, |dt|, theta, stage, level, 0} (skipped rows: {3, 0, 0, 0, 0, stage, level, 0}).
+ * The sum of iters is 1..64.  RSLO_EINVAL: n_levels outside 1..8, a null array or map, map_bytes below
+ * rslo_map_bytes(1024), a level that is not an integer in 0..n_levels-1, a stage with iters < 1 (or not an integer),
+ * a bad max_dist or scale, more than 64 iterations, and the argument errors of rslo_map_register; RSLO_EWS: ws_bytes
+ * below rslo_map_register_ws_bytes(N) (unchanged).  Every stage is checked before the first launch: an error writes
+ * nothing.  No host read, nothing allocated, and the number of launches depends on the schedule alone: capturable.
  * ------------------------------------------------------------------------------------ */
 RSLO_API int rslo_map_params(const void *map, size_t map_bytes, double *params3_host, void *stream);
 RSLO_API int rslo_map_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
@@ -1048,6 +1072,20 @@ RSLO_API int rslo_map_register(const void *map, size_t map_bytes, double voxel_s
                                int stride_floats, int width, int N, double *pose7, int iters, int metric,
                                double max_dist, int min_hits, double damping, int min_pairs, double tol_t, double tol_r,
                                double *info /*[iters,8]*/, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_map_normal_eq_w(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                  int stride_floats, int width, int N, const double *pose7, int metric, double max_dist,
+                                  int min_hits, double robust_scale, double *out29, void *ws, size_t ws_bytes,
+                                  void *stream);
+RSLO_API int rslo_map_register_w(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                 int stride_floats, int width, int N, double *pose7, int iters, int metric,
+                                 double max_dist, int min_hits, double damping, int min_pairs, double tol_t, double tol_r,
+                                 double robust_scale, double *info /*[iters,8]*/, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_map_register_sched(const void *const *maps /*[n_levels] host*/, const size_t *map_bytes /*host*/,
+                                     const double *voxel_sizes /*host*/, int n_levels,
+                                     const double *stages /*[n_stages,4] host*/, int n_stages, const float *points,
+                                     int stride_floats, int width, int N, double *pose7, int metric, int min_hits,
+                                     double damping, int min_pairs, double tol_t, double tol_r,
+                                     double *info /*[sum of iters,8]*/, void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

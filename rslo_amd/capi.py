@@ -204,6 +204,12 @@ SIGNATURES = {
     "rslo_map_normal_eq": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _i, _vp, _i, C.c_double, _i, _vp, _vp, _sz, _vp]),
     "rslo_map_register": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, _i, C.c_double, _i,
                                     C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_map_normal_eq_w": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _i, _vp, _i, C.c_double, _i, C.c_double, _vp, _vp,
+                                       _sz, _vp]),
+    "rslo_map_register_w": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, _i, C.c_double, _i,
+                                      C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_map_register_sched": (C.c_int, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, _i,
+                                          C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -1252,9 +1258,12 @@ def _map_ws(ws, P, device):
     return ws
 
 
-def map_normal_eq(buf, points, pose, voxel_size=None, metric="plane", max_dist=None, min_hits=1, out=None, ws=None):
+def map_normal_eq(buf, points, pose, voxel_size=None, metric="plane", max_dist=None, min_hits=1, out=None, ws=None,
+                  robust_scale=None):
     """rslo_map_normal_eq: out float64 CUDA [29] = the upper triangle of H (21), g (6), cost, pairs at pose, over the
-    matches of map_nearest.  metric "plane" reads the normals at columns 4..6 of points.  No host read."""
+    matches of map_nearest.  metric "plane" reads the normals at columns 4..6 of points.  No host read.
+    robust_scale (not None): rslo_map_normal_eq_w, every matched point's addends times its Geman-McClure weight
+    (0.0: no weights, the bits of rslo_map_normal_eq)."""
     ptr, nbytes = _map_buf(buf)
     src, stride = _rows3(points, "points")
     P = points.shape[0]
@@ -1265,6 +1274,13 @@ def map_normal_eq(buf, points, pose, voxel_size=None, metric="plane", max_dist=N
     if out.shape != (29,):
         raise RsloHipError("map_normal_eq: out must be [29]")
     ws = _map_ws(ws, P, points.device)
+    if robust_scale is not None:
+        _chk(lib().rslo_map_normal_eq_w(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
+                                        _pose7(pose, "map_normal_eq_w"), _map_metric(metric),
+                                        float(voxel_size if max_dist is None else max_dist), int(min_hits),
+                                        float(robust_scale), _ptr(out, torch.float64, "out"), ws.data_ptr(),
+                                        ws.numel() * ws.element_size(), _stream()), "rslo_map_normal_eq_w")
+        return out
     _chk(lib().rslo_map_normal_eq(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
                                   _pose7(pose, "map_normal_eq"), _map_metric(metric),
                                   float(voxel_size if max_dist is None else max_dist), int(min_hits),
@@ -1274,10 +1290,11 @@ def map_normal_eq(buf, points, pose, voxel_size=None, metric="plane", max_dist=N
 
 
 def map_register(buf, points, pose, voxel_size=None, iters=5, metric="plane", max_dist=None, min_hits=1, damping=0.0,
-                 min_pairs=50, tol_t=0.0, tol_r=0.0, info=None, ws=None):
+                 min_pairs=50, tol_t=0.0, tol_r=0.0, info=None, ws=None, robust_scale=None):
     """rslo_map_register: `iters` Gauss-Newton iterations of points against the map; pose (float64 CUDA [7]) is updated
     IN PLACE.  Returns info float64 CUDA [iters, 8]: rows {status, pairs, cost, |dt|, theta, 0, 0, 0}, status 0 step taken, 1
-    too few pairs, 2 not positive definite, 3 skipped after convergence.  No host read, a fixed number of launches: capturable."""
+    too few pairs, 2 not positive definite, 3 skipped after convergence.  No host read, a fixed number of launches: capturable.
+    robust_scale (not None): rslo_map_register_w, Geman-McClure weights of that scale (0.0: no weights, the same bits)."""
     ptr, nbytes = _map_buf(buf)
     src, stride = _rows3(points, "points")
     P = points.shape[0]
@@ -1289,11 +1306,52 @@ def map_register(buf, points, pose, voxel_size=None, iters=5, metric="plane", ma
     if info.shape != (iters, 8):
         raise RsloHipError("map_register: info must be [iters, 8]")
     ws = _map_ws(ws, P, points.device)
+    if robust_scale is not None:
+        _chk(lib().rslo_map_register_w(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
+                                       _pose7(pose, "map_register_w"), iters, _map_metric(metric),
+                                       float(voxel_size if max_dist is None else max_dist), int(min_hits), float(damping),
+                                       int(min_pairs), float(tol_t), float(tol_r), float(robust_scale),
+                                       _ptr(info, torch.float64, "info"), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                       _stream()), "rslo_map_register_w")
+        return info
     _chk(lib().rslo_map_register(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
                                  _pose7(pose, "map_register"), iters, _map_metric(metric),
                                  float(voxel_size if max_dist is None else max_dist), int(min_hits), float(damping),
                                  int(min_pairs), float(tol_t), float(tol_r), _ptr(info, torch.float64, "info"),
                                  ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_map_register")
+    return info
+
+
+def map_register_sched(bufs, voxel_sizes, stages, points, pose, metric="plane", min_hits=1, damping=0.0, min_pairs=50,
+                       tol_t=0.0, tol_r=0.0, info=None, ws=None):
+    """rslo_map_register_sched: the stages (rows of (level, iters, max_dist, robust_scale), host numbers) run in order
+    on pose (float64 CUDA [7], updated IN PLACE), each against bufs[level] with cell edge voxel_sizes[level].  Returns
+    info float64 CUDA [sum of iters, 8]: rows {status, pairs, cost, |dt|, theta, stage, level, 0}.  The arrays are read at
+    enqueue time; no host read of the device, a number of launches fixed by the schedule: capturable."""
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    L = len(bufs)
+    if L < 1 or len(voxel_sizes) != L:
+        raise RsloHipError("map_register_sched: one voxel size per map, and at least one map")
+    ptrs = [_map_buf(b) for b in bufs]
+    maps = (C.c_void_p * L)(*[p for p, _ in ptrs])
+    nbytes = (C.c_size_t * L)(*[n for _, n in ptrs])
+    voxels = (C.c_double * L)(*[float(v) for v in voxel_sizes])
+    rows = [tuple(float(v) for v in st) for st in stages]
+    if any(len(r) != 4 for r in rows):
+        raise RsloHipError("map_register_sched: a stage is (level, iters, max_dist, robust_scale)")
+    flat = (C.c_double * (4 * len(rows)))(*[v for r in rows for v in r])
+    total = sum(int(r[1]) for r in rows if r[1] == r[1] and abs(r[1]) < 1e9)      # (the library refuses what is not an integer >= 1)
+    if info is None:
+        info = torch.empty((max(total, 0), 8), dtype=torch.float64, device=points.device)
+    if info.shape != (total, 8):
+        raise RsloHipError("map_register_sched: info must be [sum of iters, 8] = [%d, 8]" % total)
+    ws = _map_ws(ws, P, points.device)
+    _chk(lib().rslo_map_register_sched(maps, nbytes, voxels, L, flat, len(rows), src, stride, int(points.shape[1]), P,
+                                       _pose7(pose, "map_register_sched"), _map_metric(metric), int(min_hits),
+                                       float(damping), int(min_pairs), float(tol_t), float(tol_r),
+                                       _ptr(info, torch.float64, "info"), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                       _stream()), "rslo_map_register_sched")
     return info
 
 

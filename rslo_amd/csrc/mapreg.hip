@@ -11,6 +11,11 @@
 // Sums: 28 doubles and the pair count per point, reduced in a fixed order -- a shuffle tree inside each wave, the four
 // waves of a block in wave order, the blocks in block order by the second stage (one wave; lane j owns sum j).  No
 // floating-point atomic anywhere: two runs give the same bits.
+//
+// Robust weights (rslo_map_normal_eq_w / _register_w / _register_sched): the accumulate kernel is one template; its
+// WEIGHTED instantiation scales the 28 addends of a matched point by the Geman-McClure weight of its cost addend, the
+// other one is the unweighted kernel as it always was.  A schedule is a host loop over (map, iterations, max_dist,
+// scale) stages on one pose: the launches are those of separate register calls, the info rows run on.
 #include "rslo_common.h"
 #include "map_table.h"
 
@@ -23,6 +28,8 @@
 #define MR_BLOCK 256
 #define MR_WS_HDR 256                    /* int32 word 0: the "converged" flag of rslo_map_register */
 #define MR_MAX_ITERS 32
+#define MR_MAX_SCHED_ITERS 64              /* sum of the iterations of a schedule */
+#define MR_MAX_LEVELS 8
 
 static long long mr_cap_max(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
   long long cap = 0;
@@ -106,12 +113,14 @@ __global__ __launch_bounds__(MR_BLOCK) void k_map_nearest(const void *map, long 
   if (rows_out) *(float4 *)(rows_out + (size_t)i * 4) = row;
 }
 
-// block partial [MR_NSUM] of the addends of points blockIdx.x * 256 .. + 255 at the pose in pose7
+// block partial [MR_NSUM] of the addends of points blockIdx.x * 256 .. + 255 at the pose in pose7.  WEIGHTED: the 28
+// addends of a matched point are multiplied by rho = u*u, u = s2 / (s2 + e), e its cost addend (s2 = scale*scale > 0).
+template <bool WEIGHTED>
 __global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long long cap_max, double voxel,
                                                            const float *__restrict__ points, int stride, int width, int N,
                                                            const double *__restrict__ pose, int metric, double max_dist,
                                                            int min_hits, int iter, const int32_t *__restrict__ flag,
-                                                           double *__restrict__ partials) {
+                                                           double *__restrict__ partials, double s2) {
   if (iter > 0 && *flag) return;      // converged in an earlier iteration: the second stage does not read the partials
   __shared__ double part[MR_BLOCK / 64][MR_NSUM];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -170,6 +179,12 @@ __global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long
         acc[o++] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
       }
       acc[o] = 1.0;
+      if (WEIGHTED) {      // e = acc[27] >= 0 (or NaN, which stays NaN as it would unweighted); s2 > 0: u is in [0, 1]
+        const double u = s2 / (s2 + acc[MR_NSUM - 2]);
+        const double rho = u * u;
+#pragma unroll
+        for (int k = 0; k < MR_NSUM - 1; ++k) acc[k] = rho * acc[k];
+      }
     }
   }
   // fixed order: lane l takes l + 32, then + 16, ... inside its wave; then the waves 0..3 in turn
@@ -195,17 +210,21 @@ __global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long
 struct MrSolve {
   int iters, min_pairs;
   double damping, tol_t, tol_r;
+  int row;                 // the info row of this iteration (`iter` counts inside a stage, the rows run on)
+  double stage, level;     // info columns 5 and 6 (0 outside a schedule)
 };
 
 // Second stage, one wave: lane j sums partial j of the blocks in block order.  out29 (rslo_map_normal_eq) receives the
 // sums; with pose7 (rslo_map_register) lane 0 then takes the Gauss-Newton step of iteration `iter` and writes its info row.
+// Iteration 0 (of a call, or of a stage of a schedule) does not read the flag and rewrites it: that clears it.
 __global__ __launch_bounds__(64) void k_mapreg_finish(const double *__restrict__ partials, int n_blocks,
                                                       double *__restrict__ out29, double *__restrict__ pose7, int iter,
                                                       MrSolve sp, int32_t *__restrict__ flag, double *__restrict__ info) {
   __shared__ double tot[MR_NSUM];
-  double *row = info ? info + (size_t)iter * 8 : nullptr;
+  double *row = info ? info + (size_t)sp.row * 8 : nullptr;
   if (pose7 && iter > 0 && *flag) {
-    if (threadIdx.x < 8) row[threadIdx.x] = threadIdx.x == 0 ? 3.0 : 0.0;
+    if (threadIdx.x < 8)
+      row[threadIdx.x] = threadIdx.x == 0 ? 3.0 : threadIdx.x == 5 ? sp.stage : threadIdx.x == 6 ? sp.level : 0.0;
     return;
   }
   if (threadIdx.x < MR_NSUM) {
@@ -290,7 +309,9 @@ __global__ __launch_bounds__(64) void k_mapreg_finish(const double *__restrict__
   row[2] = cost;
   row[3] = nt;
   row[4] = th;
-  row[5] = row[6] = row[7] = 0.0;
+  row[5] = sp.stage;
+  row[6] = sp.level;
+  row[7] = 0.0;
 }
 
 extern "C" int rslo_map_params(const void *map, size_t map_bytes, double *params3_host, void *stream) {
@@ -347,13 +368,16 @@ extern "C" size_t rslo_map_register_ws_bytes(int N) {
 // the launches of one evaluation of the normal equations (+ the step of iteration `iter` when pose_rw is given)
 static int mr_launch(const void *map, long long cap_max, double voxel, const float *points, int stride, int width, int N,
                      const double *pose, int metric, double max_dist, int min_hits, double *out29, double *pose_rw,
-                     int iter, const MrSolve &sp, double *info, void *ws, hipStream_t s) {
+                     int iter, const MrSolve &sp, double *info, void *ws, hipStream_t s, double scale = 0.0) {
   int32_t *flag = (int32_t *)ws;
   double *partials = (double *)((unsigned char *)ws + MR_WS_HDR);
   const int nb = (int)rslo_cdiv(N, MR_BLOCK);
-  if (nb > 0)
-    hipLaunchKernelGGL(k_mapreg_accum, dim3((unsigned)nb), dim3(MR_BLOCK), 0, s, map, cap_max, voxel, points, stride, width,
-                       N, pose, metric, max_dist, min_hits, iter, (const int32_t *)flag, partials);
+  if (nb > 0 && scale == 0.0)      // no weights: the unweighted kernel, to the bit
+    hipLaunchKernelGGL(k_mapreg_accum<false>, dim3((unsigned)nb), dim3(MR_BLOCK), 0, s, map, cap_max, voxel, points, stride,
+                       width, N, pose, metric, max_dist, min_hits, iter, (const int32_t *)flag, partials, 0.0);
+  else if (nb > 0)
+    hipLaunchKernelGGL(k_mapreg_accum<true>, dim3((unsigned)nb), dim3(MR_BLOCK), 0, s, map, cap_max, voxel, points, stride,
+                       width, N, pose, metric, max_dist, min_hits, iter, (const int32_t *)flag, partials, scale * scale);
   hipLaunchKernelGGL(k_mapreg_finish, dim3(1), dim3(64), 0, s, (const double *)partials, nb, out29, pose_rw, iter, sp, flag,
                      info);
   return RSLO_OK;
@@ -377,19 +401,65 @@ static int mr_check_sums(const char *name, const float *points, int stride, int 
   return RSLO_OK;
 }
 
+// scale == 0: no weights; otherwise scale*scale must be a positive finite double (u = s2 / (s2 + e) is then defined
+// for every e >= 0, e == 0 included)
+static bool mr_scale_ok(double scale) {
+  const double s2 = scale * scale;
+  return scale == 0.0 || (scale > 0.0 && s2 > 0.0 && s2 < (double)__builtin_inff());
+}
+
+static int mr_normal_eq(const char *name, const void *map, size_t map_bytes, double voxel_size, const float *points,
+                        int stride_floats, int width, int N, const double *pose7, int metric, double max_dist,
+                        int min_hits, double scale, double *out29, void *ws, size_t ws_bytes, void *stream) {
+  const long long cap_max = mr_cap_max(map_bytes);
+  int rc = mr_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(out29, "%s: out29 is null", name);
+  RSLO_CHECK_ARG(mr_scale_ok(scale), "%s: robust_scale must be 0 (no weights) or positive with a finite, non-zero square", name);
+  rc = mr_check_sums(name, points, stride_floats, width, N, metric, ws, ws_bytes);
+  if (rc) return rc;
+  const MrSolve sp = {0, 0, 0.0, 0.0, 0.0, 0, 0.0, 0.0};
+  mr_launch(map, cap_max, voxel_size, points, stride_floats, width, N, pose7, metric, max_dist, min_hits, out29, nullptr, 0,
+            sp, nullptr, ws, (hipStream_t)stream, scale);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
 extern "C" int rslo_map_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
                                   int stride_floats, int width, int N, const double *pose7, int metric, double max_dist,
                                   int min_hits, double *out29, void *ws, size_t ws_bytes, void *stream) {
+  return mr_normal_eq("map_normal_eq", map, map_bytes, voxel_size, points, stride_floats, width, N, pose7, metric, max_dist,
+                      min_hits, 0.0, out29, ws, ws_bytes, stream);
+}
+
+extern "C" int rslo_map_normal_eq_w(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                    int stride_floats, int width, int N, const double *pose7, int metric,
+                                    double max_dist, int min_hits, double robust_scale, double *out29, void *ws,
+                                    size_t ws_bytes, void *stream) {
+  return mr_normal_eq("map_normal_eq_w", map, map_bytes, voxel_size, points, stride_floats, width, N, pose7, metric,
+                      max_dist, min_hits, robust_scale, out29, ws, ws_bytes, stream);
+}
+
+static int mr_register(const char *name, const void *map, size_t map_bytes, double voxel_size, const float *points,
+                       int stride_floats, int width, int N, double *pose7, int iters, int metric, double max_dist,
+                       int min_hits, double damping, int min_pairs, double tol_t, double tol_r, double scale, double *info,
+                       void *ws, size_t ws_bytes, void *stream) {
   const long long cap_max = mr_cap_max(map_bytes);
-  int rc = mr_check("map_normal_eq", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  int rc = mr_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
   if (rc) return rc;
-  RSLO_CHECK_ARG(out29, "map_normal_eq: out29 is null");
-  rc = mr_check_sums("map_normal_eq", points, stride_floats, width, N, metric, ws, ws_bytes);
+  RSLO_CHECK_ARG(iters >= 1 && iters <= MR_MAX_ITERS, "%s: iters must be in 1 .. 32", name);
+  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "%s: tol_t and tol_r must be >= 0 (NaN is refused)", name);
+  RSLO_CHECK_ARG(mr_scale_ok(scale), "%s: robust_scale must be 0 (no weights) or positive with a finite, non-zero square", name);
+  RSLO_CHECK_ARG(info, "%s: info is null", name);
+  rc = mr_check_sums(name, points, stride_floats, width, N, metric, ws, ws_bytes);
   if (rc) return rc;
-  const MrSolve sp = {0, 0, 0.0, 0.0, 0.0};
-  mr_launch(map, cap_max, voxel_size, points, stride_floats, width, N, pose7, metric, max_dist, min_hits, out29, nullptr, 0,
-            sp, nullptr, ws, (hipStream_t)stream);
-  RSLO_CHECK_LAUNCH("map_normal_eq");
+  MrSolve sp = {iters, min_pairs, damping, tol_t, tol_r, 0, 0.0, 0.0};
+  for (int it = 0; it < iters; ++it) {
+    sp.row = it;
+    mr_launch(map, cap_max, voxel_size, points, stride_floats, width, N, pose7, metric, max_dist, min_hits, nullptr, pose7,
+              it, sp, info, ws, (hipStream_t)stream, scale);
+  }
+  RSLO_CHECK_LAUNCH(name);
   return RSLO_OK;
 }
 
@@ -397,18 +467,71 @@ extern "C" int rslo_map_register(const void *map, size_t map_bytes, double voxel
                                  int stride_floats, int width, int N, double *pose7, int iters, int metric,
                                  double max_dist, int min_hits, double damping, int min_pairs, double tol_t, double tol_r,
                                  double *info, void *ws, size_t ws_bytes, void *stream) {
-  const long long cap_max = mr_cap_max(map_bytes);
-  int rc = mr_check("map_register", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  return mr_register("map_register", map, map_bytes, voxel_size, points, stride_floats, width, N, pose7, iters, metric,
+                     max_dist, min_hits, damping, min_pairs, tol_t, tol_r, 0.0, info, ws, ws_bytes, stream);
+}
+
+extern "C" int rslo_map_register_w(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                   int stride_floats, int width, int N, double *pose7, int iters, int metric,
+                                   double max_dist, int min_hits, double damping, int min_pairs, double tol_t,
+                                   double tol_r, double robust_scale, double *info, void *ws, size_t ws_bytes,
+                                   void *stream) {
+  return mr_register("map_register_w", map, map_bytes, voxel_size, points, stride_floats, width, N, pose7, iters, metric,
+                     max_dist, min_hits, damping, min_pairs, tol_t, tol_r, robust_scale, info, ws, ws_bytes, stream);
+}
+
+// Every argument of every stage is checked before the first launch; then the stages are the launches of
+// rslo_map_register_w calls on maps[level], with the info rows running on and columns 5 / 6 naming stage and level.
+extern "C" int rslo_map_register_sched(const void *const *maps, const size_t *map_bytes, const double *voxel_sizes,
+                                       int n_levels, const double *stages, int n_stages, const float *points,
+                                       int stride_floats, int width, int N, double *pose7, int metric, int min_hits,
+                                       double damping, int min_pairs, double tol_t, double tol_r, double *info, void *ws,
+                                       size_t ws_bytes, void *stream) {
+  const char *name = "map_register_sched";
+  RSLO_CHECK_ARG(n_levels >= 1 && n_levels <= MR_MAX_LEVELS, "%s: n_levels must be in 1 .. 8", name);
+  RSLO_CHECK_ARG(maps && map_bytes && voxel_sizes && stages, "%s: null array", name);
+  RSLO_CHECK_ARG(n_stages >= 1 && n_stages <= MR_MAX_SCHED_ITERS, "%s: n_stages must be in 1 .. 64", name);
+  long long cap_max[MR_MAX_LEVELS];
+  for (int l = 0; l < n_levels; ++l) {
+    cap_max[l] = mr_cap_max(map_bytes[l]);
+    RSLO_CHECK_ARG(maps[l] && cap_max[l] > 0, "%s: level %d has no map (null, or map_bytes below rslo_map_bytes(1024))", name, l);
+    RSLO_CHECK_ARG(voxel_sizes[l] > 0.0 && voxel_sizes[l] < (double)__builtin_inff(),
+                   "%s: voxel_sizes[%d] must be positive and finite", name, l);
+  }
+  int total = 0;
+  for (int k = 0; k < n_stages; ++k) {
+    const double *st = stages + (size_t)k * 4;
+    RSLO_CHECK_ARG(st[0] >= 0.0 && st[0] < (double)n_levels && st[0] == (double)(int)st[0],
+                   "%s: stage %d: level must be an integer in 0 .. n_levels - 1", name, k);
+    RSLO_CHECK_ARG(st[1] >= 1.0 && st[1] <= (double)MR_MAX_SCHED_ITERS && st[1] == (double)(int)st[1],
+                   "%s: stage %d: iters must be an integer >= 1 (all stages together: at most 64)", name, k);
+    total += (int)st[1];
+    RSLO_CHECK_ARG(total <= MR_MAX_SCHED_ITERS, "%s: the iterations of all stages must sum to 1 .. 64", name);
+    RSLO_CHECK_ARG(st[2] > 0.0 && st[2] <= voxel_sizes[(int)st[0]],
+                   "%s: stage %d: need 0 < max_dist <= the level's voxel_size (NaN is refused)", name, k);
+    RSLO_CHECK_ARG(mr_scale_ok(st[3]),
+                   "%s: stage %d: robust_scale must be 0 (no weights) or positive with a finite, non-zero square", name, k);
+  }
+  RSLO_CHECK_ARG(N >= 0 && stride_floats >= 3, "%s: N < 0 or stride_floats < 3", name);
+  RSLO_CHECK_ARG(pose7, "%s: pose7 is null", name);
+  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "%s: tol_t and tol_r must be >= 0 (NaN is refused)", name);
+  RSLO_CHECK_ARG(info, "%s: info is null", name);
+  const int rc = mr_check_sums(name, points, stride_floats, width, N, metric, ws, ws_bytes);
   if (rc) return rc;
-  RSLO_CHECK_ARG(iters >= 1 && iters <= MR_MAX_ITERS, "map_register: iters must be in 1 .. 32");
-  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "map_register: tol_t and tol_r must be >= 0 (NaN is refused)");
-  RSLO_CHECK_ARG(info, "map_register: info is null");
-  rc = mr_check_sums("map_register", points, stride_floats, width, N, metric, ws, ws_bytes);
-  if (rc) return rc;
-  const MrSolve sp = {iters, min_pairs, damping, tol_t, tol_r};
-  for (int it = 0; it < iters; ++it)
-    mr_launch(map, cap_max, voxel_size, points, stride_floats, width, N, pose7, metric, max_dist, min_hits, nullptr, pose7,
-              it, sp, info, ws, (hipStream_t)stream);
-  RSLO_CHECK_LAUNCH("map_register");
+  MrSolve sp = {0, min_pairs, damping, tol_t, tol_r, 0, 0.0, 0.0};
+  int row = 0;
+  for (int k = 0; k < n_stages; ++k) {
+    const double *st = stages + (size_t)k * 4;
+    const int level = (int)st[0], iters = (int)st[1];
+    sp.iters = iters;
+    sp.stage = (double)k;
+    sp.level = (double)level;
+    for (int it = 0; it < iters; ++it) {      // `it` restarts: the stage's first iteration ignores and rewrites the flag
+      sp.row = row++;
+      mr_launch(maps[level], cap_max[level], voxel_sizes[level], points, stride_floats, width, N, pose7, metric, st[2],
+                min_hits, nullptr, pose7, it, sp, info, ws, (hipStream_t)stream, st[3]);
+    }
+  }
+  RSLO_CHECK_LAUNCH(name);
   return RSLO_OK;
 }

@@ -258,6 +258,12 @@ class OdometryRunner:
       relative() stay the open-loop chain, bit for bit; refined_trajectory() is the second chain and refine_info() the
       [n, iters, 8] info rows of register, both on the device.  A fixed number of launches per scan, no
       synchronisation, no stream.  None (the default): today's behaviour to the bit.
+    * Coarse-to-fine refinement: voxel_map=MapPyramid(...) (one VoxelMap per voxel size) with
+      refine=dict(schedule=[(level, iters, max_dist or None, robust_scale), ...]) -- or refine=dict(): the pyramid's
+      default_schedule() -- runs MapPyramid.register (rslo_map_register_sched, one call) where VoxelMap.register runs
+      above; insert, reset and prune reach every level; refine_info() is [n, sum of iters, 8] with stage and level in
+      columns 5 and 6.  refine=dict(robust_scale=s) on a plain VoxelMap weights its iterations.  schedule= with a plain
+      VoxelMap, or together with iters=, is an error at construction.
     * Rolling local map: local_map=dict(radius=R, every=K, min_hits=1, grace=0) (needs voxel_map) keeps the map near the
       sensor: behind the insert of scan n (counted from 0 since reset()), when (n + 1) % K == 0, run() calls
       voxel_map.prune(center=row n of the chain that fed the insert, radius=R, min_hits=, grace=) -- the refined chain
@@ -271,6 +277,12 @@ class OdometryRunner:
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
+        if refine is not None and voxel_map is not None:      # (before anything is built: a refused option leaves nothing behind)
+            from rslo_amd import mapping
+            try:
+                refine, info_rows = mapping.check_refine(refine, voxel_map)
+            except ValueError as e:
+                raise capi.RsloHipError("OdometryRunner: %s" % e)
         self.normals = normals
         self.normal_radius, self.normal_max_nn = float(normal_radius), int(normal_max_nn)
         if normals == "estimate" and not (3 <= self.normal_max_nn <= 32 and self.normal_radius > 0):
@@ -320,18 +332,12 @@ class OdometryRunner:
         if refine is not None:
             if voxel_map is None:
                 raise capi.RsloHipError("OdometryRunner: refine needs a voxel_map to register against")
-            refine = dict(refine)
-            unknown = set(refine) - {"iters", "max_dist", "min_hits", "damping", "min_pairs", "tol_t", "tol_r"}
-            if unknown:
-                raise capi.RsloHipError("OdometryRunner: refine takes the keyword arguments of VoxelMap.register except "
-                                        "metric (chosen by the input's width) and info; got %s" % sorted(unknown))
-            refine.setdefault("iters", 5)
             self.refine = refine
             self._state2 = torch.zeros((7,), dtype=torch.float64, device=dev)
             self._count2 = torch.zeros((1,), dtype=torch.int32, device=dev)
             self._rel2 = torch.zeros((self.capacity, 7), dtype=torch.float32, device=dev)
             self._traj2 = torch.zeros((self.capacity, 7), dtype=torch.float64, device=dev)
-            self._info2 = torch.zeros((self.capacity, int(refine["iters"]), 8), dtype=torch.float64, device=dev)
+            self._info2 = torch.zeros((self.capacity, info_rows, 8), dtype=torch.float64, device=dev)
         self.local_map = None
         if local_map is not None:
             if voxel_map is None:

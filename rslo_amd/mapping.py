@@ -62,6 +62,26 @@ both classes:
     min_pairs pairs, 2 not positive definite, 3 skipped after an iteration with |dt| < tol_t and theta < tol_r.
 The device sums run in a fixed order but not in numpy's: the sums agree within the bound of a reordered float64 sum,
 the matches and the pair count exactly.
+
+Coarse-to-fine robust registration (rules: include/rslo_hip.h "Robust weight" and "Scheduled register"), on both classes
+and on the pyramids MapPyramid (device) / MapPyramidRef (numpy):
+
+    pose, info = vmap.register(scan, pose, iters=5, robust_scale=0.2)          # Geman-McClure weights
+    pyr = MapPyramid(voxel_sizes=(0.8, 0.4, 0.2), capacity=1 << 22)             # one VoxelMap per level, coarse to fine
+    pyr.insert(scan, pose)                                                      # ... every level
+    pose, info = pyr.register(scan, pose, schedule=pyr.default_schedule(4))     # stages in order on the one pose
+
+  * robust weight: a matched point whose term (plane or point, as above) has the cost addend e gets
+    s2 = scale*scale, u = s2 / (s2 + e), rho = u*u, and each of its 28 addends is the addend above times rho; the pair
+    count stays the unweighted count; cost is the weighted cost.  robust_scale = 0: no weights, today's bits.
+    scale < 0, NaN, inf, or a positive scale whose square is not a positive finite float64: ValueError;
+  * a schedule is a sequence of stages (level, iters, max_dist or None, robust_scale); max_dist None = the level's
+    voxel size, and 0 < max_dist <= that voxel size always.  The stages run in order on the one pose; a met tolerance
+    skips the rest of its stage only (status 3), the next stage starts afresh.  info [sum of iters, 8], rows
+    {status, pairs, cost, |dt|, theta, stage, level, 0}; the iterations of all stages sum to 1 .. 64, at most 8 levels;
+  * why a pyramid: the 27-cell search is exact only for max_dist <= voxel_size, so a start further off than one cell
+    edge of the fine map finds no correct pair.  A coarser map of the same scans widens the basin at the same 27 probes
+    per point; robust weights keep the coarse stages from pulling a good start away.
 """
 import numpy as np
 
@@ -136,6 +156,82 @@ def _check_register(iters, tol_t, tol_r):
         raise ValueError("register: iters must be in 1 .. 32")
     if not (float(tol_t) >= 0.0 and float(tol_r) >= 0.0):
         raise ValueError("register: tol_t and tol_r must be >= 0")
+
+
+def check_scale(scale):
+    """robust_scale: 0.0 (no weights) or positive with a positive finite square; -> float (ValueError otherwise)"""
+    sc = float(scale)
+    s2 = sc * sc
+    if not (sc == 0.0 or (sc > 0.0 and 0.0 < s2 < float("inf"))):
+        raise ValueError("robust_scale must be 0 (no weights) or positive with a finite, non-zero square, got %r" % (scale,))
+    return sc
+
+
+MAX_LEVELS = 8
+MAX_SCHEDULE_ITERS = 64
+
+
+def check_schedule(schedule, voxel_sizes):
+    """-> [(level, iters, max_dist, robust_scale)] with every max_dist a float; ValueError for a level outside the
+    pyramid, iters < 1, max_dist outside (0, voxel of the level], a bad scale, or more than 64 iterations in all."""
+    stages = []
+    total = 0
+    for st in schedule:
+        if len(st) != 4:
+            raise ValueError("schedule: a stage is (level, iters, max_dist or None, robust_scale), got %r" % (st,))
+        level, iters, max_dist, scale = st
+        if int(level) != level or not 0 <= level < len(voxel_sizes):
+            raise ValueError("schedule: level %r is not one of the pyramid's %d levels" % (level, len(voxel_sizes)))
+        if int(iters) != iters or iters < 1:
+            raise ValueError("schedule: a stage needs iters >= 1, got %r" % (iters,))
+        total += int(iters)
+        stages.append((int(level), int(iters), _max_dist_of(max_dist, voxel_sizes[int(level)]), check_scale(scale)))
+    if not 1 <= total <= MAX_SCHEDULE_ITERS:
+        raise ValueError("schedule: the iterations of all stages must sum to 1 .. %d, got %d" % (MAX_SCHEDULE_ITERS, total))
+    return stages
+
+
+def _check_pyramid(voxel_sizes, capacity=None):
+    voxel_sizes = tuple(float(v) for v in voxel_sizes)
+    if not 1 <= len(voxel_sizes) <= MAX_LEVELS:
+        raise ValueError("a pyramid has 1 .. %d levels" % MAX_LEVELS)
+    if any(not b < a for a, b in zip(voxel_sizes, voxel_sizes[1:])):
+        raise ValueError("voxel_sizes must be ordered coarse to fine (strictly decreasing), got %r" % (voxel_sizes,))
+    if capacity is None:
+        return voxel_sizes
+    caps = [capacity] * len(voxel_sizes) if np.ndim(capacity) == 0 else list(capacity)
+    if len(caps) != len(voxel_sizes):
+        raise ValueError("capacity is an int or one value per level")
+    return voxel_sizes, [int(c) for c in caps]
+
+
+REFINE_KEYS = ("max_dist", "min_hits", "damping", "min_pairs", "tol_t", "tol_r")
+
+
+def check_refine(refine, voxel_map):
+    """The refine= options of an OdometryRunner against the map it was given (ValueError): -> (keyword arguments of
+    voxel_map.register, info rows per scan).  A VoxelMap takes iters= (default 5) and the keywords of VoxelMap.register;
+    a pyramid takes schedule= (default: its default_schedule()) and no iters= / max_dist=, which the stages carry."""
+    refine = dict(refine)
+    pyramid = isinstance(voxel_map, _PyramidBase)
+    if "iters" in refine and "schedule" in refine:
+        raise ValueError("refine: iters= and schedule= exclude each other (a schedule carries its iterations)")
+    if "schedule" in refine and not pyramid:
+        raise ValueError("refine: schedule= needs a MapPyramid as voxel_map")
+    allowed = set(REFINE_KEYS) | {"robust_scale", "iters"}
+    if pyramid:
+        allowed = (set(REFINE_KEYS) - {"max_dist"}) | {"schedule"}
+    unknown = set(refine) - allowed
+    if unknown:
+        raise ValueError("refine takes %s (the metric is chosen by the input's width); got %s"
+                         % (", ".join(sorted(allowed)), sorted(unknown)))
+    if pyramid:
+        stages = check_schedule(voxel_map.default_schedule() if refine.get("schedule") is None else refine["schedule"],
+                                voxel_map.voxel_sizes)
+        refine["schedule"] = stages
+        return refine, sum(st[1] for st in stages)
+    refine.setdefault("iters", 5)
+    return refine, int(refine["iters"])
 
 
 def _cross3(a, b):
@@ -418,15 +514,28 @@ class VoxelMapRef:
         terms[:, 27] = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2]
         return (terms, plane) if return_plane else terms
 
-    def normal_equations(self, points, pose, metric="plane", max_dist=None, min_hits=1):
-        """[29] float64: the column sums of _pair_terms, then the number of pairs."""
+    def _weighted_terms(self, points, pose, metric="plane", max_dist=None, min_hits=1, robust_scale=0.0):
+        """_pair_terms with every row multiplied by its Geman-McClure weight rho (module docstring); scale 0: as they are"""
+        scale = check_scale(robust_scale)
         terms = self._pair_terms(points, pose, metric, max_dist, min_hits)
+        if scale == 0.0:
+            return terms
+        s2 = scale * scale
+        with np.errstate(all="ignore"):
+            u = s2 / (s2 + terms[:, 27])
+            rho = u * u
+            return terms * rho[:, None]
+
+    def normal_equations(self, points, pose, metric="plane", max_dist=None, min_hits=1, robust_scale=0.0):
+        """[29] float64: the column sums of _pair_terms (weighted when robust_scale > 0), then the number of pairs."""
+        terms = self._weighted_terms(points, pose, metric, max_dist, min_hits, robust_scale)
         return np.concatenate([terms.sum(axis=0), [float(len(terms))]])
 
     def register(self, points, pose, iters=5, metric=None, max_dist=None, min_hits=1, damping=0.0, min_pairs=50,
-                 tol_t=0.0, tol_r=0.0):
+                 tol_t=0.0, tol_r=0.0, robust_scale=0.0):
         """-> (pose [7] float64, info [iters, 8]); metric None: "plane" for points with normals, else "point"."""
         _check_register(iters, tol_t, tol_r)
+        check_scale(robust_scale)
         pts = np.asarray(points)
         metric = _metric_of(metric, pts.shape[1] if pts.ndim == 2 else 0)
         pose = np.array(pose, dtype=np.float64).reshape(7)
@@ -436,7 +545,7 @@ class VoxelMapRef:
             if done:
                 info[it, 0] = 3.0
                 continue
-            sums = self.normal_equations(pts, pose, metric, max_dist, min_hits)
+            sums = self.normal_equations(pts, pose, metric, max_dist, min_hits, robust_scale)
             info[it, 1], info[it, 2] = sums[28], sums[27]
             if sums[28] < min_pairs:
                 info[it, 0] = 1.0
@@ -531,28 +640,32 @@ class VoxelMap:
         return capi.map_nearest(self._buf, points, self._pose(pose), self.voxel_size, md, min_hits,
                                 rows=True if return_rows else None)
 
-    def normal_equations(self, points, pose, metric="plane", max_dist=None, min_hits=1):
-        """float64 CUDA [29]: the upper triangle of H (21), g (6), cost, pairs of the matched points at pose."""
+    def normal_equations(self, points, pose, metric="plane", max_dist=None, min_hits=1, robust_scale=0.0):
+        """float64 CUDA [29]: the upper triangle of H (21), g (6), cost, pairs of the matched points at pose; with
+        robust_scale > 0 every point's addends carry its Geman-McClure weight (rslo_map_normal_eq_w)."""
         from rslo_amd import capi
         md = _max_dist_of(max_dist, self.voxel_size)
+        scale = check_scale(robust_scale)
         self.reserve(points.shape[0])
         return capi.map_normal_eq(self._buf, points, self._pose(pose), self.voxel_size, _metric_of(metric, points.shape[1]),
-                                  md, min_hits, ws=self._reg_ws)
+                                  md, min_hits, ws=self._reg_ws, robust_scale=scale if scale else None)
 
     def register(self, points, pose, iters=5, metric=None, max_dist=None, min_hits=1, damping=0.0, min_pairs=50,
-                 tol_t=0.0, tol_r=0.0, info=None):
+                 tol_t=0.0, tol_r=0.0, info=None, robust_scale=0.0):
         """`iters` Gauss-Newton iterations of points (fp32 CUDA [P, F], read in place) against the map, on the device.
         pose: a float64 CUDA [7] tensor (a trajectory row) is updated IN PLACE and returned; anything else is copied to
         the device first.  -> (pose [7], info [iters, 8]) device tensors; info may be preallocated.  metric None:
-        "plane" for points with normals (F >= 7), else "point".  No host read, nothing allocated after a reserve()
-        when info is given."""
+        "plane" for points with normals (F >= 7), else "point".  robust_scale > 0: Geman-McClure weights
+        (rslo_map_register_w).  No host read, nothing allocated after a reserve() when info is given."""
         from rslo_amd import capi
         _check_register(iters, tol_t, tol_r)
         md = _max_dist_of(max_dist, self.voxel_size)
+        scale = check_scale(robust_scale)
         self.reserve(points.shape[0])
         pose = self._identity.clone() if pose is None else self._pose(pose)
         info = capi.map_register(self._buf, points, pose, self.voxel_size, iters, _metric_of(metric, points.shape[1]), md,
-                                 min_hits, damping, min_pairs, tol_t, tol_r, info=info, ws=self._reg_ws)
+                                 min_hits, damping, min_pairs, tol_t, tol_r, info=info, ws=self._reg_ws,
+                                 robust_scale=scale if scale else None)
         return pose, info
 
     def reserve_prune(self):
@@ -612,3 +725,130 @@ class VoxelMap:
     def save_ply(self, path, min_hits=1):
         rows, _, hits = self.points(min_hits)
         write_ply(path, rows.cpu().numpy(), hits.cpu().numpy())
+
+
+# The default robust factor of default_schedule: scale = factor * voxel of the stage, no weights on the coarsest level.
+# Chosen from the registration-alone pass of profiles/NOTES.md "Coarse-to-fine robust registration".
+DEFAULT_ROBUST_FACTOR = 0.5
+
+
+class _PyramidBase:
+    """What MapPyramidRef and MapPyramid share: a list of maps, coarse to fine, that receive the same calls."""
+
+    def _each(self, name, *args, **kw):
+        return [getattr(m, name)(*args, **kw) for m in self.levels]
+
+    def insert(self, points, pose=None):
+        self._each("insert", points, pose)
+
+    def reset(self):
+        self._each("reset")
+
+    def prune(self, center=None, radius=None, min_hits=1, grace=0):
+        check_prune(center, radius, min_hits, grace)      # before any level is written
+        self._each("prune", center, radius, min_hits, grace)
+
+    def stats(self):
+        return self._each("stats")
+
+    def prune_stats(self):
+        return self._each("prune_stats")
+
+    def points(self, *args, **kw):
+        return self.levels[-1].points(*args, **kw)
+
+    def save_ply(self, path, min_hits=1):
+        self.levels[-1].save_ply(path, min_hits)
+
+    def lookup(self, points, pose=None, return_tags=False):
+        return self.levels[-1].lookup(points, pose, return_tags)
+
+    def overlap(self, points, pose=None):
+        return self.levels[-1].overlap(points, pose)
+
+    def default_schedule(self, iters_per_level=4, robust_factor=None):
+        """One stage per level, coarse to fine: (level, iters_per_level, None, scale) with scale = robust_factor * voxel
+        of the level, and no weights (0.0) on the coarsest level of a pyramid of more than one level: far from the
+        answer the weights shut out the very pairs that pull the pose in.  robust_factor None: DEFAULT_ROBUST_FACTOR."""
+        f = DEFAULT_ROBUST_FACTOR if robust_factor is None else float(robust_factor)
+        n = len(self.levels)
+        return [(k, int(iters_per_level), None, 0.0 if (k == 0 and n > 1) else f * self.voxel_sizes[k]) for k in range(n)]
+
+    def _stages(self, schedule):
+        return check_schedule(self.default_schedule() if schedule is None else schedule, self.voxel_sizes)
+
+
+class MapPyramidRef(_PyramidBase):
+    """The numpy restatement of a pyramid: one VoxelMapRef per voxel size, ordered coarse to fine (.levels[k]).
+    insert / reset / prune / stats / prune_stats go to every level (stats: lists), points / save_ply / lookup / overlap
+    address the finest; register runs a schedule (module docstring)."""
+
+    def __init__(self, voxel_sizes=(0.8, 0.4, 0.2), capacity=None, min_range=0.0, max_range=float("inf")):
+        self.voxel_sizes = _check_pyramid(voxel_sizes)      # (capacity: accepted for symmetry; the restatement has none)
+        self.levels = [VoxelMapRef(v, min_range, max_range) for v in self.voxel_sizes]
+
+    def reserve(self, n_points):
+        pass
+
+    def reserve_prune(self):
+        pass
+
+    def register(self, points, pose, schedule=None, metric=None, min_hits=1, damping=0.0, min_pairs=50, tol_t=0.0,
+                 tol_r=0.0, info=None):
+        """-> (pose [7] float64, info [sum of iters, 8]): the stages as successive VoxelMapRef.register calls."""
+        stages = self._stages(schedule)
+        _check_register(1, tol_t, tol_r)
+        pose = np.array(pose, dtype=np.float64).reshape(7)
+        rows = []
+        for k, (level, iters, md, scale) in enumerate(stages):
+            pose, part = self.levels[level].register(points, pose, iters, metric, md, min_hits, damping, min_pairs,
+                                                     tol_t, tol_r, robust_scale=scale)
+            part[:, 5], part[:, 6] = float(k), float(level)
+            rows.append(part)
+        rows = np.concatenate(rows)
+        if info is not None:
+            info[...] = rows
+            rows = info
+        return pose, rows
+
+
+class MapPyramid(_PyramidBase):
+    """The device pyramid: one VoxelMap per voxel size, ordered coarse to fine (.levels[k]); capacity is an int or one
+    value per level.  Every level is filled by the existing insert and pruned by the existing prune (one call per
+    level); register is ONE call of rslo_map_register_sched over all levels: no host read, nothing allocated after
+    reserve() when info is given, a launch count fixed by the schedule."""
+
+    def __init__(self, voxel_sizes=(0.8, 0.4, 0.2), capacity=1 << 22, device="cuda", min_range=0.0,
+                 max_range=float("inf")):
+        self.voxel_sizes, caps = _check_pyramid(voxel_sizes, capacity)
+        self.levels = [VoxelMap(v, c, device, min_range, max_range) for v, c in zip(self.voxel_sizes, caps)]
+        self.device = self.levels[-1].device
+
+    def reserve(self, n_points):
+        self._each("reserve", n_points)
+
+    def reserve_prune(self):
+        self._each("reserve_prune")
+
+    def prune(self, center=None, radius=None, min_hits=1, grace=0):
+        import torch
+        check_prune(center, radius, min_hits, grace)
+        if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
+            center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(-1)[:3].copy()).to(self.device)
+        self._each("prune", center, radius, min_hits, grace)
+
+    def register(self, points, pose, schedule=None, metric=None, min_hits=1, damping=0.0, min_pairs=50, tol_t=0.0,
+                 tol_r=0.0, info=None):
+        """The stages of `schedule` (None: default_schedule()) in order, on the device.  pose: a float64 CUDA [7] tensor
+        is updated IN PLACE and returned, anything else is copied to the device first.  -> (pose [7], info [sum of
+        iters, 8]) device tensors; info may be preallocated."""
+        from rslo_amd import capi
+        stages = self._stages(schedule)
+        _check_register(1, tol_t, tol_r)
+        fine = self.levels[-1]
+        self.reserve(points.shape[0])
+        pose = fine._identity.clone() if pose is None else fine._pose(pose)
+        info = capi.map_register_sched([m._buf for m in self.levels], self.voxel_sizes, stages, points, pose,
+                                       _metric_of(metric, points.shape[1]), min_hits, damping, min_pairs, tol_t, tol_r,
+                                       info=info, ws=fine._reg_ws)
+        return pose, info

@@ -7,6 +7,7 @@
     python scripts/odometry_stream.py --raw --scans 200 --warmup 20 [--out profiles/odometry_stream_raw.json]
     python scripts/odometry_stream.py --map --scans 200 --warmup 20 [--map-out map.ply] [--out profiles/odometry_stream_map.json]
     python scripts/odometry_stream.py --refine --scans 200 --warmup 20 [--refine-iters 3] [--out profiles/odometry_stream_refine.json]
+    python scripts/odometry_stream.py --refine --refine-levels 0.8 0.4 0.2 --refine-iters-per-level 4 [--refine-robust 0.5] [--out profiles/odometry_stream_pyramid.json]
     python scripts/odometry_stream.py --map --local-map-radius 100 --local-map-every 10 --scans 200 --warmup 20 [--out profiles/odometry_stream_local_map.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
@@ -29,6 +30,12 @@ registered against the map before it is inserted), timed beside the --map loop o
 alone" pass on the drive: the prediction of scan i is refined[i-1] o (true relative motion o a fixed seeded error of
 about 5 cm and 0.1 degrees); pose error against synthetic.sequence_pose before and after VoxelMap.register, pairs per
 scan and ms per register call from device events (--seed must be the drive's).
+--refine-levels V0 V1 .. (coarse to fine; implies --refine) [--refine-iters-per-level N] [--refine-robust F]: one more
+runner loop with voxel_map=MapPyramid(levels) and its default schedule (N iterations per level, scale = F * voxel below
+the coarsest level; F omitted: the library's default), ms per scan beside the --refine loop of the same process; the
+inserts alone into the pyramid beside those into the one map; and the registration-alone pass once per setting -- the
+parent's (VoxelMap.register, --refine-iters), the same with robust weights, and the schedule with factors 0, 0.5 and 1
+-- with the same seeded disturbance: ms per call and pose error before / after for each.
 --local-map-radius R [--local-map-every K] (implies --map): the --map loop, the --refine loop when given, and the
 inserts alone under the drive's own poses once more with the rolling local map (VoxelMap.prune about the scan's pose
 every K scans; rslo_map_prune in csrc/map.hip), each beside the same loop without pruning in this process: ms per scan,
@@ -111,6 +118,10 @@ def main():
     ap.add_argument("--map-out", default=None, help="write the map as a binary PLY")
     ap.add_argument("--refine", action="store_true", help="also run the runner with scan-to-map refinement (implies --map)")
     ap.add_argument("--refine-iters", type=int, default=3, help="Gauss-Newton iterations per scan")
+    ap.add_argument("--refine-levels", type=float, nargs="+", default=None,
+                    help="voxel sizes of a map pyramid, coarse to fine: also run the coarse-to-fine loops (implies --refine)")
+    ap.add_argument("--refine-iters-per-level", type=int, default=4)
+    ap.add_argument("--refine-robust", type=float, default=None, help="robust factor of the default schedule")
     ap.add_argument("--local-map-radius", type=float, default=None,
                     help="also run the map loops with a rolling local map of this radius in metres (implies --map)")
     ap.add_argument("--local-map-every", type=int, default=10, help="prune every K scans")
@@ -121,6 +132,7 @@ def main():
     ap.add_argument("--save-scans", default=None, help="write the drive's scans to this .npz and stop")
     ap.add_argument("--load-scans", default=None, help="read the scans from a --save-scans file (profiled runs)")
     args = ap.parse_args()
+    args.refine = args.refine or args.refine_levels is not None
     args.map = args.map or args.refine or args.local_map_radius is not None
     if args.launches:
         res = launches(args.launches[0], args.launches[1], args.scans_a, args.scans_b)
@@ -313,6 +325,8 @@ def main():
             res["map_ply_bytes"] = os.path.getsize(args.map_out)
     if args.refine:
         res.update(refine_report(args, net, scans, timed, res["map_ms_per_scan"]))
+    if args.refine_levels is not None:
+        res.update(pyramid_report(args, net, scans, timed, res))
     if args.local_map_radius is not None:
         res.update(local_map_report(args, net, scans, timed, res))
     line = json.dumps(res)
@@ -492,13 +506,28 @@ def refine_report(args, net, scans, timed, map_ms):
     out["refine_map_stats"] = rmap.stats()
     runner.close()
     # registration alone: the drive's own motion, disturbed by a fixed seeded error, corrected against the map so far
+    rmap.reserve(max(s.shape[0] for s in scans))
+    out.update(register_alone(args, scans, rmap, lambda s, pose: rmap.register(s, pose, iters=K)[1], "register_alone"))
+    out["register_alone_ms_per_iteration"] = round(out["register_alone_ms_per_call"] / K, 4)
+    return out
+
+
+def register_alone(args, scans, target, call, name, pairs_row=0):
+    """The registration-alone pass: the prediction of scan i is refined[i-1] o (true relative motion o a seeded error of
+    about 5 cm and 0.1 degrees; the same draws for every caller); call(scan, pose) corrects pose in place against
+    `target` (a VoxelMap or a MapPyramid, reset here) and returns its info rows; the scan is inserted under the result."""
+    import numpy as np
+    import torch
+    from rslo_amd import synthetic
+    dev = scans[0].device
+    W, N = args.warmup, args.scans
+    out = {}
     true = [synthetic.sequence_pose(i, args.seed) for i in range(W + N)]
     rng = np.random.default_rng(777)
-    rmap.reset()
-    rmap.reserve(max(s.shape[0] for s in scans))
+    target.reset()
     pose = torch.zeros((7,), dtype=torch.float64, device=dev)
     refined = true[0].copy()
-    rmap.insert(scans[0], refined)
+    target.insert(scans[0], refined)
     before, after, pairs, status, ms = [], [], [], [], []
     for i in range(1, W + N):
         axis = rng.normal(size=3)
@@ -509,28 +538,85 @@ def refine_report(args, net, scans, timed, map_ms):
         pose.copy_(torch.from_numpy(pred))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        _, info = rmap.register(scans[i], pose, iters=K)
+        info = call(scans[i], pose)
         e1.record()
         refined = pose.cpu().numpy()                # (a host read per scan: this pass times register alone)
-        rmap.insert(scans[i], pose)
+        target.insert(scans[i], pose)
         before.append(_pose_error(pred, true[i]))
         after.append(_pose_error(refined, true[i]))
         info = info.cpu().numpy()
-        pairs.append(float(info[0, 1]))
+        pairs.append(float(info[pairs_row, 1]))
         status.append(info[:, 0].tolist())
         if i >= W:
             ms.append(e0.elapsed_time(e1))
     before, after = np.array(before), np.array(after)
-    out["register_alone_ms_per_call"] = round(float(np.mean(ms)), 4)
-    out["register_alone_ms_per_iteration"] = round(float(np.mean(ms)) / K, 4)
-    out["register_alone_pairs_per_scan"] = round(float(np.mean(pairs)), 1)
-    out["register_alone_status_counts"] = [int((np.array(status) == k).sum()) for k in range(4)]
-    for name, e in (("before", before), ("after", after)):
-        out["register_alone_%s_trans_m_mean" % name] = round(float(e[:, 0].mean()), 5)
-        out["register_alone_%s_trans_m_max" % name] = round(float(e[:, 0].max()), 5)
-        out["register_alone_%s_rot_deg_mean" % name] = round(float(e[:, 1].mean()), 5)
-        out["register_alone_%s_rot_deg_max" % name] = round(float(e[:, 1].max()), 5)
-    out["register_alone_map_stats"] = rmap.stats()
+    out[name + "_ms_per_call"] = round(float(np.mean(ms)), 4)
+    out[name + "_pairs_per_scan"] = round(float(np.mean(pairs)), 1)
+    out[name + "_status_counts"] = [int((np.array(status) == k).sum()) for k in range(4)]
+    for which, e in (("before", before), ("after", after)):
+        out["%s_%s_trans_m_mean" % (name, which)] = round(float(e[:, 0].mean()), 5)
+        out["%s_%s_trans_m_max" % (name, which)] = round(float(e[:, 0].max()), 5)
+        out["%s_%s_rot_deg_mean" % (name, which)] = round(float(e[:, 1].mean()), 5)
+        out["%s_%s_rot_deg_max" % (name, which)] = round(float(e[:, 1].max()), 5)
+    out[name + "_map_stats"] = target.stats()
+    return out
+
+
+def pyramid_report(args, net, scans, timed, res):
+    """Coarse-to-fine robust registration beside the figures of the --refine loop of this process (already in `res`)."""
+    import torch
+    from rslo_amd import inference, mapping, synthetic
+    dev = scans[0].device
+    W, N, K, per = args.warmup, args.scans, args.refine_iters, args.refine_iters_per_level
+    levels = tuple(args.refine_levels)
+    pyr = mapping.MapPyramid(levels, args.map_capacity, dev)
+    sched = pyr.default_schedule(per, args.refine_robust)
+    out = {"pyramid_levels": list(levels), "pyramid_schedule": [list(st) for st in sched]}
+    runner = inference.OdometryRunner(net, voxel_map=pyr, refine=dict(schedule=sched))
+    pend = {}
+
+    def run(rng):
+        rng = list(rng)
+        for k, i in enumerate(rng):
+            if i not in pend:
+                pend[i] = runner.submit(scans[i])
+            if k + 1 < len(rng) and rng[k + 1] not in pend:
+                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
+            runner.run(pend.pop(i))
+    out["pyramid_refine_ms_per_scan"], out["pyramid_refine_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+    out["pyramid_refine_minus_refine_ms_per_scan"] = round(out["pyramid_refine_ms_per_scan"] - res["refine_ms_per_scan"], 3)
+    info = runner.refine_info().cpu().numpy()
+    out["pyramid_refine_runner_status_counts"] = [int((info[:, :, 0] == k).sum()) for k in range(4)]
+    out["pyramid_refine_map_stats"] = pyr.stats()
+    runner.close()
+    # the inserts alone under the drive's own poses: every level of the pyramid beside its finest level alone
+    true = [torch.from_numpy(synthetic.sequence_pose(i, args.seed)).to(dev) for i in range(W + N)]
+    pyr.reserve(max(s.shape[0] for s in scans))
+    for name, target in (("pyramid_finest_insert_alone_ms_per_scan", pyr.levels[-1]), ("pyramid_insert_alone_ms_per_scan", pyr)):
+        pyr.reset()
+        for i in range(W):
+            target.insert(scans[i], true[i])
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(W, W + N):
+            target.insert(scans[i], true[i])
+        e1.record()
+        e1.synchronize()
+        out[name] = round(e0.elapsed_time(e1) / N, 4)
+    out["pyramid_true_pose_stats"] = pyr.stats()
+    # the registration-alone pass, the same seeded disturbance for every setting
+    single = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+    single.reserve(max(s.shape[0] for s in scans))
+    scale = (mapping.DEFAULT_ROBUST_FACTOR if args.refine_robust is None else args.refine_robust) * args.map_voxel
+    out["weighted_scale"] = scale
+    out.update(register_alone(args, scans, single, lambda s, p: single.register(s, p, iters=K)[1], "parent_alone"))
+    out.update(register_alone(args, scans, single, lambda s, p: single.register(s, p, iters=K, robust_scale=scale)[1],
+                              "weighted_alone"))
+    for f in (0.0, 0.5, 1.0):
+        sch = pyr.default_schedule(per, f)
+        out.update(register_alone(args, scans, pyr, lambda s, p: pyr.register(s, p, sch)[1], "pyramid_alone_f%g" % f,
+                                  pairs_row=-1))
     return out
 
 
