@@ -1087,6 +1087,74 @@ RSLO_API int rslo_map_register_sched(const void *const *maps /*[n_levels] host*/
                                      double damping, int min_pairs, double tol_t, double tol_r,
                                      double *info /*[sum of iters,8]*/, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Place recognition (csrc/places.hip): a Scan Context descriptor per scan (Kim & Kim, "Scan Context: Egocentric Spatial
+ * Descriptor for Place Recognition within 3D Point Cloud Map", IROS 2018), a device-resident database of descriptors
+ * and a two-stage search for the stored scans that look like a query.  The rules are recalled from the paper and fixed
+ * here; rslo_amd/places.py (ScanContextRef, PlaceDBRef) restates them in float64 numpy and the tests compare bit for
+ * bit.  All arithmetic is IEEE double with contraction off unless a rule says float.  No transcendental function
+ * decides a bin: device and host math libraries do not agree to the bit.
+ *
+ * Parameters: R rings (1..64), S sectors (3..128), max_range > 0, z_offset (float).
+ * Tables, made ONCE by the caller and handed to the device and to the restatement alike: `tables` is
+ * 2*(S+1) + (R+1) doubles = dirs[k] = (cos(2 pi k / S), sin(2 pi k / S)) for k = 0..S with dirs[S] = dirs[0], followed
+ * by edge2[k] = (k * max_range / R)^2 for k = 0..R.
+ *
+ * Descriptor D, float32 [R, S], of one scan in the sensor frame.  For every point i:
+ *   1. x, y = double(p.x), double(p.y);
+ *   2. a coordinate of xyz that is not finite drops the point (dropped_invalid);
+ *   3. r2 = x*x + y*y; the point is dropped (dropped_range) unless r2 > 0 and r2 < edge2[R];
+ *   4. ring = the number of k in 1..R-1 with r2 >= edge2[k];
+ *   5. c_k = dirs[k].x*y - dirs[k].y*x; sector = the smallest k in 0..S-1 with c_k >= 0 and c_{k+1} < 0; none: dropped
+ *      (dropped_range).  The kernel guesses k from atan2f and confirms both conditions on the same computed c values
+ *      (also for the guess's two neighbours); a guess that is not confirmed falls back to the scan over k;
+ *   6. v = p.z + z_offset in float; the point is dropped (dropped_low) unless v > 0;
+ *   7. D[ring, sector] = max(D[ring, sector], v).  Empty bins are 0.  n_points counts the points that arrive here.
+ * With it go key[r] (int32) = the number of sectors of ring r with D > 0, and norm[j] (double) = sqrt of the sum over r
+ * ascending of double(D[r,j])^2.  counters4 = {n_points, dropped_invalid, dropped_range, dropped_low}, int64.
+ * Positive floats order as their bit patterns: the maximum is an integer maximum (per workgroup in LDS, then into the
+ * zeroed grid), which does not depend on arrival order.  Three launches (two for N == 0: an all-zero grid).
+ *
+ * Database: ONE caller-owned device allocation of rslo_place_bytes(capacity, R, S) bytes,
+ *   header (256 bytes) | D f32 [N, R, S] | norm f64 [N, S] | key i32 [N, R],   N = capacity, sections padded to 256 bytes.
+ * Header int64 words: [0] magic, [1] capacity, [2] R, [3] S, [4] n_entries, [5] dropped_full.  capacity (1 .. 2^24), R
+ * and S are fixed by rslo_place_reset; add and query take them again and do nothing on an allocation whose header
+ * says otherwise (never reset, or reset with other values).  rslo_place_add appends (D, key, norm) as entry number
+ * n_entries (read on the device); on a full database the entry is not stored and dropped_full counts it.  Two launches.
+ *
+ * Query with (D, key, norm) of a scan, exclude_recent >= 0, num_candidates C in 0..256, top_k in 1..16:
+ *   eligible: the entries with index < n_entries - exclude_recent;
+ *   stage 1 (C > 0): kd = sum over r of (key_q[r] - key_e[r])^2 in integers; the C eligible entries with the smallest
+ *     kd go on, ties to the lower index (composite key kd << 32 | index).  C == 0: every eligible entry goes on;
+ *   stage 2: for every shift s in 0..S-1, with j' = (j + s) % S: column j is valid when norm_q[j] > 0 and
+ *     norm_e[j'] > 0; dot_j = sum over r ascending of double(Dq[r,j]) * double(De[r,j']);
+ *     cos_j = dot_j / (norm_q[j] * norm_e[j']); d(s) = 1 - (sum of cos_j over the valid j, ascending) / n_valid, +inf
+ *     without a valid column.  The entry's distance is the smallest d(s), ties to the lowest s;
+ *   result: out double [top_k, 4], rows (entry index, distance, shift, (shift * 2 pi) / S) ordered by distance, then by
+ *     index; entries at +inf are not returned; unused rows are (-1, +inf, -1, 0).  Column 3 is the query's heading
+ *     relative to the entry.  No threshold is applied: acceptance is the caller's comparison.
+ * The S x S column dots are formed in double on the vector ALU, one workgroup per stage-2 entry; one thread per shift
+ * adds its wrapped diagonal in j order.  Selection compares integers (the ordered bit pattern of the distance, then
+ * the index).  Launches: 4 with C > 0, 2 with C == 0 (a grid of `capacity` workgroups); no flag between workgroups,
+ * no floating-point atomic, no host read, nothing allocated: capturable.
+ *
+ * Errors: RSLO_EINVAL (nothing is written) for R, S, capacity or a count outside its range, a null pointer, N < 0,
+ * stride_floats < 3, a z_offset that is not finite, db_bytes below rslo_place_bytes(capacity, R, S), a workspace that is
+ * null or not 8-byte aligned; RSLO_EWS for ws_bytes below rslo_place_query_ws_bytes(capacity).
+ * rslo_place_bytes / rslo_place_query_ws_bytes are host only and return 0 for arguments out of range.
+ * ------------------------------------------------------------------------------------ */
+RSLO_API size_t rslo_place_bytes(int64_t capacity, int R, int S);
+RSLO_API int rslo_place_reset(void *db, size_t db_bytes, int64_t capacity, int R, int S, void *stream);
+RSLO_API int rslo_place_describe(const float *points, int stride_floats, int N, int R, int S,
+                                 const double *tables /*[2*(S+1) + R+1]*/, float z_offset, float *D /*[R,S]*/,
+                                 int32_t *key /*[R]*/, double *norm /*[S]*/, int64_t *counters4, void *stream);
+RSLO_API int rslo_place_add(void *db, size_t db_bytes, int64_t capacity, int R, int S, const float *D,
+                            const int32_t *key, const double *norm, void *stream);
+RSLO_API size_t rslo_place_query_ws_bytes(int64_t capacity);
+RSLO_API int rslo_place_query(const void *db, size_t db_bytes, int64_t capacity, int R, int S, const float *Dq,
+                              const int32_t *keyq, const double *normq, int64_t exclude_recent, int num_candidates,
+                              int top_k, double *out /*[top_k,4]*/, void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

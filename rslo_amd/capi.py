@@ -210,6 +210,12 @@ SIGNATURES = {
                                       C.c_double, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
     "rslo_map_register_sched": (C.c_int, [_vp, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _i, _i, C.c_double, _i,
                                           C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_place_bytes": (_sz, [_i64, _i, _i]),
+    "rslo_place_reset": (C.c_int, [_vp, _sz, _i64, _i, _i, _vp]),
+    "rslo_place_describe": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp, _vp, _vp]),
+    "rslo_place_add": (C.c_int, [_vp, _sz, _i64, _i, _i, _vp, _vp, _vp, _vp]),
+    "rslo_place_query_ws_bytes": (_sz, [_i64]),
+    "rslo_place_query": (C.c_int, [_vp, _sz, _i64, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -2230,3 +2236,60 @@ def pose_targets(res_r, res_t, R_pred, T_pred, with_tq=False):
                                     _ptr(R_pred, torch.float32, "R_pred"), _ptr(T_pred, torch.float32, "T_pred"), B,
                                     _ptr(rot), _ptr(trans), _ptr(tq), _stream()), "rslo_pose_targets_tq")
     return (rot, trans, tq) if with_tq else (rot, trans)
+
+
+# --------------------------------------------------------------------------------------
+# place recognition (csrc/places.hip); the owning class is rslo_amd/places.py PlaceDB
+# --------------------------------------------------------------------------------------
+PLACE_HDR_ENTRIES = 4     # int64 words of a database's header: n_entries, dropped_full (include/rslo_hip.h)
+PLACE_COUNTERS = ("n_points", "dropped_invalid", "dropped_range", "dropped_low")
+
+
+def place_bytes(capacity, R, S):
+    """rslo_place_bytes: bytes of a database of `capacity` entries of [R, S] descriptors; 0 for arguments out of range."""
+    return int(lib().rslo_place_bytes(int(capacity), int(R), int(S)))
+
+
+def place_reset(buf, capacity, R, S):
+    """rslo_place_reset on the current stream: writes the header of an empty database."""
+    ptr, nbytes = _map_buf(buf)
+    _chk(lib().rslo_place_reset(ptr, nbytes, int(capacity), int(R), int(S), _stream()), "rslo_place_reset")
+
+
+def place_describe(points, R, S, tables, z_offset, D, key, norm, counters):
+    """rslo_place_describe: the Scan Context descriptor of one scan (fp32 CUDA [P, F >= 3], read in place) into D fp32
+    [R, S], key int32 [R], norm float64 [S] and counters int64 [4], on the current stream.  tables: float64 CUDA
+    [2*(S+1) + R+1] (places.tables).  No host read."""
+    src, stride = _rows3(points, "points")
+    if tables.numel() != 2 * (S + 1) + R + 1 or D.numel() != R * S or key.numel() != R or norm.numel() != S \
+            or counters.numel() != 4:
+        raise RsloHipError("place_describe: tables, D, key, norm or counters do not have the sizes of R = %d, S = %d" % (R, S))
+    _chk(lib().rslo_place_describe(src, stride, int(points.shape[0]), int(R), int(S), _ptr(tables, torch.float64, "tables"),
+                                   float(z_offset), _ptr(D, torch.float32, "D"), _ptr(key, torch.int32, "key"),
+                                   _ptr(norm, torch.float64, "norm"), _ptr(counters, torch.int64, "counters"), _stream()),
+         "rslo_place_describe")
+
+
+def place_add(buf, capacity, R, S, D, key, norm):
+    """rslo_place_add: append one descriptor on the current stream (a full database counts it in dropped_full)."""
+    ptr, nbytes = _map_buf(buf)
+    if D.numel() != R * S or key.numel() != R or norm.numel() != S:
+        raise RsloHipError("place_add: D, key or norm do not have the sizes of R = %d, S = %d" % (R, S))
+    _chk(lib().rslo_place_add(ptr, nbytes, int(capacity), int(R), int(S), _ptr(D, torch.float32, "D"),
+                              _ptr(key, torch.int32, "key"), _ptr(norm, torch.float64, "norm"), _stream()), "rslo_place_add")
+
+
+def place_query_ws(capacity, device):
+    """a workspace for place_query on a database of `capacity` entries"""
+    return torch.empty((max(int(lib().rslo_place_query_ws_bytes(int(capacity))), 8) // 8,), dtype=torch.int64, device=device)
+
+
+def place_query(buf, capacity, R, S, D, key, norm, exclude_recent, num_candidates, top_k, out, ws):
+    """rslo_place_query on the current stream: out float64 [top_k, 4] rows (entry, distance, shift, heading)."""
+    ptr, nbytes = _map_buf(buf)
+    if D.numel() != R * S or key.numel() != R or norm.numel() != S or out.numel() != 4 * int(top_k):
+        raise RsloHipError("place_query: D, key, norm or out do not have the sizes of R = %d, S = %d, top_k = %d" % (R, S, top_k))
+    _chk(lib().rslo_place_query(ptr, nbytes, int(capacity), int(R), int(S), _ptr(D, torch.float32, "D"),
+                                _ptr(key, torch.int32, "key"), _ptr(norm, torch.float64, "norm"), int(exclude_recent),
+                                int(num_candidates), int(top_k), _ptr(out, torch.float64, "out"),
+                                _ptr(ws, torch.int64, "ws"), ws.numel() * 8, _stream()), "rslo_place_query")

@@ -270,10 +270,20 @@ class OdometryRunner:
       with refine, else the open-loop one (VoxelMap.prune; include/rslo_hip.h "Rolling local map").  The decision is
       the host's own scan count: no device read.  The workspace (about one more table) is reserved here, so run()
       allocates nothing.  trajectory() / relative() are untouched.  None (the default): the map only grows.
+    * Place recognition: places=PlaceDB(...) (rslo_amd/places.py, csrc/places.hip) with
+      loop=dict(exclude_recent=50, num_candidates=10, top_k=1) (these defaults; keyword arguments of PlaceDB.query):
+      behind everything above, run() describes the tensor passed to submit() (sensor frame, its first three columns),
+      queries the database with that descriptor into row n of loop_candidates() ([n, top_k, 4] float64 on the device:
+      entry, distance, shift, heading), then adds it -- in that order, so a scan never finds itself; exclude_recent
+      keeps its neighbours out.  Nine launches with candidates (seven with num_candidates=0) on the caller's stream, no
+      synchronisation, nothing allocated.  No threshold is applied and nothing is corrected: verification and the pose
+      graph are the caller's.  reset() empties the database.  Unknown keys, or loop without places, are errors at
+      construction.  None (the default): no database, today's bits.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
-                 normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None):
+                 normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None,
+                 places=None, loop=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -283,6 +293,21 @@ class OdometryRunner:
                 refine, info_rows = mapping.check_refine(refine, voxel_map)
             except ValueError as e:
                 raise capi.RsloHipError("OdometryRunner: %s" % e)
+        if loop is not None and places is None:
+            raise capi.RsloHipError("OdometryRunner: loop needs places=PlaceDB(...) to search")
+        if places is not None:
+            from rslo_amd import places as places_mod
+            loop = dict(loop or {})
+            unknown = set(loop) - {"exclude_recent", "num_candidates", "top_k"}
+            if unknown:
+                raise capi.RsloHipError("OdometryRunner: loop takes exclude_recent, num_candidates and top_k; got %s"
+                                        % sorted(unknown))
+            try:
+                ex, nc, tk = places_mod.check_query(loop.get("exclude_recent", 50), loop.get("num_candidates", 10),
+                                                    loop.get("top_k", 1))
+            except ValueError as e:
+                raise capi.RsloHipError("OdometryRunner: %s" % e)
+            loop = dict(exclude_recent=ex, num_candidates=nc, top_k=tk)
         self.normals = normals
         self.normal_radius, self.normal_max_nn = float(normal_radius), int(normal_max_nn)
         if normals == "estimate" and not (3 <= self.normal_max_nn <= 32 and self.normal_radius > 0):
@@ -359,6 +384,12 @@ class OdometryRunner:
                              grace=int(local_map.get("grace", 0)))
             self.local_map = local_map
             voxel_map.reserve_prune()                   # run() must not allocate
+        self.places, self.loop = places, loop
+        if places is not None:
+            if places.device != dev:
+                raise capi.RsloHipError("OdometryRunner: the place database lives on %s, the runner on %s" % (places.device, dev))
+            places.reserve(int(point_capacity))         # run() must not allocate
+            self._loop = torch.zeros((self.capacity, loop["top_k"], 4), dtype=torch.float64, device=dev)
         self.stats = {"scans": 0, "encoder_runs": 0, "head_replays": 0, "head_eager": 0, "captures": 0,
                       "weight_refreshes": 0}
 
@@ -374,11 +405,12 @@ class OdometryRunner:
             if cloud.shape[0] > self.encoder.point_capacity:
                 raise capi.RsloHipError("OdometryRunner.submit: the scan exceeds point_capacity = %d"
                                         % self.encoder.point_capacity)
-        if self.voxel_map is not None and not (torch.is_tensor(cloud) and cloud.is_cuda and cloud.dtype == torch.float32
-                                               and cloud.dim() == 2):
-            raise capi.RsloHipError("OdometryRunner.submit: a runner with a voxel map takes one fp32 CUDA [P, F] tensor")
+        keep = self.voxel_map is not None or self.places is not None
+        if keep and not (torch.is_tensor(cloud) and cloud.is_cuda and cloud.dtype == torch.float32 and cloud.dim() == 2):
+            raise capi.RsloHipError("OdometryRunner.submit: a runner with a voxel map%s takes one fp32 CUDA [P, F] tensor"
+                                    % ("" if self.places is None else " or a place database"))
         h = self.encoder.submit(cloud)
-        h.source = cloud if self.voxel_map is not None else None
+        h.source = cloud if keep else None
         return h
 
     def _append_normals(self, scan, arena, k):
@@ -398,6 +430,14 @@ class OdometryRunner:
             self.voxel_map.reset()
         if self.refine is not None:
             self._count2.zero_()
+        if self.places is not None:
+            self.places.reset()
+
+    def loop_candidates(self):
+        """[n, top_k, 4] fp64 device rows (places=...): PlaceDB.query's result of every scan against the scans before it."""
+        if self.places is None:
+            raise capi.RsloHipError("OdometryRunner.loop_candidates: the runner was built without places")
+        return self._loop[:min(self._n, self.capacity)]
 
     def refined_trajectory(self):
         """[n, 7] fp64 device rows of the refined chain (refine=...): row i = register(refined[i-1] o rel[i])."""
@@ -481,6 +521,10 @@ class OdometryRunner:
             lm = self.local_map
             self.voxel_map.prune((self._traj if self.refine is None else self._traj2)[n], lm["radius"], lm["min_hits"],
                                  lm["grace"])
+        if self.places is not None:         # describe -> query -> add: the scan is searched for before it is stored
+            self.places.describe(handle.source)
+            self.places.query(out=self._loop[n], **self.loop)
+            self.places.add()
         self._n += 1
         self.stats["scans"] += 1
         return self._rel[n], self._traj[n]

@@ -9,6 +9,7 @@
     python scripts/odometry_stream.py --refine --scans 200 --warmup 20 [--refine-iters 3] [--out profiles/odometry_stream_refine.json]
     python scripts/odometry_stream.py --refine --refine-levels 0.8 0.4 0.2 --refine-iters-per-level 4 [--refine-robust 0.5] [--out profiles/odometry_stream_pyramid.json]
     python scripts/odometry_stream.py --map --local-map-radius 100 --local-map-every 10 --scans 200 --warmup 20 [--out profiles/odometry_stream_local_map.json]
+    python scripts/odometry_stream.py --places --scans 200 --warmup 20 [--out profiles/odometry_stream_places.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -41,6 +42,12 @@ inserts alone under the drive's own poses once more with the rolling local map (
 every K scans; rslo_map_prune in csrc/map.hip), each beside the same loop without pruning in this process: ms per scan,
 prune_stats, the largest n_cells seen, dropped_full, ms per prune call from device events (and of a call that evicts
 nothing), and the insert time over the last 200 scans.
+--places: one more runner loop with a place database attached (rslo_amd.places.PlaceDB, csrc/places.hip: every run()
+describes its scan, searches the scans before it and adds it), ms per scan beside the plain runner loop of this process;
+describe, query (10 ring-key candidates, and exhaustive) and add alone under device events against the database of the
+whole drive; and a revisit pass: the drive's scans go into the database, then queries are made with synthetic.scan at
+earlier drive positions moved 0.7 m / 0.8 m with the heading reversed -- top-1 within 5 m, the distances of the true
+matches, and the smallest distance to any entry more than 10 m away (--seed must be the drive's).
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -125,6 +132,8 @@ def main():
     ap.add_argument("--local-map-radius", type=float, default=None,
                     help="also run the map loops with a rolling local map of this radius in metres (implies --map)")
     ap.add_argument("--local-map-every", type=int, default=10, help="prune every K scans")
+    ap.add_argument("--places", action="store_true", help="also run the runner with a place-recognition database attached")
+    ap.add_argument("--places-queries", type=int, default=20, help="revisit queries of the --places report")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -329,11 +338,116 @@ def main():
         res.update(pyramid_report(args, net, scans, timed, res))
     if args.local_map_radius is not None:
         res.update(local_map_report(args, net, scans, timed, res))
+    if args.places:
+        res.update(places_report(args, net, scans, timed, res))
     line = json.dumps(res)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def _revisit_scan(a):
+    from rslo_amd import synthetic
+    x, y, yaw, seed = a
+    return synthetic.scan(pose_xy=(x, y), yaw=yaw, scan_seed=seed)
+
+
+def places_report(args, net, scans, timed, res):
+    """--places: the runner with a place database, the three calls alone, and the revisit pass"""
+    import numpy as np
+    import torch
+    from rslo_amd import inference, places, synthetic
+    W, N = args.warmup, args.scans
+    dev = scans[0].device
+    out = {}
+    loop = dict(exclude_recent=50, num_candidates=10, top_k=1)
+    db = places.PlaceDB(capacity=max(1024, W + N), device=dev)
+    runner = inference.OdometryRunner(net, places=db, loop=loop)
+    pend = {}
+
+    def run(rng):
+        rng = list(rng)
+        for k, i in enumerate(rng):
+            if i not in pend:
+                pend[i] = runner.submit(scans[i])
+            if k + 1 < len(rng) and rng[k + 1] not in pend:
+                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
+            runner.run(pend.pop(i))
+    out["places_ms_per_scan"], out["places_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+    out["places_minus_runner_ms_per_scan"] = round(out["places_ms_per_scan"] - res["runner_ms_per_scan"], 3)
+    out["places_loop"] = loop
+    out["places_stats"] = db.stats()
+    cand = runner.loop_candidates().cpu().numpy()
+    found = cand[:, 0, 0] >= 0
+    out["places_runner_scans_with_a_candidate"] = int(found.sum())
+    out["places_runner_smallest_distance"] = float(cand[found, 0, 1].min()) if found.any() else None      # a drive without a loop
+    runner.close()
+
+    def events(fn, n):
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(n):
+            fn(i)
+        e1.record()
+        e1.synchronize()
+        return round(e0.elapsed_time(e1) / n, 4)
+
+    # the three calls alone: the database holds the whole drive while it is queried
+    descs = [tuple(t.clone() for t in db.describe(s)) for s in scans]
+    db.reset()
+    for d in descs:
+        db.add(*d)
+    row = torch.zeros((16, 4), dtype=torch.float64, device=dev)
+    out["places_entries_when_queried"] = W + N
+    out["places_describe_ms"] = events(lambda i: db.describe(scans[W + i]), N)
+    for C in (10, 0):
+        out["places_query_c%d_ms" % C] = events(
+            lambda i: db.query(*descs[W + i], exclude_recent=0, num_candidates=C, top_k=1, out=row[:1]), N)
+    side = places.PlaceDB(capacity=max(1024, W + N), device=dev)
+    out["places_add_ms"] = events(lambda i: side.add(*descs[W + i]), N)
+
+    # revisit: earlier drive positions, 0.7 m / 0.8 m off, heading reversed
+    n_q = max(1, min(args.places_queries, W + N))
+    idx = [int(v) for v in np.linspace(0, W + N - 1, n_q + 2)[1:-1]]
+    poses = [synthetic._sequence_xy_yaw(i, args.seed) for i in range(W + N)]
+    jobs = [(poses[i][0] + 0.7, poses[i][1] + 0.8, poses[i][2] + np.pi, 100000 + i) for i in idx]
+    if args.workers <= 1:
+        qscans = [_revisit_scan(j) for j in jobs]
+    else:
+        import multiprocessing as mp
+        with mp.get_context("spawn").Pool(args.workers) as pool:
+            qscans = pool.map(_revisit_scan, jobs)
+    ref = db.reference()
+    eD, enorm, ekey = db.entries()
+    for k in range(len(eD)):
+        ref.add(eD[k], ekey[k], enorm[k])
+    xy = np.array([p[:2] for p in poses])
+    hits = {10: 0, 0: 0}
+    true_d, false_d, shifts, ranks = [], [], [], []
+    for i, j, q in zip(idx, jobs, qscans):
+        D, key, norm = db.describe(torch.from_numpy(q).to(dev))
+        far = np.linalg.norm(xy - np.array(j[:2]), axis=1)
+        for C in (10, 0):
+            top = db.query(D, key, norm, exclude_recent=0, num_candidates=C, top_k=1).cpu().numpy()[0]
+            hits[C] += bool(top[0] >= 0 and far[int(top[0])] <= 5.0)
+            if C == 0:
+                shifts.append(int(top[2]))
+        d, _ = ref.distances(D.cpu().numpy(), norm.cpu().numpy(), np.arange(len(eD)))
+        true_d.append(float(d[far <= 5.0].min()))
+        false_d.append(float(d[far > 10.0].min()))
+        ranks.append(int((d < true_d[-1]).sum()))
+    out["places_revisit_queries"] = len(idx)
+    out["places_revisit_query_x_m"] = [round(j[0], 1) for j in jobs]      # (the street's walls and boxes end at x = 80 m)
+    out["places_revisit_top1_within_5m_c10"], out["places_revisit_top1_within_5m_c0"] = hits[10], hits[0]
+    out["places_revisit_true_match_distance_min_max"] = [round(min(true_d), 4), round(max(true_d), 4)]
+    out["places_revisit_true_match_distances"] = [round(v, 4) for v in true_d]
+    out["places_revisit_smallest_distance_beyond_10m"] = round(min(false_d), 4)
+    out["places_revisit_distances_beyond_10m"] = [round(v, 4) for v in false_d]
+    out["places_revisit_shifts"] = shifts
+    out["places_revisit_entries_closer_than_the_true_match"] = ranks
+    return out
 
 
 def local_map_report(args, net, scans, timed, res):
