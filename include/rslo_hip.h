@@ -1155,6 +1155,107 @@ RSLO_API int rslo_place_query(const void *db, size_t db_bytes, int64_t capacity,
                               const int32_t *keyq, const double *normq, int64_t exclude_recent, int num_candidates,
                               int top_k, double *out /*[top_k,4]*/, void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Pose graph (csrc/posegraph.hip): Gauss-Newton over a trajectory with loop edges, so that "scan j is at this pose
+ * relative to scan i" spreads its correction over the poses in between.  The float64 restatement is
+ * rslo_amd/posegraph.py (PoseGraphRef); the tests compare within rounding bounds, not bit for bit (device and host
+ * sum in different orders).  All arithmetic is IEEE double with contraction off.  How a loop measurement is made, and
+ * whether it is true, is the caller's business.
+ *
+ * Poses are [7] double rows (t, q wxyz), the trajectory's format.  compose(A, B) = (t_A + rotate(q_A, t_B), q_A (x) q_B),
+ * inverse of a unit pose = (-rotate(q*, t), q*), rotate and (x) by rslo_pose_chain's formulas; products are not
+ * renormalised.  rslo_pose_between writes out[k] = A[k]^-1 o B[k].
+ *
+ * Nodes: N (2 .. 65536).  traj0 [N,7] is the input trajectory, read only; poses [N,7] is the estimate, updated in place
+ * (a copy of traj0 on a first call).  Node 0 is fixed.  Vectors over the nodes are [N,6] rows (rho, phi) with row 0
+ * read as zero and written zero.
+ * Chain edge k (0 .. N-2) joins node k to node k+1 with Z_k = traj0[k]^-1 o traj0[k+1], computed from traj0, and weights
+ * (w_t, w_r): chain_w2_host, 2 HOST doubles, positive and finite, for the whole chain, or chain_w_dev, a DEVICE
+ * [N-1,2] array that wins when it is not NULL (an entry that is not positive and finite makes its edge singular).
+ * Loop edge l (L of them, 0 .. 4096): loops_ij int32 [L,2], loops_Z double [L,7] (the pose of j in the frame of i, its
+ * quaternion divided by its norm on read), loops_w double [L,2].  A row is skipped and counted when i < 0 (the unused
+ * row of rslo_place_query), j < 0, i or j >= N, i == j, a value of Z or w is not finite, the quaternion is zero or a
+ * weight is negative.  No edge is read on the host.
+ *
+ * Residual of an edge (i, j, Z): A = T_i^-1 o T_j, E = Z^-1 o A, s = +1 if q_E.w >= 0 else -1,
+ *   r = (w_t t_E, w_r 2 s vec(q_E)).
+ * Local parametrisation T' = T o (rho, phi): t' = t + rotate(q, rho), q' = (q (x) dq(phi)) / |.| with
+ * rslo_map_register's dq, its theta < 1e-12 branch included.
+ * Jacobians, G = s (q_E.w I + [vec q_E]x): d r_t/d rho_j = R_E, d r_r/d phi_j = G, d r_t/d rho_i = -R_Z^T,
+ * d r_t/d phi_i = R_Z^T [t_A]x, d r_r/d phi_i = -G R_A^T, all other blocks zero, rows scaled by the weights.  R(q) is
+ * the matrix of the unit-quaternion formula.
+ * Robust weight, loop edges only: e = r.r, s2 = scale*scale, u = s2 / (s2 + e), rho = u*u; H += rho J^T J,
+ * g += rho J^T r, cost += rho e; scale == 0: rho = 1; a bad scale is refused by rslo_map_register_w's rule.  Chain
+ * edges are never down-weighted, so the preconditioner stays exact.
+ *
+ * One Gauss-Newton iteration: linearise at poses; H = H_chain + H_loops + damping I over nodes 1 .. N-1; solve
+ * H x = -g by conjugate gradients preconditioned with M = H_chain = J_c^T J_c, at most cg_iters (1 .. 256) iterations,
+ * stopping when r.z <= cg_tol^2 (r.z)_0; update every pose.  J_c is block lower-bidiagonal with A_k = W dr/d delta_k
+ * and B_k = W dr/d delta_{k+1} = diag(w_t R_E, w_r G), whose inverse is closed form
+ * (G^-1 = (w w I - w [v]x + v v^T) / (s w (w w + v.v)) for q_E = (w, v)).  M^-1 r: backward
+ * y_{m-1} = B_{m-1}^-T (r_m - A_m^T y_m), then forward z_{k+1} = B_k^-1 (y_k - A_k z_k).
+ * CG stops WITHOUT applying the iteration when p.Ap is not a positive finite number; x so far is the step.  A step that
+ * is entirely zero for that reason, a step that is not finite, and a singular B_k (q_E.w == 0 on a chain edge) give
+ * status 2 and leave the poses untouched.  g == 0 (no usable loop on a first call, or a stationary point) is a zero
+ * step with status 0 and 0 CG iterations.
+ * info double [gn_iters, 8], row = {status, loops used, cost at the linearisation point, CG iterations run,
+ * sqrt(r.z / (r.z)_0) at the stop, max_k |rho_k|, max_k |phi_k|, loops skipped}.  status 0: step taken; 2: failed as
+ * above; 3: skipped because an earlier iteration had max|rho| < tol_t and max|phi| < tol_r (the row is {3, 0, ...});
+ * the flag lives in the workspace, as in rslo_map_register.
+ *
+ * Kernels.  Per Gauss-Newton iteration three launches: (1) parallel over all edges: one record of
+ * RSLO_PG_EDGE_DOUBLES doubles per edge, chain edges first, then loops: r[6], rho, flag (1 used, 0 skipped, 2 singular
+ * chain edge), the 3 x 3 blocks A_tt, A_tr, A_rr, B_tt, B_rr row-major (A = [[A_tt, A_tr], [0, A_rr]] acts on node i,
+ * B = diag(B_tt, B_rr) on node j), the gradient parts rho A^T r and rho B^T r, e, and for a chain edge B^-1's two
+ * blocks; (2) ONE workgroup of 1024 threads: the gradient per node, then the whole preconditioned CG with its loop and
+ * early stop inside the kernel; (3) parallel over the nodes: the update.  Sums into a node come in a fixed order, chain
+ * edge n-1, chain edge n, then the loops at that node by ascending index; dot products are one fixed tree; no
+ * floating-point atomic: a second call gives the same bits.  The order costs one workgroup barrier per "round": a loop
+ * is added in the round of its rank among the used loops at the same node, so every H x and every gradient sum runs
+ * 1 + (the largest number of used loops that share one node other than node 0) rounds.  Loops spread over the
+ * trajectory cost one or two; L loops onto one node cost L rounds per CG iteration, up to 4096 x cg_iters x gn_iters
+ * barriers in one call -- slow, not wrong.  The fixed node 0 receives no sum and counts no round.  The chain recurrences are scanned: each thread owns a
+ * contiguous segment of ceil((N-1) / 1024) edges, runs it with zero input, a scan over the segment summaries with the
+ * segments' transfer matrices (made once per Gauss-Newton iteration) gives every segment's input, and a second local
+ * pass runs it with that input: dependent depth 2 * segment + log2(segments).
+ * No host read, nothing allocated, 3 * gn_iters launches whatever happens: capturable.
+ *
+ *   rslo_posegraph_ws_bytes   host only; 0 for N or L out of range.
+ *   rslo_posegraph_optimize   gn_iters 1 .. 32.
+ *   rslo_posegraph_cost       out4 = {cost, chain part, loops used, loops skipped}.  Two launches.
+ *   rslo_posegraph_linearize  leaves the linearisation at `poses` in the workspace; edges_out (may be NULL)
+ *                             [(N-1+L), RSLO_PG_EDGE_DOUBLES], g_out (may be NULL) [N,6], sums4 as out4 above.
+ *   rslo_posegraph_matvec     y = H x, rslo_posegraph_chain_solve  z = M^-1 r, both [N,6], on the linearisation a
+ *                             rslo_posegraph_linearize call with the same N, L and workspace left behind (they write
+ *                             nothing when the workspace holds none: rslo_posegraph_cost, rslo_posegraph_optimize
+ *                             whose last linearisation had a singular chain edge, and a linearize of such a chain
+ *                             clear the mark, because the scan's matrices are not made); one launch of one
+ *                             workgroup each, the device functions of the solve.
+ * Errors are found before the first launch and write nothing: RSLO_EINVAL for a size, count or tolerance out of
+ * range (NaN included), a null pointer, a host chain weight that is not positive and finite, a bad robust_scale, a
+ * workspace that is null or not 8-byte aligned, x aliasing y; RSLO_EWS for ws_bytes below rslo_posegraph_ws_bytes(N, L).
+ * ------------------------------------------------------------------------------------ */
+#define RSLO_PG_EDGE_DOUBLES 84
+RSLO_API size_t rslo_posegraph_ws_bytes(int N, int L);
+RSLO_API int rslo_posegraph_optimize(const double *traj0, double *poses, int N, const double *chain_w2_host,
+                                     const double *chain_w_dev /*[N-1,2] or NULL*/, const int32_t *loops_ij,
+                                     const double *loops_Z, const double *loops_w, int L, int gn_iters, int cg_iters,
+                                     double cg_tol, double robust_scale, double damping, double tol_t, double tol_r,
+                                     double *info /*[gn_iters,8]*/, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_posegraph_cost(const double *traj0, const double *poses, int N, const double *chain_w2_host,
+                                 const double *chain_w_dev, const int32_t *loops_ij, const double *loops_Z,
+                                 const double *loops_w, int L, double robust_scale, double *out4, void *ws,
+                                 size_t ws_bytes, void *stream);
+RSLO_API int rslo_posegraph_linearize(const double *traj0, const double *poses, int N, const double *chain_w2_host,
+                                      const double *chain_w_dev, const int32_t *loops_ij, const double *loops_Z,
+                                      const double *loops_w, int L, double robust_scale, double *edges_out,
+                                      double *g_out, double *sums4, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_posegraph_matvec(const double *x, double *y, int N, int L, double damping, void *ws, size_t ws_bytes,
+                                   void *stream);
+RSLO_API int rslo_posegraph_chain_solve(const double *r, double *z, int N, int L, void *ws, size_t ws_bytes,
+                                        void *stream);
+RSLO_API int rslo_pose_between(const double *A, const double *B, int n, double *out /*[n,7]*/, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

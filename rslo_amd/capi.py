@@ -216,6 +216,15 @@ SIGNATURES = {
     "rslo_place_add": (C.c_int, [_vp, _sz, _i64, _i, _i, _vp, _vp, _vp, _vp]),
     "rslo_place_query_ws_bytes": (_sz, [_i64]),
     "rslo_place_query": (C.c_int, [_vp, _sz, _i64, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _sz, _vp]),
+    "rslo_posegraph_ws_bytes": (_sz, [_i, _i]),
+    "rslo_posegraph_optimize": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i] + [C.c_double] * 5 +
+                                [_vp, _vp, _sz, _vp]),
+    "rslo_posegraph_cost": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_posegraph_linearize": (C.c_int, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _sz,
+                                           _vp]),
+    "rslo_posegraph_matvec": (C.c_int, [_vp, _vp, _i, _i, C.c_double, _vp, _sz, _vp]),
+    "rslo_posegraph_chain_solve": (C.c_int, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
+    "rslo_pose_between": (C.c_int, [_vp, _vp, _i, _vp, _vp]),
 }
 
 
@@ -2293,3 +2302,98 @@ def place_query(buf, capacity, R, S, D, key, norm, exclude_recent, num_candidate
                                 _ptr(key, torch.int32, "key"), _ptr(norm, torch.float64, "norm"), int(exclude_recent),
                                 int(num_candidates), int(top_k), _ptr(out, torch.float64, "out"),
                                 _ptr(ws, torch.int64, "ws"), ws.numel() * 8, _stream()), "rslo_place_query")
+
+
+# --------------------------------------------------------------------------------------
+# pose graph (csrc/posegraph.hip); the owning class is rslo_amd/posegraph.py PoseGraph
+# --------------------------------------------------------------------------------------
+PG_EDGE_DOUBLES = 84      # doubles of an edge record (include/rslo_hip.h)
+_D2 = C.c_double * 2
+
+
+def posegraph_ws_bytes(N, L):
+    """rslo_posegraph_ws_bytes: 0 for N outside 2..65536 or L outside 0..4096."""
+    return int(lib().rslo_posegraph_ws_bytes(int(N), int(L)))
+
+
+def _pg_graph(traj0, poses, chain_w, loops_ij, loops_Z, loops_w, name):
+    """the arguments every pose-graph call shares: (traj0, poses, N, chain pair, chain array, ij, Z, w, L)"""
+    if traj0.dim() != 2 or traj0.shape[1] != 7 or poses.shape != traj0.shape:
+        raise RsloHipError("%s: traj0 and poses must be [N, 7] float64" % name)
+    N = int(traj0.shape[0])
+    pair, arr = None, None
+    if isinstance(chain_w, torch.Tensor):
+        if tuple(chain_w.shape) != (N - 1, 2):
+            raise RsloHipError("%s: a chain weight tensor must be [N-1, 2]" % name)
+        arr = _ptr(chain_w, torch.float64, "chain_w")
+    else:
+        pair = _D2(float(chain_w[0]), float(chain_w[1]))
+    L = 0 if loops_ij is None else int(loops_ij.shape[0])
+    if L and (tuple(loops_ij.shape) != (L, 2) or tuple(loops_Z.shape) != (L, 7) or tuple(loops_w.shape) != (L, 2)):
+        raise RsloHipError("%s: loops_ij [L, 2], loops_Z [L, 7] and loops_w [L, 2] must agree" % name)
+    return (_ptr(traj0, torch.float64, "traj0"), _ptr(poses, torch.float64, "poses"), N, pair, arr,
+            _ptr(loops_ij, torch.int32, "loops_ij") if L else None, _ptr(loops_Z, torch.float64, "loops_Z") if L else None,
+            _ptr(loops_w, torch.float64, "loops_w") if L else None, L)
+
+
+def posegraph_optimize(traj0, poses, chain_w, loops_ij, loops_Z, loops_w, gn_iters, cg_iters, cg_tol, robust_scale, damping,
+                       tol_t, tol_r, info, ws):
+    """rslo_posegraph_optimize on the current stream: poses float64 CUDA [N, 7] updated in place, info [gn_iters, 8]."""
+    g = _pg_graph(traj0, poses, chain_w, loops_ij, loops_Z, loops_w, "posegraph_optimize")
+    if 1 <= int(gn_iters) <= 32 and info.numel() != 8 * int(gn_iters):      # (a gn_iters out of range is the library's error)
+        raise RsloHipError("posegraph_optimize: info must be [gn_iters, 8]")
+    _chk(lib().rslo_posegraph_optimize(*g, int(gn_iters), int(cg_iters), float(cg_tol), float(robust_scale), float(damping),
+                                       float(tol_t), float(tol_r), _ptr(info, torch.float64, "info"),
+                                       _ptr(ws, torch.int64, "ws"), ws.numel() * 8, _stream()), "rslo_posegraph_optimize")
+
+
+def posegraph_cost(traj0, poses, chain_w, loops_ij, loops_Z, loops_w, robust_scale, out4, ws):
+    """rslo_posegraph_cost: out4 float64 CUDA [4] = (cost, chain part, loops used, loops skipped)."""
+    g = _pg_graph(traj0, poses, chain_w, loops_ij, loops_Z, loops_w, "posegraph_cost")
+    if out4.numel() != 4:
+        raise RsloHipError("posegraph_cost: out4 must have 4 elements")
+    _chk(lib().rslo_posegraph_cost(*g, float(robust_scale), _ptr(out4, torch.float64, "out4"), _ptr(ws, torch.int64, "ws"),
+                                   ws.numel() * 8, _stream()), "rslo_posegraph_cost")
+
+
+def posegraph_linearize(traj0, poses, chain_w, loops_ij, loops_Z, loops_w, robust_scale, edges, g_out, sums4, ws):
+    """rslo_posegraph_linearize: the edge records [(N-1+L), 84], the gradient [N, 6] and the four sums; the workspace
+    keeps the linearisation for posegraph_matvec / posegraph_chain_solve."""
+    g = _pg_graph(traj0, poses, chain_w, loops_ij, loops_Z, loops_w, "posegraph_linearize")
+    N, L = g[2], g[8]
+    if (edges is not None and edges.numel() != (N - 1 + L) * PG_EDGE_DOUBLES) or \
+            (g_out is not None and g_out.numel() != N * 6) or sums4.numel() != 4:
+        raise RsloHipError("posegraph_linearize: edges, g or sums4 do not have the sizes of N = %d, L = %d" % (N, L))
+    _chk(lib().rslo_posegraph_linearize(*g, float(robust_scale), _ptr(edges, torch.float64, "edges"),
+                                        _ptr(g_out, torch.float64, "g"), _ptr(sums4, torch.float64, "sums4"),
+                                        _ptr(ws, torch.int64, "ws"), ws.numel() * 8, _stream()), "rslo_posegraph_linearize")
+
+
+def posegraph_matvec(x, y, N, L, damping, ws):
+    """rslo_posegraph_matvec: y = H x, both float64 CUDA [N, 6], on the linearisation the workspace holds."""
+    if x.numel() != N * 6 or y.numel() != N * 6:
+        raise RsloHipError("posegraph_matvec: x and y must be [N, 6]")
+    _chk(lib().rslo_posegraph_matvec(_ptr(x, torch.float64, "x"), _ptr(y, torch.float64, "y"), int(N), int(L), float(damping),
+                                     _ptr(ws, torch.int64, "ws"), ws.numel() * 8, _stream()), "rslo_posegraph_matvec")
+
+
+def posegraph_chain_solve(r, z, N, L, ws):
+    """rslo_posegraph_chain_solve: z = M^-1 r, both float64 CUDA [N, 6], on the linearisation the workspace holds."""
+    if r.numel() != N * 6 or z.numel() != N * 6:
+        raise RsloHipError("posegraph_chain_solve: r and z must be [N, 6]")
+    _chk(lib().rslo_posegraph_chain_solve(_ptr(r, torch.float64, "r"), _ptr(z, torch.float64, "z"), int(N), int(L),
+                                          _ptr(ws, torch.int64, "ws"), ws.numel() * 8, _stream()),
+         "rslo_posegraph_chain_solve")
+
+
+def pose_between(A, B, out=None):
+    """rslo_pose_between: out[k] = A[k]^-1 o B[k] for float64 CUDA [n, 7] rows, on the current stream."""
+    if A.dim() != 2 or A.shape[1] != 7 or B.shape != A.shape:
+        raise RsloHipError("pose_between: A and B must be [n, 7] float64")
+    if out is None:
+        out = torch.empty_like(A)
+    elif out.shape != A.shape:
+        raise RsloHipError("pose_between: out must be [n, 7]")
+    _chk(lib().rslo_pose_between(_ptr(A, torch.float64, "A"), _ptr(B, torch.float64, "B"), int(A.shape[0]),
+                                 _ptr(out, torch.float64, "out"), _stream()), "rslo_pose_between")
+    return out

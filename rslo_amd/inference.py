@@ -279,11 +279,19 @@ class OdometryRunner:
       synchronisation, nothing allocated.  No threshold is applied and nothing is corrected: verification and the pose
       graph are the caller's.  reset() empties the database.  Unknown keys, or loop without places, are errors at
       construction.  None (the default): no database, today's bits.
+    * Pose graph: pose_graph=PoseGraph(...) (rslo_amd/posegraph.py, csrc/posegraph.hip) lets the caller close loops over
+      what has been streamed: close_loops(loops_ij, loops_Z, loops_w=None, **options) optimises a COPY of
+      refined_trajectory() when the runner refines, else of trajectory(), with PoseGraph.optimize's options, on the
+      caller's stream; optimized_trajectory() and pose_graph_info() return the result.  trajectory(), relative() and
+      refined_trajectory() stay what they are, bit for bit, and run() does not change.  Out of scope: feeding the
+      corrected poses back into the chain state or the voxel map, verifying a candidate, a keyframe store -- a loop
+      measurement is the caller's (for instance VoxelMap.register against a map of the old scans, then
+      PoseGraph.between).  None (the default): close_loops raises.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
                  normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None,
-                 places=None, loop=None):
+                 places=None, loop=None, pose_graph=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -390,6 +398,10 @@ class OdometryRunner:
                 raise capi.RsloHipError("OdometryRunner: the place database lives on %s, the runner on %s" % (places.device, dev))
             places.reserve(int(point_capacity))         # run() must not allocate
             self._loop = torch.zeros((self.capacity, loop["top_k"], 4), dtype=torch.float64, device=dev)
+        self.pose_graph = pose_graph
+        self._optimized = self._pg_info = None
+        if pose_graph is not None and pose_graph.device != dev:
+            raise capi.RsloHipError("OdometryRunner: the pose graph lives on %s, the runner on %s" % (pose_graph.device, dev))
         self.stats = {"scans": 0, "encoder_runs": 0, "head_replays": 0, "head_eager": 0, "captures": 0,
                       "weight_refreshes": 0}
 
@@ -432,6 +444,34 @@ class OdometryRunner:
             self._count2.zero_()
         if self.places is not None:
             self.places.reset()
+        self._optimized = self._pg_info = None
+
+    def close_loops(self, loops_ij, loops_Z, loops_w=None, **options):
+        """Optimise a copy of the streamed trajectory (the refined chain when the runner refines) under the loop edges
+        (loops_ij int32 [L, 2] scan indices, loops_Z float64 [L, 7] the pose of j in the frame of i, loops_w [L, 2] or
+        None for ones; options: PoseGraph.optimize's).  Returns (poses, info), also kept for optimized_trajectory() and
+        pose_graph_info().  Nothing the runner streams is changed."""
+        if self.pose_graph is None:
+            raise capi.RsloHipError("OdometryRunner.close_loops: the runner was built without pose_graph")
+        if "poses" in options:
+            raise capi.RsloHipError("OdometryRunner.close_loops: the start is the runner's own trajectory")
+        traj0 = self.refined_trajectory() if self.refine is not None else self.trajectory()
+        self._optimized, self._pg_info = self.pose_graph.optimize(traj0, loops_ij, loops_Z, loops_w, **options)
+        return self._optimized, self._pg_info
+
+    def optimized_trajectory(self):
+        """[n, 7] fp64 device rows: the result of the last close_loops()."""
+        if self._optimized is None:
+            raise capi.RsloHipError("OdometryRunner.optimized_trajectory: close_loops() has not run "
+                                    "(or the runner was built without pose_graph)")
+        return self._optimized
+
+    def pose_graph_info(self):
+        """[gn_iters, 8] fp64 device rows: PoseGraph.optimize's info of the last close_loops()."""
+        if self._pg_info is None:
+            raise capi.RsloHipError("OdometryRunner.pose_graph_info: close_loops() has not run "
+                                    "(or the runner was built without pose_graph)")
+        return self._pg_info
 
     def loop_candidates(self):
         """[n, top_k, 4] fp64 device rows (places=...): PlaceDB.query's result of every scan against the scans before it."""

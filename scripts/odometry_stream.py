@@ -10,6 +10,7 @@
     python scripts/odometry_stream.py --refine --refine-levels 0.8 0.4 0.2 --refine-iters-per-level 4 [--refine-robust 0.5] [--out profiles/odometry_stream_pyramid.json]
     python scripts/odometry_stream.py --map --local-map-radius 100 --local-map-every 10 --scans 200 --warmup 20 [--out profiles/odometry_stream_local_map.json]
     python scripts/odometry_stream.py --places --scans 200 --warmup 20 [--out profiles/odometry_stream_places.json]
+    python scripts/odometry_stream.py --pose-graph --scans 200 --warmup 20 [--out profiles/odometry_stream_posegraph.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -48,6 +49,15 @@ describe, query (10 ring-key candidates, and exhaustive) and add alone under dev
 whole drive; and a revisit pass: the drive's scans go into the database, then queries are made with synthetic.scan at
 earlier drive positions moved 0.7 m / 0.8 m with the heading reversed -- top-1 within 5 m, the distances of the true
 matches, and the smallest distance to any entry more than 10 m away (--seed must be the drive's).
+--pose-graph: the runner is built with a pose graph (rslo_amd.posegraph.PoseGraph, csrc/posegraph.hip); after its loop,
+loop measurements between scan 0 and eight later scans are made from the SYNTHETIC GROUND TRUTH (synthetic.sequence_pose
+-- the library cannot verify a loop candidate yet, so nothing here comes from place recognition), close_loops optimises
+and the translation RMSE against the ground truth is reported before and after -- for the runner's own trajectory, and
+for the drive's true relative motions disturbed by a seeded 2 cm / 0.1 degree error per scan and chained (the network
+of this script is untrained: its own trajectory is noise, and Gauss-Newton has no step control).  Then a size sweep on
+PoseGraphRef.synthetic_graph, N in {256, 1024, 4096, 8192} x L in {1, 16, 256}: per case the device-event time of
+optimize (6 Gauss-Newton iterations), of one iteration, of the edge launch with the sums (PoseGraph.cost; what is left
+of an iteration is the one-workgroup solve plus the update launch), and the CG iterations per Gauss-Newton iteration.
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -134,6 +144,7 @@ def main():
     ap.add_argument("--local-map-every", type=int, default=10, help="prune every K scans")
     ap.add_argument("--places", action="store_true", help="also run the runner with a place-recognition database attached")
     ap.add_argument("--places-queries", type=int, default=20, help="revisit queries of the --places report")
+    ap.add_argument("--pose-graph", action="store_true", help="close loops over the runner's trajectory and time the optimiser")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -198,7 +209,11 @@ def main():
                     out["translation_preds"], out["rotation_preds"]
         res["eager_ms_per_scan"], res["eager_host_ms_per_scan"] = [round(v, 3) for v in timed(eager)]
 
-    runner = inference.OdometryRunner(net)
+    graph = None
+    if args.pose_graph:
+        from rslo_amd import posegraph
+        graph = posegraph.PoseGraph(capacity=8192, max_loops=256, device=dev)
+    runner = inference.OdometryRunner(net, pose_graph=graph)
     pend = {}
 
     def run(rng):
@@ -234,6 +249,9 @@ def main():
         ref = torch.cat([out["translation_preds"][0], out["rotation_preds"][0]])
         res["last_rel_max_rel_diff"] = float((runner.relative()[-1] - ref).abs().max() / ref.abs().max())
     traj_input, rel_input = runner.trajectory().clone(), runner.relative().clone()
+    if args.pose_graph:
+        res.update(posegraph_close(args, runner))
+        res.update(posegraph_sweep(graph))
     runner.close()
     if args.raw:
         from rslo_amd import capi
@@ -345,6 +363,102 @@ def main():
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def posegraph_close(args, runner):
+    """--pose-graph, first part: loops from the synthetic ground truth onto the runner's trajectory"""
+    import numpy as np
+    import torch
+    from rslo_amd import posegraph, synthetic
+    n = runner.trajectory().shape[0]
+    truth = np.stack([synthetic.sequence_pose(i, args.seed) for i in range(n)])
+    j = np.unique(np.linspace(n // 8, n - 1, 8).astype(np.int64))
+    j = j[j > 0]
+    ij = np.stack([np.zeros_like(j), j], 1).astype(np.int32)
+    Z = posegraph.between(truth[ij[:, 0]], truth[ij[:, 1]])
+    dev = runner.trajectory().device
+    w = torch.full((len(j), 2), 10.0, dtype=torch.float64, device=dev)
+    w[:, 1] = 100.0
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    poses, info = runner.close_loops(torch.from_numpy(ij).to(dev), torch.from_numpy(Z).to(dev), w, chain_w=(1.0, 10.0),
+                                     gn_iters=6, cg_iters=64, cg_tol=1e-8)
+    e1.record()
+    e1.synchronize()
+    rmse = lambda P: float(np.sqrt(((P[:, :3] - truth[:, :3]) ** 2).sum(1).mean()))
+    info = info.cpu().numpy()
+    # the same loops on a trajectory with the drift of a working odometry: the drive's true relative motions disturbed by
+    # a seeded error of 2 cm and 0.1 degrees per scan (the network here is untrained, its own trajectory is noise)
+    rng = np.random.default_rng(args.seed)
+    st, sr = 0.02, np.deg2rad(0.1)
+    noise = np.concatenate([st * rng.standard_normal((n - 1, 3)), sr * rng.standard_normal((n - 1, 3))], 1)
+    rel = posegraph.retract(posegraph.between(truth[:-1], truth[1:]), noise)
+    drift = np.empty((n, 7))
+    drift[0] = truth[0]
+    for k in range(n - 1):
+        drift[k + 1] = posegraph.compose(drift[k], rel[k])
+        drift[k + 1, 3:] /= np.linalg.norm(drift[k + 1, 3:])
+    wd = torch.tensor([[10.0, 10.0 * st / sr]] * len(j), dtype=torch.float64, device=dev)
+    pd, infod = runner.pose_graph.optimize(torch.from_numpy(drift).to(dev), torch.from_numpy(ij).to(dev),
+                                           torch.from_numpy(Z).to(dev), wd, chain_w=(1.0, st / sr), gn_iters=6, cg_iters=128,
+                                           cg_tol=1e-8)
+    infod = infod.cpu().numpy()
+    extra = {"posegraph_drift_sigma": [st, 0.1], "posegraph_drift_translation_rmse_before_m": round(rmse(drift), 4),
+             "posegraph_drift_translation_rmse_after_m": round(rmse(pd.cpu().numpy()), 4),
+             "posegraph_drift_status": infod[:, 0].tolist(), "posegraph_drift_cg_iters": infod[:, 3].tolist(),
+             "posegraph_drift_cost": [float("%.6g" % v) for v in infod[:, 2]]}
+    return {**extra, "posegraph_loops_from": "synthetic ground truth (synthetic.sequence_pose); no candidate is verified by the library",
+            "posegraph_loops_ij": ij.tolist(), "posegraph_nodes": int(n),
+            "posegraph_translation_rmse_before_m": round(rmse(runner.trajectory().cpu().numpy()), 4),
+            "posegraph_translation_rmse_after_m": round(rmse(poses.cpu().numpy()), 4),
+            "posegraph_close_loops_ms": round(e0.elapsed_time(e1), 3),
+            "posegraph_status": info[:, 0].tolist(), "posegraph_cg_iters": info[:, 3].tolist(),
+            "posegraph_cost": [float("%.6g" % v) for v in info[:, 2]]}
+
+
+def posegraph_sweep(graph):
+    """--pose-graph, second part: optimize on synthetic graphs of growing size, under device events"""
+    import torch
+    from rslo_amd import posegraph
+    dev = graph.device
+    rows = []
+
+    def events(fn, n):
+        fn()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(n):
+            fn()
+        e1.record()
+        e1.synchronize()
+        return e0.elapsed_time(e1) / n
+
+    for N in (256, 1024, 4096, 8192):
+        for L in (1, 16, 256):
+            g = posegraph.synthetic_graph(N, loops=L, seed=1)
+            t = {k: torch.from_numpy(g[k]).to(dev) for k in ("traj0", "loops_ij", "loops_Z", "loops_w")}
+            cw = tuple(g["chain_w"])
+            poses, info = t["traj0"].clone(), torch.zeros((6, 8), dtype=torch.float64, device=dev)
+            opt = dict(chain_w=cw, cg_iters=128, cg_tol=1e-8)
+
+            def six():
+                poses.copy_(t["traj0"])
+                graph.optimize(t["traj0"], t["loops_ij"], t["loops_Z"], t["loops_w"], poses=poses, gn_iters=6, info=info, **opt)
+
+            def one():
+                poses.copy_(t["traj0"])
+                graph.optimize(t["traj0"], t["loops_ij"], t["loops_Z"], t["loops_w"], poses=poses, gn_iters=1, info=info[:1], **opt)
+            out4 = torch.zeros((4,), dtype=torch.float64, device=dev)
+            ms6 = events(six, 3)
+            inf = info.cpu().numpy().copy()
+            ms1 = events(one, 3)
+            ms_edges = events(lambda: graph.cost(t["traj0"], poses, t["loops_ij"], t["loops_Z"], t["loops_w"], chain_w=cw, out=out4), 10)
+            rows.append({"N": N, "L": L, "optimize_6_iterations_ms": round(ms6, 3), "first_iteration_ms": round(ms1, 3),
+                         "edges_and_sums_ms": round(ms_edges, 4), "solve_and_update_ms": round(ms1 - ms_edges, 3),
+                         "cg_iters": inf[:, 3].tolist(), "status": inf[:, 0].tolist(),
+                         "cost_first_last": [float("%.6g" % inf[0, 2]), float("%.6g" % inf[-1, 2])]})
+    return {"posegraph_sweep": rows}
 
 
 def _revisit_scan(a):
