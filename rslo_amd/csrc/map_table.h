@@ -6,6 +6,8 @@
 
 #pragma clang fp contract(off)   /* the cell of a point must not depend on FMA formation */
 
+#include "se3.h"                 /* after the pragma: the pose algebra takes this file's contraction state */
+
 typedef unsigned long long map_u64;
 #define MAP_KEY_NONE (~(map_u64)0)
 #define MAP_MAGIC 0x52534c4f4d415031ull /* "RSLOMAP1" */
@@ -52,12 +54,6 @@ __device__ __forceinline__ map_u64 map_mix(map_u64 x) {      // splitmix64 final
   return x;
 }
 
-__device__ __forceinline__ void map_cross(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 // 0: key and world position valid; 1: skipped (not finite, or outside the range gate); 2: cell outside +-2^20
 __device__ __forceinline__ int map_point(const float *__restrict__ p, const double *__restrict__ pose, double voxel,
                                          double min_range, double max_range, map_u64 &key, double *w) {
@@ -67,14 +63,12 @@ __device__ __forceinline__ int map_point(const float *__restrict__ p, const doub
   const double x[3] = {(double)fx, (double)fy, (double)fz};
   const double d2 = x[0] * x[0] + x[1] * x[1] + x[2] * x[2];
   if (!(d2 >= min_range * min_range && d2 < max_range * max_range)) return 1;
-  const double t[3] = {pose[0], pose[1], pose[2]};
-  const double qw = pose[3], v[3] = {pose[4], pose[5], pose[6]};
-  double b[3], c[3];
-  map_cross(v, x, b);
-  map_cross(v, b, c);
+  const double t[3] = {pose[0], pose[1], pose[2]}, q[4] = {pose[3], pose[4], pose[5], pose[6]};
+  double r[3];
+  se3_rotate(q, x, r);      // form A, uncontracted; the pose's quaternion is used as it is, not renormalised
   map_u64 k = 0;
   for (int a = 0; a < 3; ++a) {
-    w[a] = t[a] + (x[a] + (2.0 * b[a] * qw + 2.0 * c[a]));       // k_pose_chain's arithmetic, not renormalised
+    w[a] = t[a] + r[a];
     const double cell = floor(w[a] / voxel);
     if (!(fabs(cell) < MAP_MAXC)) return 2;                      // also a NaN or infinite world coordinate
     k = (k << 21) | (map_u64)((long long)cell + 1048576);

@@ -143,12 +143,9 @@ __global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long
       if (metric == 1) {
         const double ns[3] = {(double)p[4], (double)p[5], (double)p[6]};
         if (ns[0] * ns[0] + ns[1] * ns[1] + ns[2] * ns[2] >= 0.25) {      // false for a NaN normal as well
-          const double v[3] = {pose[4], pose[5], pose[6]};
-          double b[3], c[3], n[3], wn[3];
-          map_cross(v, ns, b);
-          map_cross(v, b, c);
-          for (int a = 0; a < 3; ++a) n[a] = ns[a] + (2.0 * b[a] * pose[3] + 2.0 * c[a]);
-          map_cross(w, n, wn);
+          double n[3], wn[3];
+          se3_rotate(pose + 3, ns, n);
+          se3_cross(w, n, wn);
           for (int a = 0; a < 3; ++a) {
             J[0][a] = n[a];
             J[0][3 + a] = wn[a];
@@ -280,24 +277,14 @@ __global__ __launch_bounds__(64) void k_mapreg_finish(const double *__restrict__
         status = 2;      // an overflowed step is no step
         nt = th = 0.0;
       } else {
-        double dq[4];
-        if (th < 1e-12) {
-          dq[0] = 1.0;
-          for (int a = 0; a < 3; ++a) dq[1 + a] = dr[a] / 2.0;
-        } else {
-          const double f = sin(th / 2.0) / th;
-          dq[0] = cos(th / 2.0);
-          for (int a = 0; a < 3; ++a) dq[1 + a] = f * dr[a];
-        }
-        double t[3], q[4], b[3], c[3], vx[3], r[4];
+        double dq[4], t[3], q[4], b[3], c[3], r[4];
+        se3_dquat(dr, th, dq);
         for (int a = 0; a < 3; ++a) t[a] = pose7[a];
         for (int a = 0; a < 4; ++a) q[a] = pose7[3 + a];
-        map_cross(dq + 1, t, b);
-        map_cross(dq + 1, b, c);
-        for (int a = 0; a < 3; ++a) pose7[a] = dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]);
-        map_cross(dq + 1, q + 1, vx);
-        r[0] = dq[0] * q[0] - (dq[1] * q[1] + dq[2] * q[2] + dq[3] * q[3]);
-        for (int a = 0; a < 3; ++a) r[1 + a] = dq[1 + a] * q[0] + q[1 + a] * dq[0] + vx[a];
+        se3_cross(dq + 1, t, b);
+        se3_cross(dq + 1, b, c);
+        for (int a = 0; a < 3; ++a) pose7[a] = dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]);      // form B: see se3.h
+        se3_qmul(dq, q, r);
         const double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
         for (int a = 0; a < 4; ++a) pose7[3 + a] = r[a] / nr;
       }

@@ -7,6 +7,7 @@
 //      t* = res_R T_pred + res_t,
 //    matrix -> quaternion with kornia's four trace branches and eps = 1e-8.
 #include "rslo_common.h"
+#include "se3.h"      /* no fp contract pragma in this file: k_pose_chain is compiled with fused multiply-adds */
 
 __global__ void k_quat_to_rot(const float *__restrict__ q_wxyz, int B, float *__restrict__ R) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -136,12 +137,6 @@ extern "C" int rslo_pose_targets(const float *res_r, const float *res_t, const f
 // Absolute pose of a streamed sequence, one scan per launch (rslo/utils/geometric.py odom_to_abs_pose restated for one
 // step; captured in the head's hipGraph, so the row index comes from the device counter, not the host).  The state is
 // kept in float64 so that thousands of steps follow the float64 host function.
-__device__ __forceinline__ void pc_cross(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
 __global__ void k_pose_chain(const float *__restrict__ t_in, const float *__restrict__ q_in, double *__restrict__ state,
                              int32_t *__restrict__ count, float *__restrict__ rel_rows, double *__restrict__ traj, int cap) {
   if (threadIdx.x != 0) return;
@@ -157,14 +152,14 @@ __global__ void k_pose_chain(const float *__restrict__ t_in, const float *__rest
     double ts[3], qs[4];
     for (int i = 0; i < 3; ++i) ts[i] = state[i];
     for (int i = 0; i < 4; ++i) qs[i] = state[3 + i];
-    // t_s + rotate_vec_by_q(t, q_s):  t + 2 w (v x t) + 2 v x (v x t)
+    // t_s + rotate_vec_by_q(t, q_s):  t + 2 w (v x t) + 2 v x (v x t); form B: see se3.h
     double b[3], c[3];
-    pc_cross(qs + 1, t, b);
-    pc_cross(qs + 1, b, c);
+    se3_cross(qs + 1, t, b);
+    se3_cross(qs + 1, b, c);
     for (int i = 0; i < 3; ++i) ts[i] = ts[i] + (t[i] + 2.0 * b[i] * qs[0] + 2.0 * c[i]);
     // qmult(q_s, q), re-normalised with the eps inside the division (pose_utils_np.normalize)
     double vx[3];
-    pc_cross(qs + 1, q + 1, vx);
+    se3_cross(qs + 1, q + 1, vx);
     double r[4];
     r[0] = qs[0] * q[0] - (qs[1] * q[1] + qs[2] * q[2] + qs[3] * q[3]);
     for (int i = 0; i < 3; ++i) r[1 + i] = qs[1 + i] * q[0] + q[1 + i] * qs[0] + vx[i];

@@ -27,6 +27,8 @@
 
 #pragma clang fp contract(off)
 
+#include "se3.h"      /* the pose algebra, after the pragma: uncontracted here */
+
 #define PG_THREADS 1024
 #define PG_EREC 84                       /* doubles per edge record (RSLO_PG_EDGE_DOUBLES) */
 #define PG_HDR 256                       /* bytes: int32 words, see below */
@@ -86,44 +88,6 @@ static size_t pg_layout(int N, int L, void *ws, PgWs *o) {
   w.Pb = (double *)(b + off), off += lev;
   if (o) *o = w;
   return off;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// pose algebra (rslo_pose_chain's formulas)
-// ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void pg_cross(const double *a, const double *b, double *c) {
-  c[0] = a[1] * b[2] - a[2] * b[1];
-  c[1] = a[2] * b[0] - a[0] * b[2];
-  c[2] = a[0] * b[1] - a[1] * b[0];
-}
-
-__device__ __forceinline__ void pg_rotate(const double *q, const double *v, double *o) {
-  double b[3], c[3];
-  pg_cross(q + 1, v, b);
-  pg_cross(q + 1, b, c);
-  for (int i = 0; i < 3; ++i) o[i] = v[i] + (2.0 * b[i] * q[0] + 2.0 * c[i]);
-}
-
-__device__ __forceinline__ void pg_qmul(const double *a, const double *b, double *r) {
-  double vx[3];
-  pg_cross(a + 1, b + 1, vx);
-  r[0] = a[0] * b[0] - (a[1] * b[1] + a[2] * b[2] + a[3] * b[3]);
-  for (int i = 0; i < 3; ++i) r[1 + i] = a[1 + i] * b[0] + b[1 + i] * a[0] + vx[i];
-}
-
-// A^-1 o B
-__device__ __forceinline__ void pg_between(const double *A, const double *B, double *o) {
-  const double qc[4] = {A[3], -A[4], -A[5], -A[6]};
-  const double d[3] = {B[0] - A[0], B[1] - A[1], B[2] - A[2]};
-  pg_rotate(qc, d, o);
-  pg_qmul(qc, B + 3, o + 3);
-}
-
-__device__ __forceinline__ void pg_rotmat(const double *q, double *R) {
-  const double w = q[0], x = q[1], y = q[2], z = q[3];
-  R[0] = 1.0 - 2.0 * (y * y + z * z), R[1] = 2.0 * (x * y - w * z), R[2] = 2.0 * (x * z + w * y);
-  R[3] = 2.0 * (x * y + w * z), R[4] = 1.0 - 2.0 * (x * x + z * z), R[5] = 2.0 * (y * z - w * x);
-  R[6] = 2.0 * (x * z - w * y), R[7] = 2.0 * (y * z + w * x), R[8] = 1.0 - 2.0 * (x * x + y * y);
 }
 
 __device__ __forceinline__ bool pg_finite(double v) { return fabs(v) < (double)__builtin_inff(); }
@@ -189,7 +153,7 @@ __global__ __launch_bounds__(256) void k_pg_edges(const double *__restrict__ tra
   bool valid = true;
   if (chain) {
     i = e, j = e + 1;
-    pg_between(traj0 + (size_t)i * 7, traj0 + (size_t)j * 7, Z);
+    se3_between(traj0 + (size_t)i * 7, traj0 + (size_t)j * 7, Z);
     wt = cw_dev ? cw_dev[2 * e] : cwt;
     wr = cw_dev ? cw_dev[2 * e + 1] : cwr;
   } else {
@@ -220,12 +184,12 @@ __global__ __launch_bounds__(256) void k_pg_edges(const double *__restrict__ tra
     }
   }
   double A[7], E[7], RZ[9], RA[9], RE[9];
-  pg_between(poses + (size_t)i * 7, poses + (size_t)j * 7, A);
-  pg_between(Z, A, E);
+  se3_between(poses + (size_t)i * 7, poses + (size_t)j * 7, A);
+  se3_between(Z, A, E);
   const double s = E[3] >= 0.0 ? 1.0 : -1.0;
-  pg_rotmat(Z + 3, RZ);
-  pg_rotmat(A + 3, RA);
-  pg_rotmat(E + 3, RE);
+  se3_rotmat(Z + 3, RZ);
+  se3_rotmat(A + 3, RA);
+  se3_rotmat(E + 3, RE);
   const double G[9] = {s * E[3], s * -E[6], s * E[5], s * E[6], s * E[3], s * -E[4], s * -E[5], s * E[4], s * E[3]};
   const double S[9] = {0.0, -A[2], A[1], A[2], 0.0, -A[0], -A[1], A[0], 0.0};      // [t_A]x
   double r[6];
@@ -677,16 +641,9 @@ __global__ __launch_bounds__(256) void k_pg_update(PgWs ws, double *__restrict__
   double *T = poses + (size_t)n * 7;
   const double th = sqrt(x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
   double dq[4], d[3], q[4];
-  if (th < 1e-12) {
-    dq[0] = 1.0;
-    for (int a = 0; a < 3; ++a) dq[1 + a] = x[3 + a] / 2.0;
-  } else {
-    const double f = sin(th / 2.0) / th;
-    dq[0] = cos(th / 2.0);
-    for (int a = 0; a < 3; ++a) dq[1 + a] = f * x[3 + a];
-  }
-  pg_rotate(T + 3, x, d);
-  pg_qmul(T + 3, dq, q);
+  se3_dquat(x + 3, th, dq);
+  se3_rotate(T + 3, x, d);
+  se3_qmul(T + 3, dq, q);
   const double nr = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
   for (int a = 0; a < 3; ++a) T[a] = T[a] + d[a];
   for (int a = 0; a < 4; ++a) T[3 + a] = q[a] / nr;
@@ -720,7 +677,7 @@ __global__ void k_pose_between(const double *__restrict__ A, const double *__res
   const int k = blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= n) return;
   double o[7];
-  pg_between(A + (size_t)k * 7, B + (size_t)k * 7, o);
+  se3_between(A + (size_t)k * 7, B + (size_t)k * 7, o);
   for (int a = 0; a < 7; ++a) out[(size_t)k * 7 + a] = o[a];
 }
 

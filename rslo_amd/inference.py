@@ -193,7 +193,8 @@ class EncoderGraphRunner:
 
 def pose_chain_host(rows):
     """The recurrence of rslo_pose_chain on the host, one scan at a time, float64: rows [N,7] (t, q wxyz) -> poses [N,7].
-    Scan 0 seeds the state with its own odometry and is the identity (the quirk of geometric.odom_to_abs_pose)."""
+    Scan 0 seeds the state with its own odometry and is the identity (the quirk of geometric.odom_to_abs_pose).  The
+    translation update is form B: see se3.py."""
     import numpy as np
     rows = np.asarray(rows, dtype=np.float64)
     out = np.zeros_like(rows)
@@ -220,6 +221,7 @@ class OdometryRunner:
         rel, pose = runner.run(h)           # [7] (t, q) each: odometry of (previous, this) and absolute pose
         traj = runner.trajectory()          # [N, 7] fp64 device tensor = odom_to_abs_pose of the rel rows
         runner.reset()                      # new sequence: the next scan pairs with itself, the trajectory restarts
+        runner.feed(clouds)                 # THE way to drive a runner over a list of scans: submit one ahead, run
 
     * Encoder: an EncoderGraphRunner with one frame per job and no covariance branch (poses do not depend on it): every
       scan is voxelized, planned and encoded ONCE.  (The dataset builds example i from frames (max(i-1, 0), i), so an
@@ -236,7 +238,9 @@ class OdometryRunner:
       (load_state_dict, an optimizer step, bn.running_var.mul_(...)); a storage that moved is re-planned and the head
       graph captured again.  A replaced parameter object, or a write through `.data` (it bumps no version counter):
       call refresh_weights(force=True).
-    * Handles: the outstanding-handle rule of EncoderGraphRunner (fewer than `arenas` submitted and not yet run).
+    * Handles: the outstanding-handle rule of EncoderGraphRunner (fewer than `arenas` submitted and not yet run).  feed()
+      keeps it for the caller: it submits scan i + 1, then runs scan i, so two handles are outstanding at the most and the
+      helper thread plans one scan ahead of the device.  submit() / run() by hand are for callers that read `rel` / `pose`.
     * Raw scans: normals="estimate" takes what a LiDAR produces, [P, 4] (x, y, z, intensity; or [P, 3], intensity 0):
       the helper thread builds the [P, 7] cloud with capi.append_normals (csrc/normals.hip: the offline step of
       script/create_hdf5.py:130-147 with normal_radius / normal_max_nn, plus the reader's zero_vertical rule) on the plan
@@ -424,6 +428,19 @@ class OdometryRunner:
         h = self.encoder.submit(cloud)
         h.source = cloud if keep else None
         return h
+
+    def feed(self, scans):
+        """Drive the runner over the sequence `scans` in order: scan i + 1 is submitted before scan i is run, so the
+        helper thread plans the next scan while the device works on this one.  Nothing is read back and nothing is
+        returned (trajectory(), relative() ... hold the results); never more than two handles are outstanding."""
+        if len(scans) == 0:
+            return
+        h = self.submit(scans[0])
+        for cloud in scans[1:]:
+            ahead = self.submit(cloud)
+            self.run(h)
+            h = ahead
+        self.run(h)
 
     def _append_normals(self, scan, arena, k):
         """pre-plan hook (helper thread, plan stream): raw scan -> the arena's [P, 7] cloud"""

@@ -85,6 +85,8 @@ and on the pyramids MapPyramid (device) / MapPyramidRef (numpy):
 """
 import numpy as np
 
+from . import se3
+
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full")
 PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
 _MAXC = 1 << 20
@@ -240,7 +242,8 @@ def _cross3(a, b):
 
 def gauss_newton_step(sums, pose, damping=0.0):
     """The step of register from the 28 sums (H upper triangle, g, cost) at pose [7]: -> (new pose [7], |dt|, theta), or
-    None when M = H + damping * I is not positive definite.  Scalar float64 in the order of the device's one thread."""
+    None when M = H + damping * I is not positive definite.  Scalar float64 in the order of the device's one thread;
+    the translation update is form B: see se3.py."""
     import math
     f = [float(v) for v in sums]
     M = [[0.0] * 6 for _ in range(6)]
@@ -325,15 +328,7 @@ class VoxelMapRef:
             d2 = p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1] + p[:, 2] * p[:, 2]
             gate = (d2 >= self.min_range * self.min_range) & (d2 < self.max_range * self.max_range)
             status[~(finite & gate)] = 1
-            t, qw, v = pose[:3], pose[3], pose[4:7]
-
-            def cross(a, b):      # a: [3] or [P, 3]
-                a = np.broadcast_to(a, b.shape)
-                return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
-                                 a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
-            b = cross(v, p)
-            c = cross(v, b)
-            w = t[None, :] + (p + (2.0 * b * qw + 2.0 * c))
+            w = pose[None, :3] + se3.rotate(pose[3:], p)
             cell = np.floor(w / self.voxel_size)
             inside = (np.abs(cell) < float(_MAXC)).all(axis=1)      # False for NaN / inf as well
             status[(status == 0) & ~inside] = 2
@@ -490,17 +485,9 @@ class VoxelMapRef:
                 ns = pts[sel, 4:7].astype(np.float64)
                 plane = (ns[:, 0] * ns[:, 0] + ns[:, 1] * ns[:, 1] + ns[:, 2] * ns[:, 2]) >= 0.25
             ns, wp, dp = ns[plane], w[plane], d[plane]
-            qw, v = posev[3], posev[4:7]
-
-            def cross(a, b):
-                a = np.broadcast_to(a, b.shape)
-                return np.stack([a[:, 1] * b[:, 2] - a[:, 2] * b[:, 1], a[:, 2] * b[:, 0] - a[:, 0] * b[:, 2],
-                                 a[:, 0] * b[:, 1] - a[:, 1] * b[:, 0]], axis=1)
-            b = cross(v, ns)
-            c = cross(v, b)
-            n = ns + (2.0 * b * qw + 2.0 * c)
+            n = se3.rotate(posev[3:], ns)
             J[plane] = 0.0
-            J[plane, 0, :3], J[plane, 0, 3:] = n, cross(wp, n)
+            J[plane, 0, :3], J[plane, 0, 3:] = n, np.cross(wp, n)
             r[plane] = 0.0
             r[plane, 0] = n[:, 0] * dp[:, 0] + n[:, 1] * dp[:, 1] + n[:, 2] * dp[:, 2]
         terms = np.zeros((K, 28), np.float64)

@@ -16,7 +16,7 @@ A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, co
 scan by scan to
   (a) the eager loop of evaluate.py:363-408: the example of scan i is built from frames (max(i-1, 0), i) the way the
       dataset builds it (kitti_dataset_hdf5.py:184-185, workload.make_example) and `net(example)` runs under no_grad;
-  (b) the runner: submit one scan ahead, run, no host read.
+  (b) the runner: OdometryRunner.feed (submit one scan ahead, run), no host read.
 Both are timed with device events over --scans scans after --warmup scans; one JSON line is printed.
 --raw: a third loop feeds the same scans stripped to [P, 4] (what a LiDAR produces) to a runner built with
 normals="estimate" (csrc/normals.hip on the plan stream) and reports its ms per scan, the distance of its trajectory
@@ -121,6 +121,45 @@ def launches(a_csv, b_csv, n_a, n_b):
             "scans_a": n_a, "scans_b": n_b}
 
 
+def device_ms(fn, n):
+    """ms per call of fn(0) .. fn(n - 1): two device events around the n calls, behind a synchronise"""
+    import torch
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for i in range(n):
+        fn(i)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / n
+
+
+def timed_feed(runner, scans, W, N):
+    """(device ms, host ms) per scan of runner.feed over scans W .. W + N - 1, behind the W scans in front of them"""
+    import torch
+    runner.feed(scans[:W])
+    torch.cuda.synchronize()
+    h0 = time.perf_counter()
+    ms = device_ms(lambda _: runner.feed(scans[W:W + N]), 1)
+    return ms / N, (time.perf_counter() - h0) * 1e3 / N
+
+
+class EagerLoop:
+    """(a) of the module docstring behind the face timed_feed drives: feed(scans) runs net(example) scan by scan"""
+
+    def __init__(self, net):
+        self.net, self.prev = net, None
+
+    def feed(self, scans):
+        import torch
+        from rslo_amd import workload
+        with torch.no_grad():
+            for s in scans:
+                out = self.net(workload.make_example(self.net, [[s if self.prev is None else self.prev, s]]))
+                out["translation_preds"], out["rotation_preds"]
+                self.prev = s
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scans", type=int, default=200)
@@ -190,52 +229,23 @@ def main():
     res = {"metric": "odometry_stream_ms_per_scan", "scans": N, "warmup": W, "seed": args.seed,
            "points_per_scan": int(sum(c.shape[0] for c in clouds) / len(clouds)), "scan_generation_s": round(t_scans, 1)}
 
-    def timed(loop):
-        loop(range(W))
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        h0 = time.perf_counter()
-        e0.record()
-        loop(range(W, W + N))
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / N, (time.perf_counter() - h0) * 1e3 / N
-
     if not args.runner_only:
-        def eager(rng):
-            with torch.no_grad():
-                for i in rng:
-                    out = net(workload.make_example(net, [[scans[max(i - 1, 0)], scans[i]]]))
-                    out["translation_preds"], out["rotation_preds"]
-        res["eager_ms_per_scan"], res["eager_host_ms_per_scan"] = [round(v, 3) for v in timed(eager)]
+        res["eager_ms_per_scan"], res["eager_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(EagerLoop(net), scans, W, N)]
 
     graph = None
     if args.pose_graph:
         from rslo_amd import posegraph
         graph = posegraph.PoseGraph(capacity=8192, max_loops=256, device=dev)
     runner = inference.OdometryRunner(net, pose_graph=graph)
-    pend = {}
-
-    def run(rng):
-        rng = list(rng)
-        for k, i in enumerate(rng):
-            if i not in pend:
-                pend[i] = runner.submit(scans[i])
-            if k + 1 < len(rng) and rng[k + 1] not in pend:
-                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])      # one scan ahead
-            runner.run(pend.pop(i))
-    res["runner_ms_per_scan"], res["runner_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+    res["runner_ms_per_scan"], res["runner_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(runner, scans, W, N)]
     # the pair map: the two device copies per scan, measured on their own
     C = runner._pair.shape[1] // 2
     bev = torch.empty_like(runner._pair[:, C:])
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(100):
+
+    def copies(_):
         runner._pair[:, :C].copy_(runner._pair[:, C:])
         runner._pair[:, C:].copy_(bev)
-    e1.record()
-    e1.synchronize()
-    res["pair_map_copies_ms_per_scan"] = round(e0.elapsed_time(e1) / 100, 4)
+    res["pair_map_copies_ms_per_scan"] = round(device_ms(copies, 100), 4)
     res["pair_map_bytes_per_scan"] = int(2 * 2 * bev.numel() * 4)
     res["runner_stats"] = dict(runner.stats)
     res["encoder_runs_per_scan"] = round(runner.encoder.stats["runs"] / max(1, runner.stats["scans"]), 3)
@@ -250,119 +260,109 @@ def main():
         res["last_rel_max_rel_diff"] = float((runner.relative()[-1] - ref).abs().max() / ref.abs().max())
     traj_input, rel_input = runner.trajectory().clone(), runner.relative().clone()
     if args.pose_graph:
-        res.update(posegraph_close(args, runner))
-        res.update(posegraph_sweep(graph))
+        res.update(pose_graph_report(args, runner))
     runner.close()
     if args.raw:
-        from rslo_amd import capi
-        raw_scans = [s[:, :4].contiguous() for s in scans]
-        raw = inference.OdometryRunner(net, normals="estimate")
-        pend.clear()
-
-        def run_raw(rng):
-            rng = list(rng)
-            for k, i in enumerate(rng):
-                if i not in pend:
-                    pend[i] = raw.submit(raw_scans[i])
-                if k + 1 < len(rng) and rng[k + 1] not in pend:
-                    pend[rng[k + 1]] = raw.submit(raw_scans[rng[k + 1]])
-                raw.run(pend.pop(i))
-        res["raw_ms_per_scan"], res["raw_host_ms_per_scan"] = [round(v, 3) for v in timed(run_raw)]
-        res["raw_minus_input_ms_per_scan"] = round(res["raw_ms_per_scan"] - res["runner_ms_per_scan"], 3)
-        d = (raw.trajectory() - traj_input)[:, :3].norm(dim=1)
-        path = (traj_input[1:, :3] - traj_input[:-1, :3]).norm(dim=1).sum()
-        res["raw_traj_max_dist_m"], res["raw_traj_end_dist_m"] = float(d.max()), float(d[-1])
-        res["input_traj_path_m"] = float(path)
-        dr = (raw.relative() - rel_input).abs().max(dim=1).values / rel_input.abs().max(dim=1).values
-        res["raw_rel_diff_median"], res["raw_rel_diff_max"] = float(dr.median()), float(dr.max())
-        raw.close()
-        # normals of one scan on their own: time of the six launches, agreement with the analytic normals
-        s0 = scans[W]
-        capi.estimate_normals(raw_scans[W], zero_vertical=True)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(20):
-            est, cnt = capi.estimate_normals(raw_scans[W], zero_vertical=True)
-        e1.record()
-        e1.synchronize()
-        res["normals_alone_ms_per_scan"] = round(e0.elapsed_time(e1) / 20, 4)
-        both = (s0[:, 4:7].norm(dim=1) > 0) & (est.norm(dim=1) > 0)
-        cosang = (s0[:, 4:7] * est)[both].sum(1).abs().clamp(max=1.0)
-        res["normals_median_angle_deg"] = float(torch.rad2deg(torch.acos(cosang)).median())
-        res["normals_compared_points"] = int(both.sum())
-        res["normals_points_with_fewer_than_3_neighbours"] = int((cnt < 3).sum())
+        res.update(raw_report(args, net, scans, res, traj_input, rel_input))
     if args.map:
-        from rslo_amd import mapping
-        vmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
-        mapped = inference.OdometryRunner(net, voxel_map=vmap)
-        pend.clear()
-
-        def run_map(rng):
-            rng = list(rng)
-            for k, i in enumerate(rng):
-                if i not in pend:
-                    pend[i] = mapped.submit(scans[i])
-                if k + 1 < len(rng) and rng[k + 1] not in pend:
-                    pend[rng[k + 1]] = mapped.submit(scans[rng[k + 1]])
-                mapped.run(pend.pop(i))
-        res["map_ms_per_scan"], res["map_host_ms_per_scan"] = [round(v, 3) for v in timed(run_map)]
-        res["map_minus_runner_ms_per_scan"] = round(res["map_ms_per_scan"] - res["runner_ms_per_scan"], 3)
-        traj = mapped.trajectory().clone()
-        res["map_traj_equals_runner"] = bool(torch.equal(traj.view(torch.int64), traj_input.view(torch.int64)))      # bits: a NaN equals itself
-        res["map_stats"] = vmap.stats()
-        res["map_voxel"], res["map_capacity"] = args.map_voxel, args.map_capacity
-        res["map_load"] = round(res["map_stats"]["n_cells"] / float(args.map_capacity), 4)
-        mapped.close()
-        # the inserts alone: the same scans into a second map, under the runner's trajectory rows and under the drive's own
-        # poses (synthetic.sequence_pose: the registered cloud a trained network would approach)
-        alone = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
-        alone.reserve(max(s.shape[0] for s in scans))
-
-        def insert_pass(poses):
-            """(ms per timed insert, counters, mean overlap of a scan with the map before its insertion)"""
-            alone.reset()
-            for i in range(W):
-                alone.insert(scans[i], poses[i])
-            torch.cuda.synchronize()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for i in range(W, W + N):
-                alone.insert(scans[i], poses[i])
-            e1.record()
-            e1.synchronize()
-            stats = alone.stats()
-            alone.reset()
-            ov = torch.zeros((), dtype=torch.float32, device=dev)      # one host read at the end
-            for i in range(W + N):
-                if i > 0:
-                    ov += alone.overlap(scans[i], poses[i])
-                alone.insert(scans[i], poses[i])
-            return round(e0.elapsed_time(e1) / N, 4), stats, round(float(ov) / (W + N - 1), 4)
-
-        res["map_insert_alone_ms_per_scan"], stats, res["map_mean_overlap_before_insert"] = insert_pass(traj)
-        res["map_insert_alone_stats_equal"] = stats == res["map_stats"]
-        if True:      # (--load-scans: the file must hold the drive of --seed)
-            from rslo_amd import synthetic
-            true = [torch.from_numpy(synthetic.sequence_pose(i, args.seed)).to(dev) for i in range(W + N)]
-            (res["map_true_pose_insert_ms_per_scan"], res["map_true_pose_stats"],
-             res["map_true_pose_mean_overlap_before_insert"]) = insert_pass(true)
-            res["map_true_pose_load"] = round(res["map_true_pose_stats"]["n_cells"] / float(args.map_capacity), 4)
-        if args.map_out:
-            vmap.save_ply(args.map_out)
-            res["map_ply_bytes"] = os.path.getsize(args.map_out)
+        res.update(map_report(args, net, scans, res, traj_input))
     if args.refine:
-        res.update(refine_report(args, net, scans, timed, res["map_ms_per_scan"]))
+        res.update(refine_report(args, net, scans, res))
     if args.refine_levels is not None:
-        res.update(pyramid_report(args, net, scans, timed, res))
+        res.update(pyramid_report(args, net, scans, res))
     if args.local_map_radius is not None:
-        res.update(local_map_report(args, net, scans, timed, res))
+        res.update(local_map_report(args, net, scans, res))
     if args.places:
-        res.update(places_report(args, net, scans, timed, res))
+        res.update(places_report(args, net, scans, res))
     line = json.dumps(res)
     print(line)
     if args.out:
         with open(args.out, "w") as f:
             f.write(line + "\n")
+
+
+def raw_report(args, net, scans, res, traj_input, rel_input):
+    """--raw: the runner fed [P, 4] scans beside the plain runner's figures, and the normals of one scan on their own"""
+    import torch
+    from rslo_amd import capi, inference
+    W, N = args.warmup, args.scans
+    out = {}
+    raw_scans = [s[:, :4].contiguous() for s in scans]
+    raw = inference.OdometryRunner(net, normals="estimate")
+    out["raw_ms_per_scan"], out["raw_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(raw, raw_scans, W, N)]
+    out["raw_minus_input_ms_per_scan"] = round(out["raw_ms_per_scan"] - res["runner_ms_per_scan"], 3)
+    d = (raw.trajectory() - traj_input)[:, :3].norm(dim=1)
+    path = (traj_input[1:, :3] - traj_input[:-1, :3]).norm(dim=1).sum()
+    out["raw_traj_max_dist_m"], out["raw_traj_end_dist_m"] = float(d.max()), float(d[-1])
+    out["input_traj_path_m"] = float(path)
+    dr = (raw.relative() - rel_input).abs().max(dim=1).values / rel_input.abs().max(dim=1).values
+    out["raw_rel_diff_median"], out["raw_rel_diff_max"] = float(dr.median()), float(dr.max())
+    raw.close()
+    # normals of one scan on their own: time of the six launches, agreement with the analytic normals
+    s0 = scans[W]
+    est, cnt = capi.estimate_normals(raw_scans[W], zero_vertical=True)
+    out["normals_alone_ms_per_scan"] = round(device_ms(lambda _: capi.estimate_normals(raw_scans[W], zero_vertical=True), 20), 4)
+    both = (s0[:, 4:7].norm(dim=1) > 0) & (est.norm(dim=1) > 0)
+    cosang = (s0[:, 4:7] * est)[both].sum(1).abs().clamp(max=1.0)
+    out["normals_median_angle_deg"] = float(torch.rad2deg(torch.acos(cosang)).median())
+    out["normals_compared_points"] = int(both.sum())
+    out["normals_points_with_fewer_than_3_neighbours"] = int((cnt < 3).sum())
+    return out
+
+
+def map_report(args, net, scans, res, traj_input):
+    """--map: the runner with a world voxel map beside the plain runner's figures, and the inserts alone"""
+    import torch
+    from rslo_amd import inference, mapping, synthetic
+    dev = scans[0].device
+    W, N = args.warmup, args.scans
+    out = {}
+    vmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+    mapped = inference.OdometryRunner(net, voxel_map=vmap)
+    out["map_ms_per_scan"], out["map_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(mapped, scans, W, N)]
+    out["map_minus_runner_ms_per_scan"] = round(out["map_ms_per_scan"] - res["runner_ms_per_scan"], 3)
+    traj = mapped.trajectory().clone()
+    out["map_traj_equals_runner"] = bool(torch.equal(traj.view(torch.int64), traj_input.view(torch.int64)))      # bits: a NaN equals itself
+    out["map_stats"] = vmap.stats()
+    out["map_voxel"], out["map_capacity"] = args.map_voxel, args.map_capacity
+    out["map_load"] = round(out["map_stats"]["n_cells"] / float(args.map_capacity), 4)
+    mapped.close()
+    # the inserts alone: the same scans into a second map, under the runner's trajectory rows and under the drive's own
+    # poses (synthetic.sequence_pose: the registered cloud a trained network would approach)
+    alone = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
+    alone.reserve(max(s.shape[0] for s in scans))
+
+    def insert_pass(poses):
+        """(ms per timed insert, counters, mean overlap of a scan with the map before its insertion)"""
+        alone.reset()
+        for i in range(W):
+            alone.insert(scans[i], poses[i])
+        ms = device_ms(lambda i: alone.insert(scans[W + i], poses[W + i]), N)
+        stats = alone.stats()
+        alone.reset()
+        ov = torch.zeros((), dtype=torch.float32, device=dev)      # one host read at the end
+        for i in range(W + N):
+            if i > 0:
+                ov += alone.overlap(scans[i], poses[i])
+            alone.insert(scans[i], poses[i])
+        return round(ms, 4), stats, round(float(ov) / (W + N - 1), 4)
+
+    out["map_insert_alone_ms_per_scan"], stats, out["map_mean_overlap_before_insert"] = insert_pass(traj)
+    out["map_insert_alone_stats_equal"] = stats == out["map_stats"]
+    # (--load-scans: the file must hold the drive of --seed)
+    true = [torch.from_numpy(synthetic.sequence_pose(i, args.seed)).to(dev) for i in range(W + N)]
+    (out["map_true_pose_insert_ms_per_scan"], out["map_true_pose_stats"],
+     out["map_true_pose_mean_overlap_before_insert"]) = insert_pass(true)
+    out["map_true_pose_load"] = round(out["map_true_pose_stats"]["n_cells"] / float(args.map_capacity), 4)
+    if args.map_out:
+        vmap.save_ply(args.map_out)
+        out["map_ply_bytes"] = os.path.getsize(args.map_out)
+    return out
+
+
+def pose_graph_report(args, runner):
+    """--pose-graph: loops closed over the runner's trajectory, then the size sweep"""
+    return {**posegraph_close(args, runner), **posegraph_sweep(runner.pose_graph)}
 
 
 def posegraph_close(args, runner):
@@ -423,16 +423,9 @@ def posegraph_sweep(graph):
     dev = graph.device
     rows = []
 
-    def events(fn, n):
+    def events(fn, n):      # one call to warm up, then n timed
         fn()
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(n):
-            fn()
-        e1.record()
-        e1.synchronize()
-        return e0.elapsed_time(e1) / n
+        return device_ms(lambda _: fn(), n)
 
     for N in (256, 1024, 4096, 8192):
         for L in (1, 16, 256):
@@ -467,7 +460,7 @@ def _revisit_scan(a):
     return synthetic.scan(pose_xy=(x, y), yaw=yaw, scan_seed=seed)
 
 
-def places_report(args, net, scans, timed, res):
+def places_report(args, net, scans, res):
     """--places: the runner with a place database, the three calls alone, and the revisit pass"""
     import numpy as np
     import torch
@@ -478,17 +471,7 @@ def places_report(args, net, scans, timed, res):
     loop = dict(exclude_recent=50, num_candidates=10, top_k=1)
     db = places.PlaceDB(capacity=max(1024, W + N), device=dev)
     runner = inference.OdometryRunner(net, places=db, loop=loop)
-    pend = {}
-
-    def run(rng):
-        rng = list(rng)
-        for k, i in enumerate(rng):
-            if i not in pend:
-                pend[i] = runner.submit(scans[i])
-            if k + 1 < len(rng) and rng[k + 1] not in pend:
-                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
-            runner.run(pend.pop(i))
-    out["places_ms_per_scan"], out["places_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+    out["places_ms_per_scan"], out["places_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(runner, scans, W, N)]
     out["places_minus_runner_ms_per_scan"] = round(out["places_ms_per_scan"] - res["runner_ms_per_scan"], 3)
     out["places_loop"] = loop
     out["places_stats"] = db.stats()
@@ -498,16 +481,6 @@ def places_report(args, net, scans, timed, res):
     out["places_runner_smallest_distance"] = float(cand[found, 0, 1].min()) if found.any() else None      # a drive without a loop
     runner.close()
 
-    def events(fn, n):
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(n):
-            fn(i)
-        e1.record()
-        e1.synchronize()
-        return round(e0.elapsed_time(e1) / n, 4)
-
     # the three calls alone: the database holds the whole drive while it is queried
     descs = [tuple(t.clone() for t in db.describe(s)) for s in scans]
     db.reset()
@@ -515,12 +488,12 @@ def places_report(args, net, scans, timed, res):
         db.add(*d)
     row = torch.zeros((16, 4), dtype=torch.float64, device=dev)
     out["places_entries_when_queried"] = W + N
-    out["places_describe_ms"] = events(lambda i: db.describe(scans[W + i]), N)
+    out["places_describe_ms"] = round(device_ms(lambda i: db.describe(scans[W + i]), N), 4)
     for C in (10, 0):
-        out["places_query_c%d_ms" % C] = events(
-            lambda i: db.query(*descs[W + i], exclude_recent=0, num_candidates=C, top_k=1, out=row[:1]), N)
+        out["places_query_c%d_ms" % C] = round(device_ms(
+            lambda i: db.query(*descs[W + i], exclude_recent=0, num_candidates=C, top_k=1, out=row[:1]), N), 4)
     side = places.PlaceDB(capacity=max(1024, W + N), device=dev)
-    out["places_add_ms"] = events(lambda i: side.add(*descs[W + i]), N)
+    out["places_add_ms"] = round(device_ms(lambda i: side.add(*descs[W + i]), N), 4)
 
     # revisit: earlier drive positions, 0.7 m / 0.8 m off, heading reversed
     n_q = max(1, min(args.places_queries, W + N))
@@ -564,7 +537,7 @@ def places_report(args, net, scans, timed, res):
     return out
 
 
-def local_map_report(args, net, scans, timed, res):
+def local_map_report(args, net, scans, res):
     """The map loops with a rolling local map beside the figures of the same loops without one (already in `res`, or
     measured here in the same way)."""
     import torch
@@ -577,17 +550,7 @@ def local_map_report(args, net, scans, timed, res):
     def runner_loop(name, base, **kw):
         vmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
         runner = inference.OdometryRunner(net, voxel_map=vmap, local_map=lm, **kw)
-        pend = {}
-
-        def run(rng):
-            rng = list(rng)
-            for k, i in enumerate(rng):
-                if i not in pend:
-                    pend[i] = runner.submit(scans[i])
-                if k + 1 < len(rng) and rng[k + 1] not in pend:
-                    pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
-                runner.run(pend.pop(i))
-        out[name + "_ms_per_scan"], out[name + "_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+        out[name + "_ms_per_scan"], out[name + "_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(runner, scans, W, N)]
         out[name + "_minus_%s_ms_per_scan" % base] = round(out[name + "_ms_per_scan"] - res[base + "_ms_per_scan"], 3)
         out[name + "_stats"], out[name + "_prune_stats"] = vmap.stats(), vmap.prune_stats()
         # once more, untimed, for the largest n_cells: behind a run() that pruned, the cells in front of that prune are
@@ -595,7 +558,7 @@ def local_map_report(args, net, scans, timed, res):
         runner.reset()
         peak, gone = 0, 0
         for i in range(W + N):
-            run([i])
+            runner.feed(scans[i:i + 1])
             if (i + 1) % lm["every"] == 0 or i == W + N - 1:
                 ps = vmap.prune_stats()
                 peak = max(peak, vmap.stats()["n_cells"] + ps["n_evicted"] + ps["n_lost"] - gone)
@@ -670,64 +633,28 @@ def local_map_report(args, net, scans, timed, res):
     # a call that evicts nothing, on the map the pruned pass left
     out["prune_load_at_no_evict_calls"] = round(alone.stats()["n_cells"] / float(args.map_capacity), 4)
     alone.prune(true[-1], float("inf"))
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(20):
-        alone.prune(true[-1], float("inf"))
-    e1.record()
-    e1.synchronize()
-    out["prune_no_evict_ms_per_call"] = round(e0.elapsed_time(e1) / 20, 4)
+    out["prune_no_evict_ms_per_call"] = round(device_ms(lambda _: alone.prune(true[-1], float("inf")), 20), 4)
     return out
-
-
-def _rot(q, v):
-    import numpy as np
-    b = np.cross(q[1:], v)
-    return v + 2.0 * q[0] * b + 2.0 * np.cross(q[1:], b)
-
-
-def _compose(a, b):
-    """a o b of two poses [7] (t, q wxyz), float64"""
-    import numpy as np
-    qa, qb = a[3:], b[3:]
-    q = np.concatenate([[qa[0] * qb[0] - qa[1:] @ qb[1:]], qa[0] * qb[1:] + qb[0] * qa[1:] + np.cross(qa[1:], qb[1:])])
-    return np.concatenate([a[:3] + _rot(qa, b[:3]), q / np.linalg.norm(q)])
-
-
-def _inverse(a):
-    import numpy as np
-    qi = a[3:] * np.array([1.0, -1.0, -1.0, -1.0])
-    return np.concatenate([-_rot(qi, a[:3]), qi])
 
 
 def _pose_error(a, b):
     """(metres, degrees) between two poses"""
     import numpy as np
-    d = _compose(_inverse(b), a)
+    from rslo_amd import se3
+    d = se3.compose(se3.inverse(b), a)
     return float(np.linalg.norm(a[:3] - b[:3])), float(np.rad2deg(2.0 * np.arcsin(min(1.0, np.linalg.norm(d[4:])))))
 
 
-def refine_report(args, net, scans, timed, map_ms):
-    import numpy as np
-    import torch
-    from rslo_amd import inference, mapping, synthetic
+def refine_report(args, net, scans, res):
+    """--refine: the runner with scan-to-map refinement beside the --map loop, and the registration-alone pass"""
+    from rslo_amd import inference, mapping
     dev = scans[0].device
     W, N, K = args.warmup, args.scans, args.refine_iters
     out = {"refine_iters": K}
     rmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)
     runner = inference.OdometryRunner(net, voxel_map=rmap, refine=dict(iters=K))
-    pend = {}
-
-    def run(rng):
-        rng = list(rng)
-        for k, i in enumerate(rng):
-            if i not in pend:
-                pend[i] = runner.submit(scans[i])
-            if k + 1 < len(rng) and rng[k + 1] not in pend:
-                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
-            runner.run(pend.pop(i))
-    out["refine_ms_per_scan"], out["refine_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
-    out["refine_minus_map_ms_per_scan"] = round(out["refine_ms_per_scan"] - map_ms, 3)
+    out["refine_ms_per_scan"], out["refine_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(runner, scans, W, N)]
+    out["refine_minus_map_ms_per_scan"] = round(out["refine_ms_per_scan"] - res["map_ms_per_scan"], 3)
     info = runner.refine_info().cpu().numpy()
     out["refine_runner_status_counts"] = [int((info[:, :, 0] == k).sum()) for k in range(4)]
     out["refine_runner_mean_pairs"] = round(float(info[1:, 0, 1].mean()), 1)
@@ -746,7 +673,7 @@ def register_alone(args, scans, target, call, name, pairs_row=0):
     `target` (a VoxelMap or a MapPyramid, reset here) and returns its info rows; the scan is inserted under the result."""
     import numpy as np
     import torch
-    from rslo_amd import synthetic
+    from rslo_amd import se3, synthetic
     dev = scans[0].device
     W, N = args.warmup, args.scans
     out = {}
@@ -762,7 +689,7 @@ def register_alone(args, scans, target, call, name, pairs_row=0):
         ang = np.deg2rad(0.1) * rng.uniform(0.5, 1.5)
         err = np.concatenate([0.05 * rng.normal(size=3) * [1.0, 1.0, 0.3], [np.cos(ang / 2)],
                               np.sin(ang / 2) * axis / np.linalg.norm(axis)])
-        pred = _compose(refined, _compose(_compose(_inverse(true[i - 1]), true[i]), err))
+        pred = se3.compose(refined, se3.compose(se3.compose(se3.inverse(true[i - 1]), true[i]), err))
         pose.copy_(torch.from_numpy(pred))
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
@@ -790,7 +717,7 @@ def register_alone(args, scans, target, call, name, pairs_row=0):
     return out
 
 
-def pyramid_report(args, net, scans, timed, res):
+def pyramid_report(args, net, scans, res):
     """Coarse-to-fine robust registration beside the figures of the --refine loop of this process (already in `res`)."""
     import torch
     from rslo_amd import inference, mapping, synthetic
@@ -801,17 +728,8 @@ def pyramid_report(args, net, scans, timed, res):
     sched = pyr.default_schedule(per, args.refine_robust)
     out = {"pyramid_levels": list(levels), "pyramid_schedule": [list(st) for st in sched]}
     runner = inference.OdometryRunner(net, voxel_map=pyr, refine=dict(schedule=sched))
-    pend = {}
-
-    def run(rng):
-        rng = list(rng)
-        for k, i in enumerate(rng):
-            if i not in pend:
-                pend[i] = runner.submit(scans[i])
-            if k + 1 < len(rng) and rng[k + 1] not in pend:
-                pend[rng[k + 1]] = runner.submit(scans[rng[k + 1]])
-            runner.run(pend.pop(i))
-    out["pyramid_refine_ms_per_scan"], out["pyramid_refine_host_ms_per_scan"] = [round(v, 3) for v in timed(run)]
+    out["pyramid_refine_ms_per_scan"], out["pyramid_refine_host_ms_per_scan"] = [
+        round(v, 3) for v in timed_feed(runner, scans, W, N)]
     out["pyramid_refine_minus_refine_ms_per_scan"] = round(out["pyramid_refine_ms_per_scan"] - res["refine_ms_per_scan"], 3)
     info = runner.refine_info().cpu().numpy()
     out["pyramid_refine_runner_status_counts"] = [int((info[:, :, 0] == k).sum()) for k in range(4)]
@@ -824,14 +742,7 @@ def pyramid_report(args, net, scans, timed, res):
         pyr.reset()
         for i in range(W):
             target.insert(scans[i], true[i])
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(W, W + N):
-            target.insert(scans[i], true[i])
-        e1.record()
-        e1.synchronize()
-        out[name] = round(e0.elapsed_time(e1) / N, 4)
+        out[name] = round(device_ms(lambda i: target.insert(scans[W + i], true[W + i]), N), 4)
     out["pyramid_true_pose_stats"] = pyr.stats()
     # the registration-alone pass, the same seeded disturbance for every setting
     single = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev)

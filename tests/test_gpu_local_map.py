@@ -10,6 +10,7 @@ that lean on it restate the map's hash in numpy and assert that as a preconditio
 import numpy as np
 import pytest
 import torch
+from stream_support import dev, network_and_scans, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -28,10 +29,6 @@ def _cloud(seed, n=4000):
     if (seed, n) not in _CLOUD:
         _CLOUD[(seed, n)] = synthetic.small_cloud(n, seed=seed)
     return _CLOUD[(seed, n)]
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _got(vmap, **kw):
@@ -55,7 +52,7 @@ def _pair(voxel, capacity, scans):
     from rslo_amd.mapping import VoxelMap, VoxelMapRef
     vmap, ref = VoxelMap(voxel, capacity), VoxelMapRef(voxel)
     for cloud, pose in scans:
-        vmap.insert(_dev(cloud), pose)
+        vmap.insert(dev(cloud), pose)
         ref.insert(cloud, pose)
     return vmap, ref
 
@@ -114,7 +111,7 @@ def test_survivor_counts(K):
     assert ref.stats()["n_cells"] == K and ref.prune_stats() == {"n_prunes": 1, "n_evicted": 1000 - K, "n_lost": 0}
     _assert_same(vmap, ref, "K %d" % K)
     assert (_got(vmap)[1] == np.arange(K)).all()
-    hits = vmap.lookup(_dev(pts), IDENT).cpu().numpy()
+    hits = vmap.lookup(dev(pts), IDENT).cpu().numpy()
     assert (hits[:K] == 1).all() and (hits[K:] == 0).all()
 
 
@@ -135,7 +132,7 @@ def test_minimum_table_with_wrap_around():
     ref.prune(center, radius)
     assert vmap.prune_stats()["n_lost"] == 0
     _assert_same(vmap, ref, "capacity 1024")
-    got = vmap.lookup(_dev(_cloud(5, 1000)), IDENT).cpu().numpy()
+    got = vmap.lookup(dev(_cloud(5, 1000)), IDENT).cpu().numpy()
     assert (got == ref.lookup(_cloud(5, 1000), IDENT)).all() and (got == 0).sum() > 200
 
 
@@ -143,7 +140,7 @@ def test_nothing_evicted_leaves_the_table_alone():
     vmap, ref = _pair(0.4, 1 << 14, ((_cloud(0), IDENT), (_cloud(5), POSE_YAW)))
     hdr = 256 // 8
     before = vmap._buf.clone()
-    for kw in (dict(), dict(center=CENTER, radius=float("inf")), dict(center=_dev(POSE_YAW), radius=1.0e4),
+    for kw in (dict(), dict(center=CENTER, radius=float("inf")), dict(center=dev(POSE_YAW), radius=1.0e4),
                dict(min_hits=3, grace=2)):      # with two scans every cell is younger than 2
         n0 = vmap.prune_stats()["n_prunes"]
         vmap.prune(**kw)
@@ -167,25 +164,25 @@ def test_life_after_a_prune():
     print("third scan: %d points in kept cells, %d in evicted cells, %d in cells never stored" % (
         int((now > 0).sum()), n_evicted_hit, int((was == 0).sum())))
     assert n_evicted_hit > 50 and (now > 0).sum() > 50 and 100 < ref.stats()["n_cells"] < ref.prune_stats()["n_evicted"]
-    hits, tags = vmap.lookup(_dev(third), POSE_FULL, return_tags=True)      # an evicted cell reads 0, not its old hits
+    hits, tags = vmap.lookup(dev(third), POSE_FULL, return_tags=True)      # an evicted cell reads 0, not its old hits
     whits, wtags = ref.lookup(third, POSE_FULL, return_tags=True)
     assert (hits.cpu().numpy() == whits).all() and (tags.cpu().numpy() == wtags).all()
-    vmap.insert(_dev(third), POSE_BACK)
+    vmap.insert(dev(third), POSE_BACK)
     ref.insert(third, POSE_BACK)
     _assert_same(vmap, ref, "third scan after the prune")
     rtags = ref.points()[1]
     assert (rtags >> 32 == 2).sum() > n_evicted_hit // 4                    # evicted cells were created afresh by scan 2
     q = _cloud(9)
-    hits, tags = vmap.lookup(_dev(q), POSE_YAW, return_tags=True)
+    hits, tags = vmap.lookup(dev(q), POSE_YAW, return_tags=True)
     whits, wtags = ref.lookup(q, POSE_YAW, return_tags=True)
     assert (whits > 0).sum() > 100 and (hits.cpu().numpy() == whits).all() and (tags.cpu().numpy() == wtags).all()
-    t, d2, rows = vmap.nearest(_dev(q), _dev(POSE_YAW), return_rows=True)
+    t, d2, rows = vmap.nearest(dev(q), dev(POSE_YAW), return_rows=True)
     wt, wd, wr = ref.nearest(q, POSE_YAW, return_rows=True)
     assert (wt >= 0).sum() > 100 and (t.cpu().numpy() == wt).all()
     assert (d2.cpu().numpy().view(np.int64) == wd.view(np.int64)).all()
     assert (rows.cpu().numpy().view(np.int32) == wr.view(np.int32)).all()
     # and a second prune, about a pose row on the device, with the sparse rule
-    vmap.prune(_dev(POSE_BACK), 8.0, min_hits=2, grace=1)
+    vmap.prune(dev(POSE_BACK), 8.0, min_hits=2, grace=1)
     ref.prune(POSE_BACK, 8.0, min_hits=2, grace=1)
     assert ref.prune_stats()["n_prunes"] == 2 and 0 < ref.stats()["n_cells"]
     _assert_same(vmap, ref, "second prune")
@@ -209,7 +206,7 @@ def test_overflow_recovery():
     print("at most %d survivors, longest run with the fresh scan %d" % (int(could.sum()), _longest_run(_occupied(union, 1024))))
     assert 50 < could.sum() <= 256 and len(probe.keys) == 200 and _longest_run(_occupied(union, 1024)) < PROBE
     vmap = VoxelMap(0.4, 1024)
-    vmap.insert(_dev(_cloud(0)), IDENT)
+    vmap.insert(dev(_cloud(0)), IDENT)
     st0 = vmap.stats()
     assert st0["dropped_full"] > 0
     rows, tags, hits = _got(vmap)
@@ -221,10 +218,10 @@ def test_overflow_recovery():
     st = vmap.stats()
     assert st == dict(st0, n_cells=int(keep.sum()))
     assert vmap.prune_stats() == {"n_prunes": 1, "n_evicted": len(tags) - int(keep.sum()), "n_lost": 0}
-    vmap.insert(_dev(fresh), IDENT)
+    vmap.insert(dev(fresh), IDENT)
     st2 = vmap.stats()
     assert st2["dropped_full"] == st0["dropped_full"] and st2["n_cells"] == st["n_cells"] + 200
-    assert bool((vmap.lookup(_dev(fresh), IDENT) > 0).all())
+    assert bool((vmap.lookup(dev(fresh), IDENT) > 0).all())
 
 
 @pytest.mark.parametrize("grace", [0, 1])
@@ -247,14 +244,14 @@ def test_capture_and_replay():
     poses = [IDENT, POSE_YAW]
     radius = 7.0
     warm = VoxelMap(0.4, 1 << 14)                   # the kernels' first launches, outside the capture
-    warm.insert(_dev(clouds[0]), IDENT)
-    warm.prune(_dev(IDENT), radius)
+    warm.insert(dev(clouds[0]), IDENT)
+    warm.prune(dev(IDENT), radius)
     vmap, ref = VoxelMap(0.4, 1 << 14), VoxelMapRef(0.4)
     vmap.reserve(len(clouds[0]))
     vmap.reserve_prune()
     static_pts = torch.zeros((len(clouds[0]), 4), dtype=torch.float32, device="cuda")
     static_pose = torch.zeros(7, dtype=torch.float64, device="cuda")
-    dev = [(_dev(c), _dev(p)) for c, p in zip(clouds, poses)]
+    on_dev = [(dev(c), dev(p)) for c, p in zip(clouds, poses)]
     torch.cuda.synchronize()
     g = torch.cuda.CUDAGraph()
     with torch.cuda.graph(g):
@@ -263,7 +260,7 @@ def test_capture_and_replay():
     assert vmap.stats()["n_scans"] == 0 and vmap.prune_stats()["n_prunes"] == 0      # captured, not run
     torch.cuda.synchronize()
     mem = torch.cuda.memory_allocated()
-    for k, (c, p) in enumerate(dev):
+    for k, (c, p) in enumerate(on_dev):
         static_pts.copy_(c)
         static_pose.copy_(p)
         g.replay()
@@ -281,8 +278,8 @@ def test_determinism():
     for _ in range(2):
         vmap, _ = _pair(0.4, 1 << 14, ((_cloud(0), IDENT), (_cloud(5), POSE_YAW)))
         vmap.prune(CENTER, 6.0)
-        vmap.insert(_dev(_cloud(7)), POSE_BACK)
-        vmap.prune(_dev(POSE_BACK), 9.0, min_hits=2, grace=1)
+        vmap.insert(dev(_cloud(7)), POSE_BACK)
+        vmap.prune(dev(POSE_BACK), 9.0, min_hits=2, grace=1)
         got = _got(vmap), vmap.stats(), vmap.prune_stats()
         assert len(got[0][1]) > 100 and got[2]["n_prunes"] == 2
         if first is not None:
@@ -297,7 +294,7 @@ def test_argument_errors_write_nothing():
     vmap.reserve_prune()
     before = vmap._buf.clone()
     buf, ws = vmap._buf, vmap._prune_ws
-    c = _dev(CENTER)
+    c = dev(CENTER)
     nb, wb = buf.numel() * 8, ws.numel() * 8
     assert wb == lib.rslo_map_prune_ws_bytes(2048)
     rcs = [lib.rslo_map_prune(buf.data_ptr(), nb, c.data_ptr(), -1.0, 1, 0, ws.data_ptr(), wb, None),
@@ -329,27 +326,13 @@ MAP_ARGS = dict(voxel_size=0.2, capacity=1 << 21, min_range=2.5, max_range=80.0)
 LOCAL = dict(radius=30.0, every=2)
 
 
-def _stream(runner, scans):
-    pend = runner.submit(scans[0])
-    for i in range(len(scans)):
-        nxt = runner.submit(scans[i + 1]) if i + 1 < len(scans) else None
-        runner.run(pend)
-        pend = nxt
-    torch.cuda.synchronize()
-    return runner.relative().cpu().numpy(), runner.trajectory().cpu().numpy()
-
-
 def test_runner_keeps_a_local_map():
-    from rslo_amd import capi, inference, synthetic, workload
+    from rslo_amd import capi, inference
     from rslo_amd.mapping import VoxelMap, VoxelMapRef
-    torch.manual_seed(21)
-    net, _ = workload.build_network()
-    net.eval()
-    scans = [torch.from_numpy(synthetic.sequence_scan(i, seed=3)).cuda() for i in range(N_SCANS)]
-    workload.calibrate_head_bn(net, (scans[0], scans[1]))
+    net, scans = network_and_scans(21, 3, N_SCANS)
     plain = inference.OdometryRunner(net)
     try:
-        rel0, traj0 = _stream(plain, scans)
+        rel0, traj0 = stream(plain, scans)
     finally:
         plain.close()
     for bad in (dict(radius=30.0, every=0), dict(radius=30.0, evry=2), dict(every=2), dict(radius=-1.0)):
@@ -361,7 +344,7 @@ def test_runner_keeps_a_local_map():
     runner = inference.OdometryRunner(net, voxel_map=vmap, local_map=LOCAL)
     try:
         assert vmap._prune_ws is not None                       # reserved by the constructor
-        rel, traj = _stream(runner, scans)
+        rel, traj = stream(runner, scans)
         assert rel.tobytes() == rel0.tobytes() and traj.tobytes() == traj0.tobytes()      # the local map disturbs nothing
         ref = VoxelMapRef(MAP_ARGS["voxel_size"], MAP_ARGS["min_range"], MAP_ARGS["max_range"])
         for n, (s, pose) in enumerate(zip(scans, traj)):
@@ -379,7 +362,7 @@ def test_runner_keeps_a_local_map():
     refined = inference.OdometryRunner(net, voxel_map=rmap, refine=dict(iters=1), local_map=dict(radius=30.0, every=1))
     try:
         assert refined.local_map == dict(radius=30.0, every=1, min_hits=1, grace=0)
-        _stream(refined, scans[:2])
+        stream(refined, scans[:2])
         traj2 = refined.refined_trajectory().cpu().numpy()
         assert traj2[1].tobytes() != refined.trajectory().cpu().numpy()[1].tobytes()      # the two chains differ
         ref = VoxelMapRef(MAP_ARGS["voxel_size"], MAP_ARGS["min_range"], MAP_ARGS["max_range"])

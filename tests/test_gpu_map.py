@@ -12,6 +12,7 @@ import ctypes
 import numpy as np
 import pytest
 import torch
+from stream_support import dev, odom_fixture, stream
 
 pytestmark = pytest.mark.gpu
 
@@ -42,10 +43,6 @@ def _ref(voxel, scans, **kw):
     return _REF[key]
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _got(vmap, **kw):
     rows, tags, hits = vmap.points(**kw)
     return rows.cpu().numpy(), tags.cpu().numpy(), hits.cpu().numpy()
@@ -73,11 +70,11 @@ def test_small_cloud(voxel):
     if voxel == 2.0:
         assert rhits.max() > 32
     assert (ref.points()[0][:, 3] != 0).all()      # the intensities are real
-    pts = _dev(_cloud(0))
+    pts = dev(_cloud(0))
     first = None
     for k in range(2):                             # two fresh maps: the same bits
         vmap = VoxelMap(voxel, 1 << 14)
-        vmap.insert(pts, _dev(IDENT))
+        vmap.insert(pts, dev(IDENT))
         _assert_same(vmap, ref, "small %.1f run %d" % (voxel, k))
         got = _got(vmap)
         if first is not None:
@@ -100,7 +97,7 @@ def test_sizes(N):
         if voxel == 10.0:
             assert ref.points()[2].tolist() == [N]
         vmap = VoxelMap(voxel, 1 << 12)
-        vmap.insert(_dev(c), pose)
+        vmap.insert(dev(c), pose)
         _assert_same(vmap, ref, "N %d voxel %.1f" % (N, voxel))
 
 
@@ -119,8 +116,8 @@ def test_two_scans(name):
     n0 = len(only0.points()[1])
     assert rrows[:n0].tobytes() == only0.points()[0].tobytes()      # a later scan never changes an earlier cell's row
     vmap = VoxelMap(0.4, 1 << 14)
-    vmap.insert(_dev(_cloud(0)), IDENT)
-    vmap.insert(_dev(_cloud(5)), _dev(pose))
+    vmap.insert(dev(_cloud(0)), IDENT)
+    vmap.insert(dev(_cloud(5)), dev(pose))
     _assert_same(vmap, ref, "two scans " + name)
 
 
@@ -137,7 +134,7 @@ def test_negative_and_far_coordinates():
         assert ref.stats()["dropped_range"] == dropped and ref.stats()["n_points"] == len(c) - dropped
         assert (ref.points()[0][:, 0] < 0).all() or dropped
         vmap = VoxelMap(0.1, 1 << 14)
-        vmap.insert(_dev(cloud), IDENT)
+        vmap.insert(dev(cloud), IDENT)
         _assert_same(vmap, ref, "far cloud, %d out of range" % dropped)
         assert vmap.stats()["dropped_range"] == dropped
         refs.append(ref)
@@ -156,7 +153,7 @@ def test_invalid_and_gated_points():
     ref.insert(c, POSE_YAW)
     assert ref.stats()["dropped_invalid"] == 2
     vmap = VoxelMap(0.4, 1 << 14)
-    vmap.insert(_dev(c), POSE_YAW)
+    vmap.insert(dev(c), POSE_YAW)
     _assert_same(vmap, ref, "NaN / inf")
     s = synthetic.scan(n_az=520, n_el=16)
     rng = np.linalg.norm(s[:, :3].astype(np.float64), axis=1)
@@ -166,14 +163,14 @@ def test_invalid_and_gated_points():
     st = ref.stats()
     assert 0 < st["dropped_invalid"] < len(s) and st["n_points"] + st["dropped_invalid"] == len(s)
     vmap = VoxelMap(0.4, 1 << 14, min_range=10.0, max_range=40.0)
-    vmap.insert(_dev(s), POSE_YAW)
+    vmap.insert(dev(s), POSE_YAW)
     _assert_same(vmap, ref, "range gate 10 .. 40 m")
 
 
 def test_strided_input():
     from rslo_amd.mapping import VoxelMap
     ref = _ref(0.4, ((0, POSE_YAW),))
-    c7 = _dev(_cloud(0))
+    c7 = dev(_cloud(0))
     maps = []
     for pts in (c7, c7[:, :4].contiguous(), c7[:, :4], c7[:, :3].contiguous(), c7[:, :3]):      # views are read in place
         vmap = VoxelMap(0.4, 1 << 14)
@@ -195,7 +192,7 @@ def test_full_table_is_a_counter_not_a_hang():
     rrows, rtags, rhits = ref.points()
     assert len(rtags) > 2 * 1024
     vmap = VoxelMap(0.4, 1024)
-    pts = _dev(_cloud(0))
+    pts = dev(_cloud(0))
     vmap.insert(pts, IDENT)
     rows, tags, hits = _got(vmap)
     st = vmap.stats()
@@ -218,7 +215,7 @@ def test_long_probe_chains_without_overflow():
     ref = _ref(0.4, ((0, IDENT),))
     assert len(ref.points()[1]) / 4096.0 > 0.7
     vmap = VoxelMap(0.4, 4096)
-    vmap.insert(_dev(_cloud(0)), IDENT)
+    vmap.insert(dev(_cloud(0)), IDENT)
     _assert_same(vmap, ref, "load 0.72")
 
 
@@ -230,11 +227,11 @@ def test_lookup_and_overlap():
     want, wtags = ref.lookup(q, POSE_YAW, return_tags=True)
     assert (want > 0).sum() > 100 and (want == 0).sum() > 100 and want[7] == -1      # partly new, one invalid point
     vmap = VoxelMap(0.4, 1 << 14)
-    vmap.insert(_dev(_cloud(0)), IDENT)
+    vmap.insert(dev(_cloud(0)), IDENT)
     before = _got(vmap)
-    hits, tags = vmap.lookup(_dev(q), _dev(POSE_YAW), return_tags=True)
+    hits, tags = vmap.lookup(dev(q), dev(POSE_YAW), return_tags=True)
     assert hits.dtype == torch.int32 and (hits.cpu().numpy() == want).all() and (tags.cpu().numpy() == wtags).all()
-    ov = vmap.overlap(_dev(q), POSE_YAW)
+    ov = vmap.overlap(dev(q), POSE_YAW)
     assert ov.is_cuda and abs(float(ov) - ref.overlap(q, POSE_YAW)) < 1e-6
     assert all(a.tobytes() == b.tobytes() for a, b in zip(before, _got(vmap)))       # read-only
     assert vmap.stats() == ref.stats()
@@ -243,9 +240,9 @@ def test_lookup_and_overlap():
     gref = VoxelMapRef(0.4, min_range=5.0, max_range=15.0)
     gref.insert(_cloud(0), IDENT)
     gmap = VoxelMap(0.4, 1 << 14, min_range=5.0, max_range=15.0)
-    gmap.insert(_dev(_cloud(0)), IDENT)
+    gmap.insert(dev(_cloud(0)), IDENT)
     want = gref.lookup(_cloud(5), IDENT)
-    assert (want == -1).sum() > 100 and (gmap.lookup(_dev(_cloud(5)), IDENT).cpu().numpy() == want).all()
+    assert (want == -1).sum() > 100 and (gmap.lookup(dev(_cloud(5)), IDENT).cpu().numpy() == want).all()
 
 
 def test_export():
@@ -253,8 +250,8 @@ def test_export():
     from rslo_amd.mapping import VoxelMap
     ref = _ref(0.4, ((0, IDENT), (5, POSE_YAW)))
     vmap = VoxelMap(0.4, 1 << 14)
-    vmap.insert(_dev(_cloud(0)), IDENT)
-    vmap.insert(_dev(_cloud(5)), POSE_YAW)
+    vmap.insert(dev(_cloud(0)), IDENT)
+    vmap.insert(dev(_cloud(5)), POSE_YAW)
     for min_hits in (1, 2, 3):
         want = ref.points(min_hits=min_hits)
         assert 0 < len(want[1]) and (min_hits == 1 or len(want[1]) < len(ref.points()[1]))
@@ -262,7 +259,7 @@ def test_export():
     center = np.array([3.0, -2.0, 0.1])
     want = ref.points(min_hits=2, center=center, radius=4.0)
     assert 10 < len(want[1]) < len(ref.points(min_hits=2)[1])
-    for c in (_dev(center), center):               # a device row, or host values
+    for c in (dev(center), center):               # a device row, or host values
         assert all(a.tobytes() == b.tobytes() for a, b in zip(_got(vmap, min_hits=2, center=c, radius=4.0), want))
     # unsorted: the same set
     rows, tags, hits = _got(vmap, sort=False)
@@ -287,13 +284,13 @@ def test_export():
 def test_reset():
     from rslo_amd.mapping import VoxelMap
     vmap = VoxelMap(0.4, 1 << 14)
-    vmap.insert(_dev(_cloud(5)), POSE_FULL)
-    vmap.insert(_dev(_cloud(5)[:0]), POSE_FULL)      # an empty scan still counts
+    vmap.insert(dev(_cloud(5)), POSE_FULL)
+    vmap.insert(dev(_cloud(5)[:0]), POSE_FULL)      # an empty scan still counts
     assert vmap.stats()["n_scans"] == 2 and vmap.stats()["n_cells"] > 0
     vmap.reset()
     assert set(vmap.stats().values()) == {0} and len(vmap.points()[1]) == 0
-    assert int((vmap.lookup(_dev(_cloud(5)), POSE_FULL) != 0).sum()) == 0
-    vmap.insert(_dev(_cloud(0)), IDENT)               # the tags start at scan 0 again
+    assert int((vmap.lookup(dev(_cloud(5)), POSE_FULL) != 0).sum()) == 0
+    vmap.insert(dev(_cloud(0)), IDENT)               # the tags start at scan 0 again
     _assert_same(vmap, _ref(0.4, ((0, IDENT),)), "after reset")
 
 
@@ -305,8 +302,8 @@ def test_argument_errors_write_nothing():
     sentinel = 0x5A5A5A5A5A5A5A5A
     buf = torch.full((nbytes // 8,), sentinel, dtype=torch.int64, device="cuda")
     p, inf = buf.data_ptr(), float("inf")
-    pts = _dev(_cloud(0)[:64, :4])
-    pose = _dev(IDENT)
+    pts = dev(_cloud(0)[:64, :4])
+    pose = dev(IDENT)
     ws = torch.empty((lib.rslo_map_insert_ws_bytes(64),), dtype=torch.uint8, device="cuda")
     rcs = [lib.rslo_map_reset(p, nbytes, 1000, 0.1, 0.0, inf, None),            # not a power of two
            lib.rslo_map_reset(p, nbytes, 1536, 0.1, 0.0, inf, None),
@@ -333,7 +330,7 @@ def test_argument_errors_write_nothing():
     with pytest.raises(ValueError):
         VoxelMap(0.0, 1024)
     with pytest.raises(capi.RsloHipError):
-        VoxelMap(0.1, 1024).insert(_dev(_cloud(0)).cpu(), IDENT)
+        VoxelMap(0.1, 1024).insert(dev(_cloud(0)).cpu(), IDENT)
     assert ctypes.sizeof(ctypes.c_size_t) == 8
 
 
@@ -342,8 +339,8 @@ def test_capture_and_replay():
     it equals two eager inserts: the scan counter lives on the device and nothing reads the host."""
     from rslo_amd.mapping import VoxelMap
     ref = _ref(0.4, ((0, IDENT), (5, POSE_YAW)))
-    clouds = [_dev(_cloud(0)[:, :4]), _dev(_cloud(5)[:, :4])]
-    poses = [_dev(IDENT), _dev(POSE_YAW)]
+    clouds = [dev(_cloud(0)[:, :4]), dev(_cloud(5)[:, :4])]
+    poses = [dev(IDENT), dev(POSE_YAW)]
     eager = VoxelMap(0.4, 1 << 14)
     for c, p in zip(clouds, poses):
         eager.insert(c, p)                          # (also the kernels' first launches, outside the capture)
@@ -371,25 +368,7 @@ N_SCANS = 3
 MAP_ARGS = dict(voxel_size=0.2, capacity=1 << 21, min_range=2.5, max_range=80.0)
 
 
-@pytest.fixture(scope="module")
-def odom():
-    from rslo_amd import synthetic, workload
-    torch.manual_seed(21)
-    net, _ = workload.build_network()
-    net.eval()
-    scans = [torch.from_numpy(synthetic.sequence_scan(i, seed=3)).cuda() for i in range(N_SCANS)]
-    workload.calibrate_head_bn(net, (scans[0], scans[1]))
-    return net, scans
-
-
-def _stream(runner, scans):
-    pend = runner.submit(scans[0])
-    for i in range(len(scans)):
-        nxt = runner.submit(scans[i + 1]) if i + 1 < len(scans) else None      # one scan ahead, as a streaming caller does
-        runner.run(pend)
-        pend = nxt
-    torch.cuda.synchronize()
-    return runner.relative().cpu().numpy(), runner.trajectory().cpu().numpy()
+odom = odom_fixture(21, 3, N_SCANS)
 
 
 def _ref_of(scans, traj):
@@ -406,14 +385,14 @@ def test_runner_fills_the_map(odom):
     net, scans = odom
     plain = inference.OdometryRunner(net)
     try:
-        rel0, traj0 = _stream(plain, scans)
+        rel0, traj0 = stream(plain, scans)
         keys0 = set(plain.stats)
     finally:
         plain.close()
     vmap = VoxelMap(**MAP_ARGS)
     runner = inference.OdometryRunner(net, voxel_map=vmap)
     try:
-        rel, traj = _stream(runner, scans)
+        rel, traj = stream(runner, scans)
         assert set(runner.stats) == keys0
         assert rel.tobytes() == rel0.tobytes() and traj.tobytes() == traj0.tobytes()      # the map disturbs nothing
         assert traj[0].tolist() == IDENT.tolist() and np.abs(traj[1:] - IDENT).max() > 0
@@ -430,7 +409,7 @@ def test_runner_fills_the_map(odom):
         assert vmap.stats()["n_cells"] >= first.stats()["n_cells"] > 10000
         runner.reset()                              # a new sequence has a new frame
         assert set(vmap.stats().values()) == {0} and len(vmap.points()[1]) == 0
-        _stream(runner, scans[:1])
+        stream(runner, scans[:1])
         _assert_same(vmap, first, "runner map after reset")
     finally:
         runner.close()
@@ -439,7 +418,7 @@ def test_runner_fills_the_map(odom):
     rmap = VoxelMap(**MAP_ARGS)
     raw = inference.OdometryRunner(net, normals="estimate", voxel_map=rmap)
     try:
-        _, rtraj = _stream(raw, raw_scans)
+        _, rtraj = stream(raw, raw_scans)
         _assert_same(rmap, _ref_of(raw_scans, rtraj), "runner map, raw scans")
         same_traj = rtraj.tobytes() == traj.tobytes()
         print("raw scans: trajectory %s the [P, 7] run's" % ("equals" if same_traj else "differs from"))

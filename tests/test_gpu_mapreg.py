@@ -13,6 +13,7 @@ The bars follow from the formats, not from what the kernels return:
 import numpy as np
 import pytest
 import torch
+from stream_support import cond_of, dev, odom_fixture, same_bits, seed_poses, stream, turned
 
 pytestmark = pytest.mark.gpu
 
@@ -41,19 +42,15 @@ def _ref(voxel, **kw):
     return _REF[key]
 
 
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
 def _map_of(voxel, capacity=1 << 14, **kw):
     from rslo_amd.mapping import VoxelMap
     vmap = VoxelMap(voxel, capacity, **kw)
-    vmap.insert(_dev(_cloud(0)), IDENT)
+    vmap.insert(dev(_cloud(0)), IDENT)
     return vmap
 
 
 def _same_nearest(vmap, ref, q, pose, label="", dev_q=None, **kw):
-    tags, d2, rows = vmap.nearest(_dev(q) if dev_q is None else dev_q, _dev(pose), return_rows=True, **kw)
+    tags, d2, rows = vmap.nearest(dev(q) if dev_q is None else dev_q, dev(pose), return_rows=True, **kw)
     wt, wd, wr = ref.nearest(q, pose, return_rows=True, **kw)
     tags, d2, rows = tags.cpu().numpy(), d2.cpu().numpy(), rows.cpu().numpy()
     print("%s: %d queries, %d matched (reference %d)" % (label, len(q), int((tags >= 0).sum()), int((wt >= 0).sum())))
@@ -96,7 +93,7 @@ def test_nearest_sizes(N):
     _same_nearest(vmap, _ref(2.0), q, POSE_FULL, "N %d, full rotation" % N)
     wt = _same_nearest(vmap, _ref(2.0), q, POSE_YAW, "N %d" % N)
     assert (wt >= 0).sum() >= (1 if N < 63 else N // 2)
-    capi.map_nearest(vmap._buf, _dev(q), _dev(POSE_YAW), 2.0, tags=sentinel[:N])       # nothing behind row N - 1
+    capi.map_nearest(vmap._buf, dev(q), dev(POSE_YAW), 2.0, tags=sentinel[:N])       # nothing behind row N - 1
     assert (sentinel[N:] == -7).all() and (sentinel[:N].cpu().numpy() == wt).all()
 
 
@@ -114,7 +111,7 @@ def test_nearest_negative_and_far_coordinates():
     cx, cy = (ref.keys >> 42) & 0x1fffff, (ref.keys >> 21) & 0x1fffff
     assert cx.max() == (1 << 21) - 1 and cx.min() == 1 and cy.max() == (1 << 21) - 1 and ref.stats()["dropped_range"] == 0
     vmap = VoxelMap(0.1, 1 << 14)
-    vmap.insert(_dev(c), IDENT)
+    vmap.insert(dev(c), IDENT)
     q = c.copy()
     q[:, :3] += np.float32(0.03)
     q[13, 0] = np.float32(2.0e5)                   # out of range itself
@@ -139,7 +136,7 @@ def test_nearest_invalid_and_gated_queries():
 def test_nearest_strided_views():
     ref = _ref(0.4)
     vmap = _map_of(0.4)
-    q7 = _dev(_cloud(5))
+    q7 = dev(_cloud(5))
     for view in (q7, q7[:, :4], q7[:, :3], q7[:, :3].contiguous()):
         _same_nearest(vmap, ref, _cloud(5), POSE_YAW, "stride %d" % view.stride(0), dev_q=view)
 
@@ -170,7 +167,7 @@ def test_nearest_overflowed_table():
         wt = _same_nearest(vmap, sub, q, pose, "overflowed table")
         assert np.isin(wt[wt >= 0], stored).all() and (wt >= 0).sum() > 100
         # d2 is exact for the returned cell: recomputed here from the exported row
-        tags, d2 = (t.cpu().numpy() for t in vmap.nearest(_dev(q), _dev(pose)))
+        tags, d2 = (t.cpu().numpy() for t in vmap.nearest(dev(q), dev(pose)))
         rows = vmap.points()[0].cpu().numpy()[np.searchsorted(stored, tags[tags >= 0])]
         d = ref._cells(q, pose)[2][tags >= 0] - rows[:, :3].astype(np.float64)
         assert ((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]).tobytes() == d2[tags >= 0].tobytes())
@@ -180,13 +177,6 @@ def test_nearest_overflowed_table():
 # the drive: scans 0 and 1 in the map under the true poses, scan 2 to be registered
 # ---------------------------------------------------------------------------------------------------------------------
 DRIVE_MAP = dict(voxel_size=0.4, min_range=2.5, max_range=80.0)
-
-
-def _turned(q, rotvec):
-    th = np.linalg.norm(rotvec)
-    dq = np.concatenate([[np.cos(th / 2)], np.sin(th / 2) / th * rotvec])
-    r = np.concatenate([[dq[0] * q[0] - dq[1:] @ q[1:]], dq[0] * q[1:] + q[0] * dq[1:] + np.cross(dq[1:], q[1:])])
-    return r / np.linalg.norm(r)
 
 
 @pytest.fixture(scope="module")
@@ -199,13 +189,13 @@ def drive():
     vmap = VoxelMap(capacity=1 << 16, **DRIVE_MAP)
     for s, p in zip(scans[:2], poses[:2]):
         ref.insert(s, p)
-        vmap.insert(_dev(s), p)
+        vmap.insert(dev(s), p)
     axis = np.array([0.3, -0.4, 0.866])
     start = np.concatenate([poses[2][:3] + 0.1 * np.array([0.6, -0.5, 0.2]),
-                            _turned(poses[2][3:], np.deg2rad(0.15) * axis / np.linalg.norm(axis))])
+                            turned(poses[2][3:], np.deg2rad(0.15) * axis / np.linalg.norm(axis))])
     tiled = np.concatenate([scans[2] + np.array([0.01 * k, -0.01 * k, 0, 0, 0, 0, 0], np.float32) for k in range(9)])
     assert vmap.stats()["dropped_full"] == 0 and vmap.stats() == ref.stats()
-    return dict(scans=scans, poses=poses, ref=ref, vmap=vmap, start=start, tiled=tiled, dev2=_dev(scans[2]))
+    return dict(scans=scans, poses=poses, ref=ref, vmap=vmap, start=start, tiled=tiled, dev2=dev(scans[2]))
 
 
 @pytest.mark.parametrize("metric", ["point", "plane"])
@@ -218,7 +208,7 @@ def test_normal_equations(drive, N, metric):
     terms = ref._pair_terms(pts, drive["start"], metric)
     K = len(terms)
     want = ref.normal_equations(pts, drive["start"], metric)
-    dpts, dpose = _dev(pts), _dev(drive["start"])
+    dpts, dpose = dev(pts), dev(drive["start"])
     got = vmap.normal_equations(dpts, dpose, metric).cpu().numpy()
     again = vmap.normal_equations(dpts, dpose, metric).cpu().numpy()
     bound = K * 2.0 ** -50 * np.abs(terms).sum(axis=0)
@@ -232,17 +222,11 @@ def test_normal_equations(drive, N, metric):
     assert got.tobytes() == again.tobytes()
 
 
-def _cond_of(sums):
-    H = np.zeros((6, 6))
-    H[np.triu_indices(6)] = sums[:21]
-    return np.linalg.cond(H + np.triu(H, 1).T)
-
-
 @pytest.mark.parametrize("metric", ["plane", "point"])
 def test_one_step_teacher_forced(drive, metric):
     """Six successive iterations; both implementations start every one of them from the DEVICE's current pose."""
     ref, vmap, pts = drive["ref"], drive["vmap"], drive["scans"][2]
-    pose = _dev(drive["start"])
+    pose = dev(drive["start"])
     worst = 0.0
     for it in range(6):
         cur = pose.cpu().numpy().copy()
@@ -251,7 +235,7 @@ def test_one_step_teacher_forced(drive, metric):
         assert out is pose                           # in place
         got, info = pose.cpu().numpy(), info.cpu().numpy()
         assert info.shape == (1, 8) and info[0, 0] == winfo[0, 0] == 0.0 and info[0, 1] == winfo[0, 1]
-        bound = 1e4 * _cond_of(ref.normal_equations(pts, cur, metric)) * 2.0 ** -52 * (1.0 + np.linalg.norm(cur[:3]))
+        bound = 1e4 * cond_of(ref.normal_equations(pts, cur, metric)) * 2.0 ** -52 * (1.0 + np.linalg.norm(cur[:3]))
         err = np.abs(got - want).max()
         worst = max(worst, err / bound)
         print("%s iteration %d: step %.3e m, |dev - ref| %.3e, bound %.3e, pairs %d" % (
@@ -264,9 +248,9 @@ def test_one_step_teacher_forced(drive, metric):
 @pytest.mark.parametrize("metric,ratio", [("plane", 0.25), ("point", 0.5)])
 def test_whole_call(drive, metric, ratio):
     vmap, pts, true = drive["vmap"], drive["dev2"], drive["poses"][2]
-    pose6 = _dev(drive["start"])
+    pose6 = dev(drive["start"])
     _, info6 = vmap.register(pts, pose6, iters=6, metric=metric)
-    pose1 = _dev(drive["start"])
+    pose1 = dev(drive["start"])
     rows = [vmap.register(pts, pose1, iters=1, metric=metric)[1] for _ in range(6)]
     after_one = None
     assert torch.equal(pose6.view(torch.int64), pose1.view(torch.int64))
@@ -276,21 +260,21 @@ def test_whole_call(drive, metric, ratio):
     print("%s: translation error %.4f -> %.4f m (ratio %.3f)" % (metric, e0, e1, e1 / e0))
     assert (info6[:, 0] == 0).all() and e1 <= ratio * e0
     # tolerances that the first step meets: the later iterations are skipped
-    after_one = _dev(drive["start"])
+    after_one = dev(drive["start"])
     vmap.register(pts, after_one, iters=1, metric=metric)
-    pose = _dev(drive["start"])
+    pose = dev(drive["start"])
     _, info = vmap.register(pts, pose, iters=4, metric=metric, tol_t=10.0, tol_r=10.0)
     assert info[:, 0].tolist() == [0.0, 3.0, 3.0, 3.0] and not info[1:, 1:].any()
     assert torch.equal(pose.view(torch.int64), after_one.view(torch.int64))
     # ... and a tolerance that is never met skips nothing, whatever the flag held before
-    pose = _dev(drive["start"])
+    pose = dev(drive["start"])
     _, info = vmap.register(pts, pose, iters=6, metric=metric, tol_t=1e-30, tol_r=1e-30)
     assert torch.equal(pose.view(torch.int64), pose6.view(torch.int64)) and (info[:, 0] == 0).all()
 
 
 def test_register_leaves_the_pose_alone(drive):
     from rslo_amd.mapping import VoxelMap
-    start = _dev(drive["start"])
+    start = dev(drive["start"])
     bits = start.view(torch.int64).clone()
     empty = VoxelMap(capacity=1024, **DRIVE_MAP)
     pose, info = empty.register(drive["dev2"], start, iters=2)
@@ -314,7 +298,7 @@ def test_argument_errors_write_nothing(drive):
     N = 500
     p, nbytes = vmap._buf.data_ptr(), vmap._buf.numel() * 8
     before = vmap._buf.clone()
-    pose = _dev(drive["start"])
+    pose = dev(drive["start"])
     S = -7.0
     tags = torch.full((N,), -7, dtype=torch.int64, device="cuda")
     d2 = torch.full((N,), S, dtype=torch.float64, device="cuda")
@@ -367,8 +351,8 @@ def test_capture_and_replay(drive):
     calls: the iteration state lives on the device and nothing reads the host."""
     vmap = drive["vmap"]
     n = min(len(drive["scans"][1]), len(drive["scans"][2]))
-    clouds = [_dev(drive["scans"][2][:n]), _dev(drive["scans"][1][:n])]
-    starts = [_dev(drive["start"]), _dev(np.concatenate([drive["poses"][1][:3] + [0.05, 0.03, -0.02], drive["poses"][1][3:]]))]
+    clouds = [dev(drive["scans"][2][:n]), dev(drive["scans"][1][:n])]
+    starts = [dev(drive["start"]), dev(np.concatenate([drive["poses"][1][:3] + [0.05, 0.03, -0.02], drive["poses"][1][3:]]))]
     eager = []
     for c, s in zip(clouds, starts):
         pose = s.clone()
@@ -399,37 +383,7 @@ MAP_ARGS = dict(voxel_size=0.2, capacity=1 << 21, min_range=2.5, max_range=80.0)
 REFINE = dict(iters=3)
 
 
-@pytest.fixture(scope="module")
-def odom():
-    from rslo_amd import synthetic, workload
-    torch.manual_seed(21)
-    net, _ = workload.build_network()
-    net.eval()
-    scans = [torch.from_numpy(synthetic.sequence_scan(i, seed=3)).cuda() for i in range(N_SCANS)]
-    workload.calibrate_head_bn(net, (scans[0], scans[1]))
-    return net, scans
-
-
-def _stream(runner, scans):
-    pend = runner.submit(scans[0])
-    for i in range(len(scans)):
-        nxt = runner.submit(scans[i + 1]) if i + 1 < len(scans) else None      # one scan ahead, as a streaming caller does
-        runner.run(pend)
-        pend = nxt
-    torch.cuda.synchronize()
-    return runner.relative().cpu().numpy(), runner.trajectory().cpu().numpy()
-
-
-def _seed_poses(rel):
-    """Where the refined chain will predict scans 1.. from an unrefined scan 0 (identity o rel[1] o ...), moved by a few
-    centimetres: copies of the scans put there give the registration of an UNTRAINED network's poses something to find
-    (its own scans do not overlap: the head's motion is metres per scan in changing directions)."""
-    from rslo_amd import inference
-    rows = rel.cpu().numpy().astype(np.float64)
-    rows[0] = IDENT
-    seeds = inference.pose_chain_host(rows)
-    seeds[:, :3] += np.array([0.05, -0.04, 0.02])
-    return seeds
+odom = odom_fixture(21, 3, N_SCANS)
 
 
 def _seed(vmap, scans, seeds):
@@ -463,16 +417,11 @@ def _stream_seeded(runner, vmap, scans, seeds):
     runner.reset()
     runner.run(runner.submit(scans[0]))
     _seed(vmap, scans, seeds)
-    _stream(runner, scans[1:])
+    stream(runner, scans[1:])
 
 
 def _same_map(a, b):
     return all(torch.equal(x, y) for x, y in zip(a.points(), b.points())) and a.stats() == b.stats()
-
-
-def _same_bits(a, b):
-    bits = torch.int64 if a.dtype == torch.float64 else torch.int32
-    return a.dtype == b.dtype and torch.equal(a.contiguous().view(bits), b.contiguous().view(bits))
 
 
 def _check_refined_chain(runner, vmap, scans, hand_refine):
@@ -486,19 +435,19 @@ def _check_refined_chain(runner, vmap, scans, hand_refine):
     assert not torch.equal(refined[1:], runner.trajectory()[1:])
     rel = runner.relative().clone()
     hand_map, hand_traj, hand_info = _replay_by_hand(scans, rel, hand_refine)
-    assert _same_bits(refined, hand_traj) and _same_bits(info, hand_info)
+    assert same_bits(refined, hand_traj) and same_bits(info, hand_info)
     assert _same_map(vmap, hand_map) and vmap.stats()["n_scans"] == N_SCANS and vmap.stats()["dropped_full"] == 0
     runner.reset()                                  # a new sequence: both chains and the map restart
     assert len(runner.refined_trajectory()) == 0 and len(runner.refine_info()) == 0 and set(vmap.stats().values()) == {0}
-    seeds = _seed_poses(rel)
+    seeds = seed_poses(rel)
     _stream_seeded(runner, vmap, scans, seeds)
-    assert _same_bits(runner.relative(), rel)
+    assert same_bits(runner.relative(), rel)
     refined, info = runner.refined_trajectory(), runner.refine_info()
     print("seeded map: status\n%s\npairs\n%s\n|dt|\n%s" % tuple(info[:, :, k].cpu().numpy() for k in (0, 1, 3)))
     assert refined[0].tolist() == IDENT.tolist() and info[0, :, 0].tolist() == [1.0] * 3
     assert (info[1:, :, 0] == 0).all() and (info[1:, :, 1] > 10000).all() and (info[1:, 0, 3] > 1e-3).all()
     hand_map, hand_traj, hand_info = _replay_by_hand(scans, rel, hand_refine, seeds)
-    assert _same_bits(refined, hand_traj) and _same_bits(info, hand_info)
+    assert same_bits(refined, hand_traj) and same_bits(info, hand_info)
     assert _same_map(vmap, hand_map) and vmap.stats()["n_scans"] == 2 * N_SCANS - 1
 
 
@@ -508,7 +457,7 @@ def test_runner_refines_against_its_map(odom):
     net, scans = odom
     plain = inference.OdometryRunner(net)
     try:
-        rel0, traj0 = _stream(plain, scans)
+        rel0, traj0 = stream(plain, scans)
         keys0 = set(plain.stats)
         with pytest.raises(capi.RsloHipError):
             plain.refined_trajectory()
@@ -521,7 +470,7 @@ def test_runner_refines_against_its_map(odom):
     vmap = VoxelMap(**MAP_ARGS)
     runner = inference.OdometryRunner(net, voxel_map=vmap, refine=REFINE)
     try:
-        rel, traj = _stream(runner, scans)
+        rel, traj = stream(runner, scans)
         assert set(runner.stats) == keys0
         assert rel.tobytes() == rel0.tobytes() and traj.tobytes() == traj0.tobytes()      # the open-loop chain is untouched
         _check_refined_chain(runner, vmap, scans, REFINE)
@@ -538,7 +487,7 @@ def test_runner_refines_raw_scans(odom):
     vmap = VoxelMap(**MAP_ARGS)
     runner = inference.OdometryRunner(net, normals="estimate", voxel_map=vmap, refine=REFINE)
     try:
-        _stream(runner, raw_scans)
+        stream(runner, raw_scans)
         _check_refined_chain(runner, vmap, raw_scans, dict(REFINE, metric="point"))
     finally:
         runner.close()

@@ -13,40 +13,13 @@ The bars are those of tests/test_gpu_mapreg.py and follow from the formats:
 import numpy as np
 import pytest
 import torch
+from stream_support import bits, cond_of, dev, disturbed, odom_fixture, same_bits, seed_poses, stream, turned
 
 pytestmark = pytest.mark.gpu
 
 DRIVE_MAP = dict(voxel_size=0.4, min_range=2.5, max_range=80.0)
 GATE = dict(min_range=2.5, max_range=80.0)
 PYRAMID = (1.6, 0.8, 0.4)
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _turned(q, rotvec):
-    th = np.linalg.norm(rotvec)
-    dq = np.concatenate([[np.cos(th / 2)], np.sin(th / 2) / th * rotvec])
-    r = np.concatenate([[dq[0] * q[0] - dq[1:] @ q[1:]], dq[0] * q[1:] + q[0] * dq[1:] + np.cross(dq[1:], q[1:])])
-    return r / np.linalg.norm(r)
-
-
-def disturbed(true_pose, off, deg):
-    """the true pose moved by `off` metres along (0.6, -0.5, 0.2) / norm and turned by `deg` degrees about
-    (0.3, -0.4, 0.866) / norm"""
-    d = np.array([0.6, -0.5, 0.2])
-    axis = np.array([0.3, -0.4, 0.866])
-    return np.concatenate([true_pose[:3] + off * d / np.linalg.norm(d),
-                           _turned(true_pose[3:], np.deg2rad(deg) * axis / np.linalg.norm(axis))])
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else torch.int32)
-
-
-def _same_bits(a, b):
-    return a.dtype == b.dtype and a.shape == b.shape and torch.equal(_bits(a), _bits(b))
 
 
 @pytest.fixture(scope="module")
@@ -66,16 +39,16 @@ def drive():
         for m in (ref, pref):
             m.insert(s, p)
         for m in (vmap, pyr):
-            m.insert(_dev(s), p)
+            m.insert(dev(s), p)
     axis = np.array([0.3, -0.4, 0.866])
     start = np.concatenate([poses[2][:3] + 0.1 * np.array([0.6, -0.5, 0.2]),
-                            _turned(poses[2][3:], np.deg2rad(0.15) * axis / np.linalg.norm(axis))])
+                            turned(poses[2][3:], np.deg2rad(0.15) * axis / np.linalg.norm(axis))])
     tiled = np.concatenate([scans[2] + np.array([0.01 * k, -0.01 * k, 0, 0, 0, 0, 0], np.float32) for k in range(9)])
     assert len(scans[2]) == 7374
     assert vmap.stats()["dropped_full"] == 0 and vmap.stats() == ref.stats()
     assert pyr.stats() == pref.stats() and all(st["dropped_full"] == 0 for st in pyr.stats())
     return dict(scans=scans, poses=poses, ref=ref, vmap=vmap, pref=pref, pyr=pyr, start=start, tiled=tiled,
-                dev2=_dev(scans[2]))
+                dev2=dev(scans[2]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -85,7 +58,7 @@ def _check_sums(ref, vmap, pts, pose, metric, scale, label):
     terms = ref._weighted_terms(pts, pose, metric, robust_scale=scale)
     K = len(terms)
     want = ref.normal_equations(pts, pose, metric, robust_scale=scale)
-    dpts, dpose = _dev(pts), _dev(pose)
+    dpts, dpose = dev(pts), dev(pose)
     got = vmap.normal_equations(dpts, dpose, metric, robust_scale=scale).cpu().numpy()
     again = vmap.normal_equations(dpts, dpose, metric, robust_scale=scale).cpu().numpy()
     bound = K * 2.0 ** -50 * np.abs(terms).sum(axis=0)
@@ -109,7 +82,7 @@ def test_weighted_normal_equations(drive, N, metric, scale):
                          "N %d %s scale %g" % (N, metric, scale))
     if N >= 1025:
         assert K > N // 2
-        plain = drive["vmap"].normal_equations(_dev(src[:N]), _dev(drive["start"]), metric).cpu().numpy()
+        plain = drive["vmap"].normal_equations(dev(src[:N]), dev(drive["start"]), metric).cpu().numpy()
         assert got[27] < plain[27] and got[28] == plain[28]      # the weights lower the cost, not the count
 
 
@@ -118,15 +91,15 @@ def test_weighted_normal_equations(drive, N, metric, scale):
 def test_scale_zero_is_the_unweighted_entry_point(drive, N, metric):
     from rslo_amd import capi
     vmap = drive["vmap"]
-    pts, pose = _dev(drive["scans"][2][:N]), _dev(drive["start"])
+    pts, pose = dev(drive["scans"][2][:N]), dev(drive["start"])
     plain = capi.map_normal_eq(vmap._buf, pts, pose, 0.4, metric)                        # rslo_map_normal_eq
     zero = capi.map_normal_eq(vmap._buf, pts, pose, 0.4, metric, robust_scale=0.0)       # rslo_map_normal_eq_w, scale 0
-    assert _same_bits(plain, zero) and plain[28] > N // 2
-    assert _same_bits(vmap.normal_equations(pts, pose, metric, robust_scale=0.0), plain)
+    assert same_bits(plain, zero) and plain[28] > N // 2
+    assert same_bits(vmap.normal_equations(pts, pose, metric, robust_scale=0.0), plain)
     a, b = pose.clone(), pose.clone()
     ia = capi.map_register(vmap._buf, pts, a, 0.4, 3, metric)                            # rslo_map_register
     ib = capi.map_register(vmap._buf, pts, b, 0.4, 3, metric, robust_scale=0.0)          # rslo_map_register_w, scale 0
-    assert _same_bits(a, b) and _same_bits(ia, ib) and not _same_bits(a, pose)
+    assert same_bits(a, b) and same_bits(ia, ib) and not same_bits(a, pose)
 
 
 def test_nan_normal_and_vanishing_weight(drive):
@@ -145,7 +118,7 @@ def test_nan_normal_and_vanishing_weight(drive):
     ident = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
     own_ref, own = VoxelMapRef(**DRIVE_MAP), VoxelMap(capacity=1 << 14, **DRIVE_MAP)
     own_ref.insert(pts, ident)
-    own.insert(_dev(pts), ident)
+    own.insert(dev(pts), ident)
     n_cells = own.stats()["n_cells"]
     got, K = _check_sums(own_ref, own, pts, ident, "point", 1e-150, "own rows, scale 1e-150")
     assert n_cells < K and got[0] == float(n_cells)      # H(0, 0) of a point term is 1: only the owners count
@@ -157,17 +130,11 @@ def test_nan_normal_and_vanishing_weight(drive):
     assert K == len(matched) and not got[:28].any()
 
 
-def _cond_of(sums):
-    H = np.zeros((6, 6))
-    H[np.triu_indices(6)] = sums[:21]
-    return np.linalg.cond(H + np.triu(H, 1).T)
-
-
 @pytest.mark.parametrize("metric,scale", [("plane", 0.2), ("point", 0.2), ("plane", 0.05)])
 def test_weighted_step_teacher_forced(drive, metric, scale):
     """Six successive weighted iterations; both implementations start every one of them from the DEVICE's current pose."""
     ref, vmap, pts = drive["ref"], drive["vmap"], drive["scans"][2]
-    pose = _dev(drive["start"])
+    pose = dev(drive["start"])
     worst = 0.0
     for it in range(6):
         cur = pose.cpu().numpy().copy()
@@ -177,7 +144,7 @@ def test_weighted_step_teacher_forced(drive, metric, scale):
         got, info = pose.cpu().numpy(), info.cpu().numpy()
         assert info.shape == (1, 8) and info[0, 0] == winfo[0, 0] == 0.0 and info[0, 1] == winfo[0, 1]
         sums = ref.normal_equations(pts, cur, metric, robust_scale=scale)
-        bound = 1e4 * _cond_of(sums) * 2.0 ** -52 * (1.0 + np.linalg.norm(cur[:3]))
+        bound = 1e4 * cond_of(sums) * 2.0 ** -52 * (1.0 + np.linalg.norm(cur[:3]))
         err = np.abs(got - want).max()
         worst = max(worst, err / bound)
         print("%s scale %g iteration %d: step %.3e m, |dev - ref| %.3e, bound %.3e, pairs %d, cost %.4f" % (
@@ -198,28 +165,28 @@ def test_schedule_equals_its_stages(drive):
     pyr, pts = drive["pyr"], drive["dev2"]
     start = disturbed(drive["poses"][2], 0.3, 0.5)
     before = [m._buf.clone() for m in pyr.levels]
-    pose = _dev(start)
+    pose = dev(start)
     out, info = pyr.register(pts, pose, SCHED, metric="plane")
     assert out is pose and info.shape == (8, 8) and info.dtype == torch.float64
-    hand = _dev(start)
+    hand = dev(start)
     rows = []
     for level, iters, md, scale in SCHED:
         rows.append(pyr.levels[level].register(pts, hand, iters=iters, metric="plane", max_dist=md, robust_scale=scale)[1])
     rows = torch.cat(rows)
-    assert _same_bits(pose, hand) and _same_bits(info[:, :5], rows[:, :5])
+    assert same_bits(pose, hand) and same_bits(info[:, :5], rows[:, :5])
     assert (info[:, 0] == 0).all() and (info[:, 1] > 1000).all()
     assert info[:, 5].tolist() == [0.0] * 3 + [1.0] * 2 + [2.0] * 3
     assert info[:, 6].tolist() == [0.0] * 3 + [1.0] * 2 + [2.0] * 3 and not info[:, 7].any()
     # the levels may come in any order and more than once
     sched = [(2, 1, None, 0.2), (0, 2, None, 0.0), (2, 2, 0.3, 0.1)]
-    pose, hand = _dev(start), _dev(start)
+    pose, hand = dev(start), dev(start)
     _, info = pyr.register(pts, pose, sched, metric="point")
     for level, iters, md, scale in sched:
         pyr.levels[level].register(pts, hand, iters=iters, metric="point", max_dist=md, robust_scale=scale)
-    assert _same_bits(pose, hand) and info[:, 6].tolist() == [2.0, 0.0, 0.0, 2.0, 2.0] and info[:, 5].tolist() == [0.0, 1.0, 1.0, 2.0, 2.0]
+    assert same_bits(pose, hand) and info[:, 6].tolist() == [2.0, 0.0, 0.0, 2.0, 2.0] and info[:, 5].tolist() == [0.0, 1.0, 1.0, 2.0, 2.0]
     # against the restatement: the device pyramid follows MapPyramidRef within what six teacher-free steps allow
     want, winfo = drive["pref"].register(drive["scans"][2], start, SCHED, metric="plane")
-    pose = _dev(start)
+    pose = dev(start)
     _, info = pyr.register(pts, pose, SCHED, metric="plane")
     assert (info[:, 1].cpu().numpy() == winfo[:, 1]).all() and (info[:, 5:].cpu().numpy() == winfo[:, 5:]).all()
     assert np.abs(pose.cpu().numpy() - want).max() < 1e-6
@@ -230,21 +197,21 @@ def test_tolerance_skips_only_its_own_stage(drive):
     pyr, pts = drive["pyr"], drive["dev2"]
     start = disturbed(drive["poses"][2], 0.3, 0.5)
     sched = [(0, 3, None, 0.0), (1, 2, None, 0.4), (2, 2, None, 0.2)]
-    pose = _dev(start)
+    pose = dev(start)
     _, info = pyr.register(pts, pose, sched, metric="plane", tol_t=10.0, tol_r=10.0)      # met by every first step
     assert info[:, 0].tolist() == [0.0, 3.0, 3.0, 0.0, 3.0, 0.0, 3.0]
     skipped = info[:, 0] == 3.0
     assert not info[skipped][:, 1:5].any()
     assert info[:, 5].tolist() == [0.0, 0.0, 0.0, 1.0, 1.0, 2.0, 2.0] and info[:, 6].tolist() == info[:, 5].tolist()
-    hand = _dev(start)
+    hand = dev(start)
     for level, _, _, scale in sched:                 # one iteration per stage is what ran
         pyr.levels[level].register(pts, hand, iters=1, metric="plane", robust_scale=scale)
-    assert _same_bits(pose, hand)
+    assert same_bits(pose, hand)
     # a tolerance that is never met skips nothing, whatever the flag held before
-    a, b = _dev(start), _dev(start)
+    a, b = dev(start), dev(start)
     _, ia = pyr.register(pts, a, sched, metric="plane", tol_t=1e-30, tol_r=1e-30)
     _, ib = pyr.register(pts, b, sched, metric="plane")
-    assert (ia[:, 0] == 0).all() and _same_bits(a, b) and _same_bits(ia, ib)
+    assert (ia[:, 0] == 0).all() and same_bits(a, b) and same_bits(ia, ib)
 
 
 def _err(pose, true):
@@ -254,8 +221,8 @@ def _err(pose, true):
 def test_basin_pyramid_without_weights(drive):
     pyr, pts, true = drive["pyr"], drive["dev2"], drive["poses"][2]
     start = disturbed(true, 1.00, 2.0)
-    pose, info = pyr.register(pts, _dev(start), [(0, 4, None, 0), (1, 4, None, 0), (2, 4, None, 0)], metric="plane")
-    fine, _ = pyr.levels[2].register(pts, _dev(start), iters=12, metric="plane")
+    pose, info = pyr.register(pts, dev(start), [(0, 4, None, 0), (1, 4, None, 0), (2, 4, None, 0)], metric="plane")
+    fine, _ = pyr.levels[2].register(pts, dev(start), iters=12, metric="plane")
     print("start 1.00 m, 2.0 deg: pyramid %.4f m, fine map alone %.4f m" % (_err(pose, true), _err(fine, true)))
     assert (info[:, 0] == 0).all()
     assert _err(pose, true) <= 0.05
@@ -265,8 +232,8 @@ def test_basin_pyramid_without_weights(drive):
 def test_basin_robust_schedule(drive):
     pyr, pts, true = drive["pyr"], drive["dev2"], drive["poses"][2]
     start = disturbed(true, 0.60, 1.0)
-    pose, info = pyr.register(pts, _dev(start), [(k, 4, None, 0.5 * v) for k, v in enumerate(PYRAMID)], metric="plane")
-    fine, _ = pyr.levels[2].register(pts, _dev(start), iters=12, metric="plane")
+    pose, info = pyr.register(pts, dev(start), [(k, 4, None, 0.5 * v) for k, v in enumerate(PYRAMID)], metric="plane")
+    fine, _ = pyr.levels[2].register(pts, dev(start), iters=12, metric="plane")
     print("start 0.60 m, 1.0 deg: robust pyramid %.4f m, fine map alone %.4f m" % (_err(pose, true), _err(fine, true)))
     assert (info[:, 0] == 0).all()
     assert _err(pose, true) <= 0.02
@@ -276,7 +243,7 @@ def test_basin_robust_schedule(drive):
 def test_schedule_leaves_the_pose_alone(drive):
     from rslo_amd.mapping import MapPyramid
     pyr, pts = drive["pyr"], drive["dev2"]
-    start = _dev(drive["start"])
+    start = dev(drive["start"])
     bits = start.view(torch.int64).clone()
     sched = [(0, 2, None, 0.0), (2, 1, None, 0.2)]
     empty = MapPyramid(PYRAMID, capacity=1024, **GATE)
@@ -305,7 +272,7 @@ def test_argument_errors_write_nothing(drive):
     N = 500
     p, nbytes = vmap._buf.data_ptr(), vmap._buf.numel() * 8
     before = [m._buf.clone() for m in pyr.levels] + [vmap._buf.clone()]
-    pose = _dev(drive["start"])
+    pose = dev(drive["start"])
     S = -7.0
     out = torch.full((29,), S, dtype=torch.float64, device="cuda")
     info = torch.full((65, 8), S, dtype=torch.float64, device="cuda")
@@ -355,7 +322,7 @@ def test_argument_errors_write_nothing(drive):
     torch.cuda.synchronize()
     assert (info[:4] != S).all() and (info[4:] == S).all()
     # the Python face refuses before anything is enqueued
-    pose = _dev(drive["start"])
+    pose = dev(drive["start"])
     for bad in ([(3, 1, None, 0.0)], [(0, 0, None, 0.0)], [(2, 1, 0.41, 0.0)], [(0, 1, None, -1.0)], [(0, 1, None, nan)], []):
         with pytest.raises(ValueError):
             pyr.register(pts, pose, bad)
@@ -374,8 +341,8 @@ def test_capture_and_replay(drive):
     scans it equals the eager calls: the stage state lives on the device and the schedule is baked into the launches."""
     pyr = drive["pyr"]
     n = min(len(drive["scans"][1]), len(drive["scans"][2]))
-    clouds = [_dev(drive["scans"][2][:n]), _dev(drive["scans"][1][:n])]
-    starts = [_dev(disturbed(drive["poses"][2], 0.3, 0.5)), _dev(disturbed(drive["poses"][1], 0.2, 0.3))]
+    clouds = [dev(drive["scans"][2][:n]), dev(drive["scans"][1][:n])]
+    starts = [dev(disturbed(drive["poses"][2], 0.3, 0.5)), dev(disturbed(drive["poses"][1], 0.2, 0.3))]
     sched = [(0, 2, None, 0.0), (1, 3, None, 0.4), (2, 3, None, 0.2)]
     kw = dict(metric="plane", tol_t=0.004, tol_r=0.004)
     eager = []
@@ -395,9 +362,9 @@ def test_capture_and_replay(drive):
         static_pts.copy_(c)
         static_pose.copy_(s)
         g.replay()
-        assert _same_bits(static_pose, pose) and _same_bits(static_info, info)
+        assert same_bits(static_pose, pose) and same_bits(static_info, info)
         assert (static_info[:, 1][static_info[:, 0] == 0] > 1000).all() and static_info[0, 0] == 0.0
-        assert not _same_bits(static_pose, s)
+        assert not same_bits(static_pose, s)
     print("statuses of the replays' last scan:", static_info[:, 0].tolist())
 
 
@@ -410,36 +377,7 @@ PYR_ARGS = dict(voxel_sizes=(0.8, 0.4, 0.2), capacity=1 << 21, min_range=2.5, ma
 RUN_SCHED = [(0, 2, None, 0.0), (2, 2, None, 0.1)]
 
 
-@pytest.fixture(scope="module")
-def odom():
-    from rslo_amd import synthetic, workload
-    torch.manual_seed(21)
-    net, _ = workload.build_network()
-    net.eval()
-    scans = [torch.from_numpy(synthetic.sequence_scan(i, seed=3)).cuda() for i in range(N_SCANS)]
-    workload.calibrate_head_bn(net, (scans[0], scans[1]))
-    return net, scans
-
-
-def _stream(runner, scans):
-    pend = runner.submit(scans[0])
-    for i in range(len(scans)):
-        nxt = runner.submit(scans[i + 1]) if i + 1 < len(scans) else None      # one scan ahead, as a streaming caller does
-        runner.run(pend)
-        pend = nxt
-    torch.cuda.synchronize()
-    return runner.relative().cpu().numpy(), runner.trajectory().cpu().numpy()
-
-
-def _seed_poses(rel):
-    """where the refined chain will predict scans 1.. from an unrefined scan 0, moved by a few centimetres: copies of
-    the scans put there give the registration of an UNTRAINED network's poses something to find"""
-    from rslo_amd import inference
-    rows = rel.cpu().numpy().astype(np.float64)
-    rows[0] = IDENT
-    seeds = inference.pose_chain_host(rows)
-    seeds[:, :3] += np.array([0.05, -0.04, 0.02])
-    return seeds
+odom = odom_fixture(21, 3, N_SCANS)
 
 
 def _replay_by_hand(scans, rel, seeds):
@@ -476,7 +414,7 @@ def test_runner_refines_against_a_pyramid(odom):
     net, scans = odom
     plain = inference.OdometryRunner(net)
     try:
-        rel0, traj0 = _stream(plain, scans)
+        rel0, traj0 = stream(plain, scans)
     finally:
         plain.close()
     single = VoxelMap(0.2, 1 << 21, min_range=2.5, max_range=80.0)
@@ -489,7 +427,7 @@ def test_runner_refines_against_a_pyramid(odom):
         inference.OdometryRunner(net, voxel_map=pyr, refine=dict(schedule=[(5, 1, None, 0.0)]))
     runner = inference.OdometryRunner(net, voxel_map=pyr, refine=dict(schedule=RUN_SCHED))
     try:
-        rel, traj = _stream(runner, scans)
+        rel, traj = stream(runner, scans)
         assert rel.tobytes() == rel0.tobytes() and traj.tobytes() == traj0.tobytes()      # the open-loop chain is untouched
         refined, info = runner.refined_trajectory(), runner.refine_info()
         assert refined.shape == (N_SCANS, 7) and info.shape == (N_SCANS, 4, 8) and info.is_cuda
@@ -503,17 +441,17 @@ def test_runner_refines_against_a_pyramid(odom):
         assert len(runner.refined_trajectory()) == 0 and len(runner.refine_info()) == 0
         assert all(set(st.values()) == {0} for st in pyr.stats())
         # a seeded map, where the registration has pairs to work on, against the replay by hand
-        seeds = _seed_poses(rel_dev)
+        seeds = seed_poses(rel_dev)
         runner.run(runner.submit(scans[0]))
         for k in range(1, N_SCANS):
             pyr.insert(scans[k], seeds[k])
-        _stream(runner, scans[1:])
-        assert _same_bits(runner.relative(), rel_dev)
+        stream(runner, scans[1:])
+        assert same_bits(runner.relative(), rel_dev)
         refined, info = runner.refined_trajectory(), runner.refine_info()
         print("seeded pyramid: status\n%s\npairs\n%s\n|dt|\n%s" % tuple(info[:, :, k].cpu().numpy() for k in (0, 1, 3)))
         assert (info[1:, :, 0] == 0).all() and (info[1:, :, 1] > 10000).all() and (info[1:, 0, 3] > 1e-3).all()
         hand_pyr, hand_traj, hand_info = _replay_by_hand(scans, rel_dev, seeds)
-        assert _same_bits(refined, hand_traj) and _same_bits(info, hand_info)
+        assert same_bits(refined, hand_traj) and same_bits(info, hand_info)
         assert _same_pyramid(pyr, hand_pyr) and all(st["n_scans"] == 2 * N_SCANS - 1 for st in pyr.stats())
     finally:
         runner.close()

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
+from stream_support import odom_fixture
 
 pytestmark = pytest.mark.gpu
 
@@ -130,15 +131,7 @@ def test_pose_chain_kernel_1000_steps():
 N_SCANS = 12
 
 
-@pytest.fixture(scope="module")
-def odom():
-    from rslo_amd import synthetic, workload
-    torch.manual_seed(21)
-    net, _ = workload.build_network()
-    net.eval()
-    scans = [torch.from_numpy(synthetic.sequence_scan(i, seed=3)).cuda() for i in range(N_SCANS)]
-    workload.calibrate_head_bn(net, (scans[0], scans[1]))
-    return net, scans
+odom = odom_fixture(21, 3, N_SCANS)
 
 
 def _eager_rel(net, a, b):

@@ -12,14 +12,11 @@ import pytest
 import torch
 
 from test_places_host import R, S, RANGE, ZOFF, edge_clouds, street_db, street_queries
+from stream_support import dev, odom_fixture, stream
 
 pytestmark = pytest.mark.gpu
 
 _CACHE = {}
-
-
-def _dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _cloud(seed=0):
@@ -56,29 +53,29 @@ def test_small_cloud_both_layouts():
     db = _db()
     c = _cloud()
     assert len(c) > 2048                                    # more than one workgroup
-    rD, _, _ = _assert_descriptor(db, _dev(c), c, "[P, 7]")
+    rD, _, _ = _assert_descriptor(db, dev(c), c, "[P, 7]")
     assert (rD > 0).sum() > 100
-    _assert_descriptor(db, _dev(c[:, :4]), c[:, :4], "[P, 4] copy")
-    _assert_descriptor(db, _dev(c)[:, :3], c[:, :3], "[P, 3] view of [P, 7]")
+    _assert_descriptor(db, dev(c[:, :4]), c[:, :4], "[P, 4] copy")
+    _assert_descriptor(db, dev(c)[:, :3], c[:, :3], "[P, 3] view of [P, 7]")
 
 
 def test_synthetic_scan():
     from rslo_amd import synthetic
     scan = synthetic.scan(720, 16, (-20.0, 0.5), 0.3, scan_seed=4)
     assert scan.shape[0] > 8000
-    rD, rkey, _ = _assert_descriptor(_db(), _dev(scan), scan, "16 x 720 scan")
+    rD, rkey, _ = _assert_descriptor(_db(), dev(scan), scan, "16 x 720 scan")
     assert (rD > 0).sum() > 200 and rkey.max() <= S
 
 
 @pytest.mark.parametrize("name", sorted(edge_clouds()))
 def test_edge_clouds(name):
     c = edge_clouds()[name]
-    _assert_descriptor(_db(), _dev(c), c, name)
+    _assert_descriptor(_db(), dev(c), c, name)
 
 
 def test_all_edge_clouds_in_one_scan():
     c = np.concatenate([edge_clouds()[k] for k in sorted(edge_clouds())] + [_cloud()[:300, :3]])
-    _assert_descriptor(_db(), _dev(c), c, "edge clouds together")
+    _assert_descriptor(_db(), dev(c), c, "edge clouds together")
 
 
 @pytest.mark.parametrize("P", [0, 1, 63, 64, 65, 257])
@@ -86,8 +83,8 @@ def test_sizes(P):
     c = _cloud()[:P, :4]
     db = _db()
     if P:
-        db.describe(_dev(_cloud(1)))                        # the buffers hold another scan's descriptor first
-    rD, rkey, rnorm = _assert_descriptor(db, _dev(c), c, "P = %d" % P)
+        db.describe(dev(_cloud(1)))                        # the buffers hold another scan's descriptor first
+    rD, rkey, rnorm = _assert_descriptor(db, dev(c), c, "P = %d" % P)
     if P == 0:
         assert not rD.any() and not rkey.any() and not rnorm.any()
 
@@ -102,7 +99,7 @@ def test_shapes(shape):
     descs = []
     for seed in range(4):
         c = _cloud(seed)
-        descs.append(_assert_descriptor(db, _dev(c), c, "R = %d, S = %d, cloud %d" % (r, s, seed)))
+        descs.append(_assert_descriptor(db, dev(c), c, "R = %d, S = %d, cloud %d" % (r, s, seed)))
         if seed < 3:
             db.add()
             ref.add(*descs[-1])
@@ -125,7 +122,7 @@ def _street():
         entries = street_db()[:30] + [zero] + street_db()[30:] + [street_db()[12]]
         for D, key, norm in entries:
             ref.add(D, key, norm)
-            db.add(_dev(D), _dev(key), _dev(norm))
+            db.add(dev(D), dev(key), dev(norm))
         queries = [q[2] for q in street_queries()[::5]] + [street_db()[12], zero]      # 3 revisits, a stored scan, zeros
         _CACHE["street"] = (db, ref, queries)
     return _CACHE["street"]
@@ -153,7 +150,7 @@ def _ref_query(qi, exclude, C, top_k):
 def test_query(C, top_k, exclude):
     db, ref, queries = _street()
     for qi, (D, key, norm) in enumerate(queries):
-        got = db.query(_dev(D), _dev(key), _dev(norm), exclude_recent=exclude, num_candidates=C, top_k=top_k).cpu().numpy()
+        got = db.query(dev(D), dev(key), dev(norm), exclude_recent=exclude, num_candidates=C, top_k=top_k).cpu().numpy()
         want = _ref_query(qi, exclude, C, top_k)
         if top_k == 5:
             print("query %d, C = %d, exclude %d: entries %s distances %s shifts %s" % (
@@ -173,20 +170,20 @@ def test_overflowing_database():
     ref = db.reference()
     for D, key, norm in street_db()[:12:2]:
         ref.add(D, key, norm)
-        db.add(_dev(D), _dev(key), _dev(norm))
+        db.add(dev(D), dev(key), dev(norm))
     st = db.stats()
     assert st["n_entries"] == 4 and st["dropped_full"] == 2 and ref.stats()["dropped_full"] == 2
     assert db.entries()[0].tobytes() == np.stack(ref.D).tobytes()
     D, key, norm = street_queries()[0][2]
     for C in (0, 2, 256):
-        got = db.query(_dev(D), _dev(key), _dev(norm), exclude_recent=1, num_candidates=C, top_k=5).cpu().numpy()
+        got = db.query(dev(D), dev(key), dev(norm), exclude_recent=1, num_candidates=C, top_k=5).cpu().numpy()
         want = ref.query(D, key, norm, exclude_recent=1, num_candidates=C, top_k=5)
         assert got.view(np.int64).tolist() == want.view(np.int64).tolist()
         n = min(C, 3) if C else 3                          # three eligible entries
         assert (want[:n, 0] >= 0).all() and (want[n:, 0] == -1).all()
     db.reset()
     assert db.stats()["n_entries"] == 0 and db.stats()["dropped_full"] == 0
-    assert (db.query(_dev(D), _dev(key), _dev(norm), top_k=2).cpu().numpy()[:, 0] == -1).all()
+    assert (db.query(dev(D), dev(key), dev(norm), top_k=2).cpu().numpy()[:, 0] == -1).all()
 
 
 def test_argument_errors_write_nothing():
@@ -200,8 +197,8 @@ def test_argument_errors_write_nothing():
     buf = torch.full((nbytes // 8,), sentinel, dtype=torch.int64, device="cuda")
     outs = torch.full((1024,), sentinel, dtype=torch.int64, device="cuda")
     p, o = buf.data_ptr(), outs.data_ptr()
-    pts = _dev(_cloud()[:64, :4])
-    tab = _dev(places.tables(R, S, RANGE))
+    pts = dev(_cloud()[:64, :4])
+    tab = dev(places.tables(R, S, RANGE))
     ws = capi.place_query_ws(8, "cuda")
     wsb = ws.numel() * 8
     D, key, norm = o, o + 5120, o + 5632
@@ -240,7 +237,7 @@ def test_argument_errors_write_nothing():
         with pytest.raises((capi.RsloHipError, ValueError)):
             _db(**bad)
     with pytest.raises(capi.RsloHipError):
-        _db().describe(_dev(_cloud()).cpu())
+        _db().describe(dev(_cloud()).cpu())
     with pytest.raises(capi.RsloHipError):
         _db().query(top_k=17)
 
@@ -260,7 +257,7 @@ def test_capture_and_replay():
     bits, which equal the restatement; two eager runs agree."""
     loop = dict(exclude_recent=1, num_candidates=2, top_k=3)
     hosts = [_cloud(seed)[:, :4] for seed in (0, 1, 2, 0)]
-    clouds = [_dev(h) for h in hosts]
+    clouds = [dev(h) for h in hosts]
     res_a, ent_a, st_a = _three_scans(_db(), clouds, loop)
     res_b, ent_b, st_b = _three_scans(_db(), clouds, loop)
     assert res_a.tobytes() == res_b.tobytes() and st_a == st_b and all(a.tobytes() == b.tobytes() for a, b in zip(ent_a, ent_b))
@@ -301,25 +298,7 @@ N_SCANS = 3
 LOOP = dict(exclude_recent=1, num_candidates=2, top_k=2)
 
 
-@pytest.fixture(scope="module")
-def odom():
-    from rslo_amd import synthetic, workload
-    torch.manual_seed(21)
-    net, _ = workload.build_network()
-    net.eval()
-    scans = [torch.from_numpy(synthetic.sequence_scan(i, seed=3)).cuda() for i in range(N_SCANS)]
-    workload.calibrate_head_bn(net, (scans[0], scans[1]))
-    return net, scans
-
-
-def _stream(runner, scans):
-    pend = runner.submit(scans[0])
-    for i in range(len(scans)):
-        nxt = runner.submit(scans[i + 1]) if i + 1 < len(scans) else None      # one scan ahead, as a streaming caller does
-        runner.run(pend)
-        pend = nxt
-    torch.cuda.synchronize()
-    return runner.relative().cpu().numpy(), runner.trajectory().cpu().numpy()
+odom = odom_fixture(21, 3, N_SCANS)
 
 
 def test_runner_records_loop_candidates(odom):
@@ -331,7 +310,7 @@ def test_runner_records_loop_candidates(odom):
             inference.OdometryRunner(net, **bad)
     plain = inference.OdometryRunner(net)
     try:
-        rel0, traj0 = _stream(plain, scans)
+        rel0, traj0 = stream(plain, scans)
         keys0 = set(plain.stats)
         with pytest.raises(capi.RsloHipError):
             plain.loop_candidates()
@@ -340,7 +319,7 @@ def test_runner_records_loop_candidates(odom):
     db = _db(capacity=16)
     runner = inference.OdometryRunner(net, places=db, loop=LOOP)
     try:
-        rel, traj = _stream(runner, scans)
+        rel, traj = stream(runner, scans)
         assert set(runner.stats) == keys0
         assert rel.tobytes() == rel0.tobytes() and traj.tobytes() == traj0.tobytes()      # the database disturbs nothing
         got = runner.loop_candidates().cpu().numpy()
@@ -358,7 +337,7 @@ def test_runner_records_loop_candidates(odom):
         assert db.entries()[0].tobytes() == np.stack(ref.D).tobytes()
         runner.reset()                                      # a new sequence has a new database
         assert db.stats()["n_entries"] == 0 and len(runner.loop_candidates()) == 0
-        _stream(runner, scans[:1])
+        stream(runner, scans[:1])
         assert db.stats()["n_entries"] == 1 and (runner.loop_candidates().cpu().numpy()[0, :, 0] == -1).all()
     finally:
         runner.close()

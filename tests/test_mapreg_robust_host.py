@@ -6,6 +6,7 @@ import math
 
 import numpy as np
 import pytest
+from stream_support import disturbed, turned
 
 IDENT = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
 POSE_YAW = np.array([1.0, -0.5, 0.1, np.cos(0.15), 0.0, 0.0, np.sin(0.15)], np.float64)
@@ -19,22 +20,6 @@ def _cloud(seed):
     if ("cloud", seed) not in _CACHE:
         _CACHE["cloud", seed] = synthetic.small_cloud(4000, seed=seed)
     return _CACHE["cloud", seed]
-
-
-def _turned(q, rotvec):
-    th = np.linalg.norm(rotvec)
-    dq = np.concatenate([[np.cos(th / 2)], np.sin(th / 2) / th * rotvec])
-    r = np.concatenate([[dq[0] * q[0] - dq[1:] @ q[1:]], dq[0] * q[1:] + q[0] * dq[1:] + np.cross(dq[1:], q[1:])])
-    return r / np.linalg.norm(r)
-
-
-def disturbed(true_pose, off, deg):
-    """the true pose moved by `off` metres along (0.6, -0.5, 0.2) / norm and turned by `deg` degrees about
-    (0.3, -0.4, 0.866) / norm"""
-    d = np.array([0.6, -0.5, 0.2])
-    axis = np.array([0.3, -0.4, 0.866])
-    return np.concatenate([true_pose[:3] + off * d / np.linalg.norm(d),
-                           _turned(true_pose[3:], np.deg2rad(deg) * axis / np.linalg.norm(axis))])
 
 
 def _drive():
@@ -162,7 +147,7 @@ def _scalar_sums(ref, scan, pose, metric, scale):
 @pytest.mark.parametrize("scale", [0.0, 0.05, 0.2, 1.0])
 def test_weight_follows_the_formula(metric, scale):
     ref, scan = _hand_map()
-    pose = np.concatenate([[0.02, -0.03, 0.01], _turned(IDENT[3:], np.array([0.004, -0.003, 0.01]))])
+    pose = np.concatenate([[0.02, -0.03, 0.01], turned(IDENT[3:], np.array([0.004, -0.003, 0.01]))])
     got = ref.normal_equations(scan, pose, metric, robust_scale=scale)
     want = _scalar_sums(ref, scan, pose, metric, scale)
     assert got[28] == want[28] == 60

@@ -1,5 +1,6 @@
 """Streaming odometry (rslo_amd.inference.OdometryRunner) on the host: the pose-chain recurrence of rslo_pose_chain, the
-BatchNorm folding of rslo_bn_fold_many and the runner's configuration checks (no GPU needed)."""
+BatchNorm folding of rslo_bn_fold_many, the runner's configuration checks and the call order of OdometryRunner.feed, the
+one submit-ahead loop, on a stand-in that only records submit() and run() (no GPU needed)."""
 import numpy as np
 import pytest
 import torch
@@ -101,3 +102,44 @@ def test_plain_eval_forward_does_not_take_the_fused_path():
     with torch.no_grad():
         out = h([x[:, :16], x[:, 16:]])
     assert len(out["translation_preds"]) == 1 and "pyramid_motion" in out
+
+
+class _Recorder:
+    def __init__(self):
+        self.calls, self.outstanding, self.most = [], set(), 0
+
+    def submit(self, cloud):
+        self.calls.append(("s", cloud))
+        self.outstanding.add(cloud)
+        self.most = max(self.most, len(self.outstanding))
+        return ("handle", cloud)
+
+    def run(self, handle):
+        tag, cloud = handle
+        assert tag == "handle" and cloud in self.outstanding      # run() gets what submit() returned, once
+        self.outstanding.remove(cloud)
+        self.calls.append(("r", cloud))
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 5])
+def test_feed_submits_one_scan_ahead(n):
+    rec = _Recorder()
+    assert inference.OdometryRunner.feed(rec, list(range(n))) is None
+    want = []                                     # s0, s1, r0, s2, r1, ..., r(n-1)
+    for i in range(n):
+        if i == 0:
+            want.append(("s", 0))
+        if i + 1 < n:
+            want.append(("s", i + 1))
+        want.append(("r", i))
+    assert rec.calls == want
+    assert [c for k, c in rec.calls if k == "r"] == list(range(n))      # every handle run exactly once, in order
+    assert not rec.outstanding and rec.most <= 2
+    if n >= 2:
+        assert rec.most == 2                      # it does submit ahead
+
+
+def test_feed_of_nothing_does_nothing():
+    rec = _Recorder()
+    inference.OdometryRunner.feed(rec, [])
+    assert rec.calls == []
