@@ -1124,7 +1124,8 @@ RSLO_API int rslo_map_register_sched(const void *const *maps /*[n_levels] host*/
  *
  * Query with (D, key, norm) of a scan, exclude_recent >= 0, num_candidates C in 0..256, top_k in 1..16:
  *   eligible: the entries with index < n_entries - exclude_recent;
- *   stage 1 (C > 0): kd = sum over r of (key_q[r] - key_e[r])^2 in integers; the C eligible entries with the smallest
+ *   stage 1 (C > 0): kd = min(sum over r of (key_q[r] - key_e[r])^2, 2^32 - 1), the sum exact for any int32 keys (a
+ *     term of |difference| >= 2^16 alone reaches the bound; nothing wraps); the C eligible entries with the smallest
  *     kd go on, ties to the lower index (composite key kd << 32 | index).  C == 0: every eligible entry goes on;
  *   stage 2: for every shift s in 0..S-1, with j' = (j + s) % S: column j is valid when norm_q[j] > 0 and
  *     norm_e[j'] > 0; dot_j = sum over r ascending of double(Dq[r,j]) * double(De[r,j']);

@@ -256,6 +256,7 @@ __device__ __forceinline__ long long place_eligible(const PlaceHdr *h, long long
 }
 
 // stage 1a: (kd << 32 | index) of every eligible entry
+// kd = min(sum of squares, 2^32 - 1) for ANY int32 keys: |d| <= 2^32 - 1; a term of |d| >= 2^16 alone reaches the clamp
 __global__ __launch_bounds__(256) void k_place_keys(void *db, size_t db_bytes, long long cap, int R, int S,
                                                     const int32_t *__restrict__ keyq, long long exclude_recent, void *ws) {
   PlaceView v;
@@ -265,7 +266,8 @@ __global__ __launch_bounds__(256) void k_place_keys(void *db, size_t db_bytes, l
   place_u64 kd = 0;
   for (int r = 0; r < R; ++r) {
     const long long d = (long long)keyq[r] - (long long)v.key[(size_t)e * R + r];
-    kd += (place_u64)(d * d);
+    const place_u64 a = (place_u64)(d < 0 ? -d : d);
+    kd += a >= 65536ull ? 0x100000000ull : a * a;      // every term <= 2^32 and R <= 64: the sum stays < 2^39
   }
   if (kd > 0xFFFFFFFFull) kd = 0xFFFFFFFFull;      // a key is a count 0..S of an honest descriptor: kd <= R * S * S < 2^21
   place_ws(ws, cap).kd[e] = (kd << 32) | (place_u64)e;

@@ -21,7 +21,8 @@ rules in one place (all arithmetic IEEE double, no fused multiply-add, unless it
   * key[r] int32 = #{j: D[r, j] > 0}; norm[j] = sqrt(sum over r ascending of double(D[r, j])^2);
   * the database appends entries; a full one drops the entry and counts it (dropped_full);
   * query: eligible = entries with index < n_entries - exclude_recent.  Stage 1 (num_candidates C > 0): the C eligible
-    entries with the smallest kd = sum_r (key_q[r] - key_e[r])^2, ties to the lower index; C = 0: all of them.  Stage 2:
+    entries with the smallest kd = min(sum_r (key_q[r] - key_e[r])^2, 2^32 - 1), the sum exact for any int32 keys,
+    ties to the lower index; C = 0: all of them.  Stage 2:
     for every shift s, j' = (j + s) % S, column j valid when norm_q[j] > 0 and norm_e[j'] > 0,
     cos_j = (sum over r ascending of double(Dq[r,j]) * double(De[r,j'])) / (norm_q[j] * norm_e[j']),
     d(s) = 1 - (sum of cos_j over valid j ascending) / n_valid (+inf without a valid column); the entry's distance is
@@ -35,6 +36,7 @@ import numpy as np
 
 TWO_PI = 2.0 * np.pi
 UNUSED_ROW = (-1.0, float("inf"), -1.0, 0.0)
+KD_MAX = (1 << 32) - 1      # the bound of a stage-1 ring-key distance
 
 
 def check_params(R, S, max_range, z_offset):
@@ -194,7 +196,8 @@ class PlaceDBRef:
         E = max(len(self.D) - int(exclude_recent), 0)
         if num_candidates == 0 or E == 0:
             return np.arange(E, dtype=np.int64)
-        kd = ((np.asarray(key, np.int64)[None, :] - np.stack(self.key[:E]).astype(np.int64)) ** 2).sum(1)
+        a = np.abs(np.asarray(key, np.int64)[None, :] - np.stack(self.key[:E]).astype(np.int64))
+        kd = np.minimum((np.minimum(a, 65536) ** 2).sum(1), KD_MAX)      # |d| >= 2^16 reaches the bound alone: nothing wraps
         order = np.lexsort((np.arange(E), kd))
         return order[:num_candidates].astype(np.int64)
 
@@ -214,7 +217,8 @@ class PlaceDBRef:
 class PlaceDB:
     """The device database: owns the allocation (rslo_place_bytes bytes), the tables, the query workspace and one set of
     descriptor buffers.  describe / add / query / reset enqueue on the current stream, read nothing on the host and
-    allocate nothing (query's result excepted, unless out= is given); stats() makes one host read."""
+    allocate nothing (query's result excepted, unless out= is given); stats() makes one host read.  add() and query()
+    take key and norm as the caller gives them: any int32 key has a defined stage-1 distance (clamped at 2^32 - 1)."""
 
     def __init__(self, capacity=8192, R=20, S=60, max_range=80.0, z_offset=2.0, device="cuda"):
         import torch

@@ -89,10 +89,11 @@ def test_sizes(P):
         assert not rD.any() and not rkey.any() and not rnorm.any()
 
 
-@pytest.mark.parametrize("shape", [(1, 3), (7, 13), (20, 60), (64, 128)])
+@pytest.mark.parametrize("shape", [(1, 3), (7, 13), (20, 60), (64, 128), (3, 16), (5, 17), (2, 32), (4, 33)])
 def test_shapes(shape):
     """every (R, S) corner: the descriptor, and a small query (S = 13: one short pass of the distance kernel, S = 128:
-    eight passes and the largest LDS image)"""
+    eight passes and the largest LDS image; S = 16, 17, 32, 33: exactly one and two passes of 16 columns, and one column
+    more)"""
     r, s = shape
     db = _db(capacity=5, R=r, S=s, max_range=25.0, z_offset=1.0)
     ref = db.reference()

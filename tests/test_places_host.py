@@ -53,6 +53,85 @@ def street_queries():
 
 _STREET = {}
 
+# ---------------------------------------------------------------------------------------------------------------------
+# a database larger than any stride of the query kernels (k_place_keys: 256 per workgroup, k_place_select: 1024 threads,
+# k_place_topk: 256 threads), shared with tests/test_gpu_places_large.py
+# ---------------------------------------------------------------------------------------------------------------------
+LARGE_N = 2100
+LARGE_SHAPES = ((7, 13), (20, 60))
+LARGE_COPIES = (0, 255, 256, 257, 1023, 1024, 1025, 2047, 2048, 2049, 2099)      # column-rolled copies of Q
+LARGE_SCALED = ((300, 0.5), (700, 0.25), (1836, 0.5))      # copies of Q with the stored norm scaled: distances -1, -3, -1
+LARGE_NEGATED = 1500                                       # -Q with the true norm: d(0) = 2, distance in (1, 2]
+LARGE_KEEP = (0.2, 0.5, 0.8)                               # P(bin filled) of a filler; one level per entry
+LARGE_SEED = {(7, 13): 2, (20, 60): 9}                     # chosen for test_large_db_has_the_cases_it_is_for
+
+
+def large_db(R, S):
+    """{D [n, R, S] f32, key [n, R] i32, norm [n, S] f64, Q: (D, key, norm), roll: {index: columns rolled}} of LARGE_N
+    entries, made once per process and never modified.  Q's level is the first of LARGE_KEEP, so a third of the fillers
+    have ring keys near Q's and the candidate cut falls among them."""
+    if (R, S) not in _LARGE:
+        rng = np.random.default_rng(LARGE_SEED[(R, S)])
+        level = rng.integers(0, 3, LARGE_N)
+        keep = rng.random((LARGE_N, R, S)) < np.array(LARGE_KEEP)[level][:, None, None]
+        D = ((0.25 + 3.0 * rng.random((LARGE_N, R, S))) * keep).astype(np.float32)
+        Q = ((0.25 + 3.0 * rng.random((R, S))) * (rng.random((R, S)) < LARGE_KEEP[0])).astype(np.float32)
+        roll = {}
+        for n, i in enumerate(LARGE_COPIES):                 # shifts 1, 4, 7, ...; the last repeats the second
+            roll[i] = (3 * n + 1) % S if n < len(LARGE_COPIES) - 1 else 4
+        for n, (i, _) in enumerate(LARGE_SCALED):
+            roll[i] = (5, 0, 2)[n]
+        for i, k in roll.items():
+            D[i] = np.roll(Q, k, axis=1)
+        D[LARGE_NEGATED] = -Q
+        kn = [places.key_and_norm(d) for d in D]
+        key, norm = np.stack([k for k, _ in kn]), np.stack([n for _, n in kn])
+        for i, f in LARGE_SCALED:
+            norm[i] = norm[i] * f                            # the API takes the norm from the caller
+        key[LARGE_NEGATED] = places.key_and_norm(Q)[0]       # ... and the key: -Q counts as Q in stage 1
+        _LARGE[(R, S)] = dict(D=D, key=key, norm=norm, Q=(Q,) + places.key_and_norm(Q), roll=roll)
+    return _LARGE[(R, S)]
+
+
+def large_ref(R, S, max_range=40.0, z_offset=2.0, tables_=None):
+    """a PlaceDBRef (capacity 2112) holding large_db(R, S); made once per process, only queried"""
+    if ("ref", R, S) not in _LARGE:
+        L = large_db(R, S)
+        ref = places.PlaceDBRef(2112, R, S, max_range, z_offset, tables_)
+        for i in range(LARGE_N):
+            ref.add(L["D"][i], L["key"][i], L["norm"][i])
+        _LARGE[("ref", R, S)] = ref
+    return _LARGE[("ref", R, S)]
+
+
+def large_queries(R, S):
+    """Q, a roll of Q, a filler entry (it finds itself) and an all-zero descriptor, as (D, key, norm)"""
+    L = large_db(R, S)
+    Qr = np.roll(L["Q"][0], 2, axis=1)
+    Z = np.zeros((R, S), np.float32)
+    return [L["Q"], (Qr,) + places.key_and_norm(Qr), (L["D"][1234], L["key"][1234], L["norm"][1234]),
+            (Z,) + places.key_and_norm(Z)]
+
+
+_LARGE = {}
+
+
+def saturation_db():
+    """(entry keys, query keys) for R = 4: ring keys no honest descriptor has, where a 64-bit sum of squares wraps (four
+    terms of (2^31)^2 are 2^64), where one term is just below / exactly at 2^16 (65535^2 < 2^32 - 1 <= 65536^2), where the
+    sum alone passes the bound, and INT32_MIN against INT32_MAX"""
+    lo, hi, b = -2 ** 31, 2 ** 31 - 1, 2 ** 30
+    entries = [[-b] * 4, [b + 1] * 4, [b] * 4, [65535, 0, 0, 0], [65536, 0, 0, 0], [65535, 363, 0, 0], [65535, 362, 0, 0],
+               [lo] * 4, [hi] * 4, [0] * 4, [-65536, 0, 0, 0], [0, 0, 0, -65535], [0, 1, 0, 65535], [hi, lo, hi, lo]]
+    queries = [[b] * 4, [0] * 4, [hi] * 4, [lo] * 4, [-1, 0, 0, 0]]
+    return entries, queries
+
+
+def saturation_order(entries, q, n=None):
+    """the stage-1 order of the first n entries by the header's rule, in Python integers"""
+    kd = [min(sum((int(a) - int(b)) ** 2 for a, b in zip(q, e)), 2 ** 32 - 1) for e in entries[:n]]
+    return sorted(range(len(kd)), key=lambda i: (kd[i], i)), kd
+
 
 def _sc():
     return places.ScanContextRef(R, S, RANGE, ZOFF)
@@ -214,3 +293,72 @@ def test_revisit_on_the_synthetic_street():
           % (hit0, hit10, shift31, min(true_d), max(true_d), min(false_d), no_sector))
     assert hit0 >= 14 and hit10 >= 14 and shift31 >= 14
     assert no_sector == 0
+
+
+def test_stage1_distance_is_total():
+    """kd = min(sum of squares, 2^32 - 1) for any int32 keys, against Python integers: the full candidate order for every
+    C, with and without excluded entries"""
+    entries, queries = saturation_db()
+    n = len(entries)
+    db = places.PlaceDBRef(16, 4, 8, 40.0, 2.0)
+    for e in entries:
+        db.add(np.zeros((4, 8), np.float32), np.array(e, np.int32), np.zeros(8))
+    top = 2 ** 32 - 1
+    for q in queries:
+        for exclude in (0, 3):
+            order, kd = saturation_order(entries, q, n - exclude)
+            print("query key %s, exclude %d: kd %s order %s" % (q, exclude, kd, order))
+            assert db.candidates(np.array(q, np.int32), exclude, 0).tolist() == list(range(n - exclude))
+            for C in range(1, n + 1):
+                assert db.candidates(np.array(q, np.int32), exclude, C).tolist() == order[:C], (q, exclude, C)
+    # what the cases are there for, in the integers of the rule
+    order, kd = saturation_order(entries, queries[0])
+    assert kd[:3] == [top, 4, 0] and order[:3] == [2, 1, 0]              # 4 * (2^31)^2 = 2^64 must not read as 0
+    assert order[3:] == list(range(3, n)) and set(kd[3:]) == {top}       # saturated entries tie: index order
+    order, kd = saturation_order(entries, queries[1])
+    assert kd[3] == 65535 ** 2 < top and kd[4] == top and 65536 ** 2 > top and kd[10] == top
+    assert kd[6] == 65535 ** 2 + 362 ** 2 < top and kd[5] == top and 65535 ** 2 + 363 ** 2 > top      # the sum passes it
+    assert order[:5] == [9, 3, 11, 12, 6]
+    for qi in (2, 3):
+        order, kd = saturation_order(entries, queries[qi])
+        assert kd[10 - qi] == 0 and kd[5 + qi] == top and sum(int(a) - int(b) for a, b in zip(
+            queries[qi], entries[5 + qi])) in (4 * (2 ** 32 - 1), -4 * (2 ** 32 - 1))      # INT32_MIN against INT32_MAX
+
+
+@pytest.mark.parametrize("shape", LARGE_SHAPES)
+def test_large_db_has_the_cases_it_is_for(shape):
+    """Properties of large_db on the restatement alone; the GPU test means nothing without them: negative distances
+    (with a tie), a run of bit-equal distances on entries of every stride, a candidate cut inside a run of equal kd."""
+    L, ref = large_db(*shape), large_ref(*shape)
+    D, key, norm = L["Q"]
+    assert ref.stats()["n_entries"] == LARGE_N and L["key"].dtype == np.int32 and L["norm"].dtype == np.float64
+    top = ref.query(D, key, norm, exclude_recent=0, num_candidates=0, top_k=16)
+    idx, d, shift = top[:, 0].astype(int).tolist(), top[:, 1], top[:, 2].astype(int).tolist()
+    print("top 16 of Q: entries %s\ndistances %s\nshifts %s" % (idx, d.tolist(), shift))
+    assert idx[:3] == [700, 300, 1836] and d[0] < d[1] < 0 and d[1:3].view(np.int64).tolist() == [d[1].view(np.int64)] * 2
+    assert abs(d[0] + 3) < 1e-14 and abs(d[1] + 1) < 1e-14
+    nc = len(LARGE_COPIES)
+    assert idx[3:3 + nc] == list(LARGE_COPIES) and len(set(d[3:3 + nc].view(np.int64).tolist())) == 1 and nc >= 8
+    assert abs(d[3]) < 1e-15 and d[3 + nc] > d[3] and (np.diff(d) >= 0).all()
+    assert {i // 1024 for i in LARGE_COPIES} == {0, 1, 2} and len({i // 256 for i in LARGE_COPIES}) >= 5
+    for stride in (256, 1024):                                 # equal distances on one thread of a kernel and on several
+        assert 1 < len({i % stride for i in LARGE_COPIES}) < nc
+    assert shift[:3 + nc] == [L["roll"][i] for i in idx[:3 + nc]]
+    rolls = [L["roll"][i] for i in LARGE_COPIES]
+    assert len(set(rolls)) == nc - 1                           # two copies share a shift
+    dn, _ = ref.distances(D, norm, [LARGE_NEGATED])
+    assert 1.0 < dn[0] <= 2.0 + 1e-14      # every cosine is negative: 2 at shift 0, the smallest d(s) still above any honest one
+    order, kd = saturation_order(L["key"].tolist(), key.tolist())
+    s = [kd[i] for i in order]
+    for C in (255, 256):
+        cand = ref.candidates(key, 0, C).tolist()
+        print("C = %d: kd at the cut %s, shared by %d entries" % (C, s[C - 2:C + 2], s.count(s[C])))
+        assert cand == order[:C]
+        assert s[C - 2] == s[C - 1] == s[C] == s[C + 1]        # >= 2 entries of the cut's kd on each side of it
+        for lo, hi in ((0, 256), (256, 1024), (1024, 2048), (2048, LARGE_N)):
+            assert any(lo <= c < hi for c in cand)
+    for D, key, norm in large_queries(*shape)[1:3]:            # the other queries see ties in kd as well
+        kd = saturation_order(L["key"].tolist(), key.tolist())[1]
+        assert len(set(kd)) < LARGE_N - 100
+    self_top = ref.query(*large_queries(*shape)[2], exclude_recent=0, num_candidates=10, top_k=1)
+    assert self_top[0, 0] == 1234 and abs(self_top[0, 1]) < 1e-15
