@@ -1257,6 +1257,95 @@ RSLO_API int rslo_posegraph_chain_solve(const double *r, double *z, int N, int L
                                         void *stream);
 RSLO_API int rslo_pose_between(const double *A, const double *B, int n, double *out /*[n,7]*/, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Loop verification (csrc/loopverify.hip): a device-resident store of down-sampled keyframes, a geometric check that
+ * turns the candidate rows of rslo_place_query into measured loop edges in ONE launch, and a device edge list that
+ * rslo_posegraph_optimize reads as it is.  The float64 restatement is rslo_amd/loops.py (KeyframeStoreRef,
+ * LoopVerifierRef): the store is compared bit for bit, the matching exactly, the sums within rounding bounds (device
+ * and host sum in different orders).  All arithmetic is IEEE double with contraction off; the pose algebra is that of
+ * the pose graph (csrc/se3.h, rslo_amd/se3.py).
+ *
+ * Keyframe store: ONE caller-owned device allocation (16-byte aligned) of rslo_keyframe_bytes(capacity, K) bytes,
+ *   header (256 bytes) | counts i32 [capacity] | rows f32 [capacity, K, 4],   sections padded to 256 bytes.
+ * Header int64 words: [0] magic, [1] capacity, [2] K, [3] 0, [4] n_entries, [5] dropped_full.  capacity is in 1 .. 2^16,
+ * K a multiple of 64 in 64 .. 4096; both are fixed by rslo_keyframe_reset, and add / verify / emit take them again and
+ * do nothing on an allocation whose header says otherwise.
+ *
+ * rslo_keyframe_prepare builds the frame [K, 4] and frame_info int32 [4] = {count, Q, flags, gated} of one scan
+ * (points[i * stride_floats + 0..2], sensor frame):
+ *   1. gate: a point is gated out (counted in `gated`) when a coordinate is not finite, when double(z) > min_z is
+ *      false, or when x*x + y*y + z*z < max_range*max_range is false (doubles, summed left to right).  The kept points
+ *      go into a [N, 3] copy in the workspace, the gated ones as NaN rows;
+ *   2. rslo_voxel_downsample (its rules, no normals) at voxel_size on that copy: Q centroid rows in its cell order.
+ *      Its overflow flag is flags bit 0, and then Q = count = 0;
+ *   3. count = min(Q, K); frame row k = down-sample row (k * Q) / K (int64, truncating) when Q > K, else row k; column
+ *      3 is 0; rows >= count are zero.
+ * rslo_keyframe_add appends (frame, count) as entry n_entries (read on the device); a full store drops it and counts
+ * dropped_full.  Two launches.  prepare: the down-sample's launches and three more (one for N == 0).
+ *
+ * rslo_loop_verify: the grid is top_k workgroups; workgroup b verifies candidate row b = (entry, distance, shift,
+ * heading) of cands [top_k, 4] against the staged query frame on its own.  out double [top_k, 16], row =
+ *   {status, entry, pairs of the last iteration, overlap, rms, query count, Z (7), distance, heading, 0}.
+ *   status 1 (no candidate): entry >= 0 and entry < n_entries is false;
+ *   status 2 (gated): distance < max_distance is false;
+ *   status 3 (too few points): the query's count or the entry's count is below min_pairs.
+ *   In these three cases the row is {status, entry as given, 0, 0, 0, 0, identity, 0, 0, 0}, the info rows are
+ *   {status, 0 ...} and matches are -1.
+ * Z is the pose of the query in the frame of the entry, p_e = Z p_q: the Z of a pose-graph loop edge (i = entry,
+ * j = query).  Start: row b of `start` [top_k, 7] when it is not NULL, else t = 0, q = (cos(h/2), 0, 0, sin(h/2)) with
+ * h = heading.  Match of source point i (< query count): w = rotate(q, p_i) + t; for every target point j (< the
+ * entry's count) m = double(row.xyz), d = w - m, d2 = d.x*d.x + d.y*d.y + d.z*d.z; the match is the j with the smallest
+ * d2, ties to the lowest j (a d2 that is NaN or +inf is never chosen), accepted iff d2 < max_dist*max_dist: the EXACT
+ * nearest point within max_dist.  stages [n_stages, 2] HOST doubles {max_dist, iters}, read at enqueue: 1 .. 8 stages,
+ * the iterations sum to 1 .. 64.  One iteration: every matched point adds the point term of "Scan-to-map
+ * registration" (J = [I | -[w]x], residual d) to the 28 sums and the pair count; fewer than min_pairs pairs, a
+ * H + damping I that is not positive definite (row-by-row Cholesky) or a step that is not finite is status 4: Z stays
+ * the last good pose, the remaining iterations are skipped (their info rows are {4, 0, 0, 0, 0, stage, 0, 0}), no
+ * fitness is taken (overlap = rms = 0, matches -1).  Otherwise the step is rslo_map_register's, update formulas
+ * included.  info double [top_k, sum of iters, 8] (may be NULL), row = {0 or 4, pairs, cost, |dt|, theta, stage, 0, 0}.
+ * Fitness at the final Z: match again with inlier_dist as the gate; overlap = inliers / query count;
+ * rms = sqrt((sum of d2 over the inliers) / inliers); matches int32 [top_k, K] (may be NULL) = the matched target index
+ * or -1 (also for i >= query count).  Status 0 (accepted) iff inliers > 0, overlap >= min_overlap and rms <= max_rms,
+ * else 5 (without an inlier overlap = rms = 0).
+ * Kernel: one workgroup of min(K, 1024) threads per candidate; the entry's frame is staged once into LDS as three
+ * float planes (12 K bytes) and every source point scans all of it in ascending j, replacing on a strict `<`: exact by
+ * construction.  The whole schedule and the fitness pass run inside the launch on a pose kept in LDS.  Sums: a thread's
+ * own points (i = thread, thread + threads, ...) in ascending order, a shuffle tree inside each wave, the waves in
+ * wave order; no floating-point atomic: two calls on the same input give the same bits, and a schedule gives the bits
+ * of its iterations issued as successive single-iteration calls chained through `start`.
+ *
+ * Edge list: ij int32 [E, 2], Z double [E, 7], w double [E, 2], counters int64 [2] = {n_edges, dropped_full}, E in
+ * 1 .. 4096.  rslo_loop_edges_reset writes i = j = -1, Z = identity, w = 0 into every row and zeroes the counters: rows
+ * rslo_posegraph_optimize skips and counts, so the whole list can be handed to it without a host read.
+ * rslo_loop_emit (one thread): among the rows of out [top_k, 16] with status 0 the one with the largest overlap wins,
+ * ties to the lowest row; it is appended as (i = entry, j = the store's n_entries now, Z, (w_t, w_r)), or counted in
+ * dropped_full when the list is full.  It runs BEFORE rslo_keyframe_add of the same scan.  At most one edge per call.
+ *
+ * Nothing here reads on the host (the stages excepted, at enqueue) or allocates: capturable.  Errors are found before
+ * the first launch and write nothing: RSLO_EINVAL for a size, count or threshold out of range (NaN included), a null
+ * or misaligned pointer, store_bytes below rslo_keyframe_bytes; RSLO_EWS for a prepare workspace (256-byte aligned)
+ * below rslo_keyframe_prepare_ws_bytes(N).  rslo_keyframe_bytes returns 0 for arguments out of range.
+ * ------------------------------------------------------------------------------------ */
+RSLO_API size_t rslo_keyframe_bytes(int64_t capacity, int K);
+RSLO_API int rslo_keyframe_reset(void *store, size_t store_bytes, int64_t capacity, int K, void *stream);
+RSLO_API size_t rslo_keyframe_prepare_ws_bytes(int N);
+RSLO_API int rslo_keyframe_prepare(const float *points, int stride_floats, int N, int K, double voxel_size, double min_z,
+                                   double max_range, float *frame /*[K,4]*/, int32_t *frame_info /*[4]*/, void *ws,
+                                   size_t ws_bytes, void *stream);
+RSLO_API int rslo_keyframe_add(void *store, size_t store_bytes, int64_t capacity, int K, const float *frame,
+                               const int32_t *frame_info, void *stream);
+RSLO_API int rslo_loop_verify(const void *store, size_t store_bytes, int64_t capacity, int K, const float *frame,
+                              const int32_t *frame_info, const double *cands /*[top_k,4]*/, int top_k,
+                              const double *start /*[top_k,7] or NULL*/, const double *stages /*[n_stages,2] host*/,
+                              int n_stages, double max_distance, double inlier_dist, double min_overlap, double max_rms,
+                              int min_pairs, double damping, double *out /*[top_k,16]*/,
+                              double *info /*[top_k,sum of iters,8] or NULL*/, int32_t *matches /*[top_k,K] or NULL*/,
+                              void *stream);
+RSLO_API int rslo_loop_edges_reset(int32_t *ij, double *Z, double *w, int64_t *counters2, int max_edges, void *stream);
+RSLO_API int rslo_loop_emit(const double *out /*[top_k,16]*/, int top_k, const void *store, size_t store_bytes,
+                            int64_t capacity, int K, int32_t *ij, double *Z, double *w, int64_t *counters2, int max_edges,
+                            double w_t, double w_r, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -225,6 +225,15 @@ SIGNATURES = {
     "rslo_posegraph_matvec": (C.c_int, [_vp, _vp, _i, _i, C.c_double, _vp, _sz, _vp]),
     "rslo_posegraph_chain_solve": (C.c_int, [_vp, _vp, _i, _i, _vp, _sz, _vp]),
     "rslo_pose_between": (C.c_int, [_vp, _vp, _i, _vp, _vp]),
+    "rslo_keyframe_bytes": (_sz, [_i64, _i]),
+    "rslo_keyframe_reset": (C.c_int, [_vp, _sz, _i64, _i, _vp]),
+    "rslo_keyframe_prepare_ws_bytes": (_sz, [_i]),
+    "rslo_keyframe_prepare": (C.c_int, [_vp, _i, _i, _i, C.c_double, C.c_double, C.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "rslo_keyframe_add": (C.c_int, [_vp, _sz, _i64, _i, _vp, _vp, _vp]),
+    "rslo_loop_verify": (C.c_int, [_vp, _sz, _i64, _i, _vp, _vp, _vp, _i, _vp, _vp, _i] + [C.c_double] * 4 +
+                         [_i, C.c_double, _vp, _vp, _vp, _vp]),
+    "rslo_loop_edges_reset": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp]),
+    "rslo_loop_emit": (C.c_int, [_vp, _i, _vp, _sz, _i64, _i, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp]),
 }
 
 
@@ -2397,3 +2406,97 @@ def pose_between(A, B, out=None):
     _chk(lib().rslo_pose_between(_ptr(A, torch.float64, "A"), _ptr(B, torch.float64, "B"), int(A.shape[0]),
                                  _ptr(out, torch.float64, "out"), _stream()), "rslo_pose_between")
     return out
+
+
+# --------------------------------------------------------------------------------------
+# loop verification (csrc/loopverify.hip); the owning classes are rslo_amd/loops.py KeyframeStore / LoopVerifier
+# --------------------------------------------------------------------------------------
+KF_HDR_ENTRIES = 4        # int64 words of a store's header: n_entries, dropped_full (include/rslo_hip.h)
+LOOP_OUT_COLS = 16
+
+
+def keyframe_bytes(capacity, K):
+    """rslo_keyframe_bytes: bytes of a store of `capacity` frames of K points; 0 for arguments out of range."""
+    return int(lib().rslo_keyframe_bytes(int(capacity), int(K)))
+
+
+def keyframe_reset(buf, capacity, K):
+    """rslo_keyframe_reset on the current stream: writes the header of an empty store."""
+    ptr, nbytes = _map_buf(buf)
+    _chk(lib().rslo_keyframe_reset(ptr, nbytes, int(capacity), int(K), _stream()), "rslo_keyframe_reset")
+
+
+def keyframe_prepare_ws(n_points, device):
+    """a workspace for keyframe_prepare on scans of up to n_points points"""
+    return torch.empty((max(int(lib().rslo_keyframe_prepare_ws_bytes(int(n_points))), 8) // 8 + 1,), dtype=torch.int64,
+                       device=device)
+
+
+def _frame(frame, info, K, name):
+    if frame.numel() != 4 * int(K) or info.numel() != 4:
+        raise RsloHipError("%s: frame must be [K, 4] float32 and frame_info [4] int32 for K = %d" % (name, K))
+    return _ptr(frame, torch.float32, "frame"), _ptr(info, torch.int32, "frame_info")
+
+
+def keyframe_prepare(points, K, voxel_size, min_z, max_range, frame, info, ws):
+    """rslo_keyframe_prepare: gate, down-sample and select one scan (fp32 CUDA [P, F >= 3], read in place) into frame
+    fp32 [K, 4] and frame_info int32 [4] = {count, Q, flags, gated}, on the current stream.  No host read."""
+    src, stride = _rows3(points, "points")
+    f, i = _frame(frame, info, K, "keyframe_prepare")
+    _chk(lib().rslo_keyframe_prepare(src, stride, int(points.shape[0]), int(K), float(voxel_size), float(min_z),
+                                     float(max_range), f, i, _ptr(ws, torch.int64, "ws"), ws.numel() * 8, _stream()),
+         "rslo_keyframe_prepare")
+
+
+def keyframe_add(buf, capacity, K, frame, info):
+    """rslo_keyframe_add: append the staged frame on the current stream (a full store counts it in dropped_full)."""
+    ptr, nbytes = _map_buf(buf)
+    f, i = _frame(frame, info, K, "keyframe_add")
+    _chk(lib().rslo_keyframe_add(ptr, nbytes, int(capacity), int(K), f, i, _stream()), "rslo_keyframe_add")
+
+
+def loop_verify(buf, capacity, K, frame, info_q, cands, top_k, start, stages, max_distance, inlier_dist, min_overlap,
+                max_rms, min_pairs, damping, out, info, matches):
+    """rslo_loop_verify on the current stream: one workgroup per row of cands float64 [top_k, 4]; out float64
+    [top_k, 16], info [top_k, sum of iters, 8] or None, matches int32 [top_k, K] or None, start [top_k, 7] or None.
+    stages: host rows (max_dist, iters)."""
+    ptr, nbytes = _map_buf(buf)
+    f, i = _frame(frame, info_q, K, "loop_verify")
+    top_k = int(top_k)
+    flat = [float(v) for st in stages for v in st]
+    n_stages = len(flat) // 2
+    total = sum(int(st[1]) for st in stages) if n_stages else 0
+    if cands.numel() != 4 * top_k or out.numel() != LOOP_OUT_COLS * top_k or (start is not None and start.numel() != 7 * top_k) \
+            or (info is not None and 1 <= total <= 64 and info.numel() != top_k * total * 8) \
+            or (matches is not None and matches.numel() != top_k * int(K)):
+        raise RsloHipError("loop_verify: cands, start, out, info or matches do not have the sizes of top_k = %d, K = %d"
+                           % (top_k, K))
+    arr = (C.c_double * max(len(flat), 1))(*flat)
+    _chk(lib().rslo_loop_verify(ptr, nbytes, int(capacity), int(K), f, i, _ptr(cands, torch.float64, "cands"), top_k,
+                                _ptr(start, torch.float64, "start"), arr, n_stages, float(max_distance), float(inlier_dist),
+                                float(min_overlap), float(max_rms), int(min_pairs), float(damping),
+                                _ptr(out, torch.float64, "out"), _ptr(info, torch.float64, "info"),
+                                _ptr(matches, torch.int32, "matches"), _stream()), "rslo_loop_verify")
+
+
+def _edges(ij, Z, w, counters, name):
+    E = int(ij.shape[0]) if ij.dim() == 2 else -1
+    if tuple(ij.shape) != (E, 2) or tuple(Z.shape) != (E, 7) or tuple(w.shape) != (E, 2) or counters.numel() != 2:
+        raise RsloHipError("%s: ij [E, 2], Z [E, 7], w [E, 2] and counters [2] must agree" % name)
+    return (_ptr(ij, torch.int32, "ij"), _ptr(Z, torch.float64, "Z"), _ptr(w, torch.float64, "w"),
+            _ptr(counters, torch.int64, "counters"), E)
+
+
+def loop_edges_reset(ij, Z, w, counters):
+    """rslo_loop_edges_reset: every row of the edge list becomes an unused one (i = j = -1), the counters zero."""
+    _chk(lib().rslo_loop_edges_reset(*_edges(ij, Z, w, counters, "loop_edges_reset"), _stream()), "rslo_loop_edges_reset")
+
+
+def loop_emit(out, top_k, buf, capacity, K, ij, Z, w, counters, w_t, w_r):
+    """rslo_loop_emit: append the best accepted row of out float64 [top_k, 16] to the edge list, on the current stream."""
+    ptr, nbytes = _map_buf(buf)
+    if out.numel() != LOOP_OUT_COLS * int(top_k):
+        raise RsloHipError("loop_emit: out must be [top_k, 16]")
+    e = _edges(ij, Z, w, counters, "loop_emit")
+    _chk(lib().rslo_loop_emit(_ptr(out, torch.float64, "out"), int(top_k), ptr, nbytes, int(capacity), int(K), *e,
+                              float(w_t), float(w_r), _stream()), "rslo_loop_emit")

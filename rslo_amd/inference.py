@@ -288,14 +288,25 @@ class OdometryRunner:
       refined_trajectory() when the runner refines, else of trajectory(), with PoseGraph.optimize's options, on the
       caller's stream; optimized_trajectory() and pose_graph_info() return the result.  trajectory(), relative() and
       refined_trajectory() stay what they are, bit for bit, and run() does not change.  Out of scope: feeding the
-      corrected poses back into the chain state or the voxel map, verifying a candidate, a keyframe store -- a loop
-      measurement is the caller's (for instance VoxelMap.register against a map of the old scans, then
-      PoseGraph.between).  None (the default): close_loops raises.
+      corrected poses back into the chain state or the voxel map.  The loop measurements are the caller's, or the
+      runner's own with verify= (next).  None (the default): close_loops raises.
+    * Loop verification: keyframes=KeyframeStore(...) (rslo_amd/loops.py, csrc/loopverify.hip) with verify=dict(...)
+      (the options of loops.check_verify -- stages, max_distance, inlier_dist, min_overlap, max_rms, min_pairs, damping
+      -- plus edge_w=(1.0, 1.0) and max_edges=256; needs places) turns the candidates into measured loop edges on the
+      device: behind places.describe / query and before places.add, run() calls keyframes.prepare(the submitted
+      tensor), verifies row n of loop_candidates() into row n of loop_checks() ([n, top_k, 16]: status, entry, pairs,
+      overlap, rms, query count, Z, distance, heading, 0) in ONE launch, emits the best accepted row into the edge list
+      loop_edges() = (ij, Z, w, counters) and then keyframes.add().  A fixed number of launches, no synchronisation,
+      nothing allocated.  close_verified_loops(**options) is close_loops on that edge list (its unused rows hold
+      i = j = -1, which the pose graph skips), with no host read.  The capacities of places and keyframes must reach
+      the runner's capacity (an entry's index is its scan's index), and max_edges must not exceed
+      pose_graph.max_loops.  keyframes= without verify= only stores the frames.  reset() empties the store and the
+      edge list.  Unknown keys are an error at construction.  verify=None (the default): today's bits.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
                  normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None,
-                 places=None, loop=None, pose_graph=None):
+                 places=None, loop=None, pose_graph=None, keyframes=None, verify=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -320,6 +331,25 @@ class OdometryRunner:
             except ValueError as e:
                 raise capi.RsloHipError("OdometryRunner: %s" % e)
             loop = dict(exclude_recent=ex, num_candidates=nc, top_k=tk)
+        edge_opts = None
+        if verify is not None:
+            from rslo_amd import loops as loops_mod
+            if places is None or keyframes is None:
+                raise capi.RsloHipError("OdometryRunner: verify needs places=PlaceDB(...) and keyframes=KeyframeStore(...)")
+            verify = dict(verify)
+            edge_w, max_edges = verify.pop("edge_w", (1.0, 1.0)), verify.pop("max_edges", 256)
+            try:
+                verify = loops_mod.check_verify(verify)
+                edge_opts = loops_mod.check_edges(max_edges, edge_w)
+            except ValueError as e:
+                raise capi.RsloHipError("OdometryRunner: %s" % e)
+            if pose_graph is not None and edge_opts[0] > pose_graph.max_loops:
+                raise capi.RsloHipError("OdometryRunner: verify max_edges = %d exceeds pose_graph.max_loops = %d"
+                                        % (edge_opts[0], pose_graph.max_loops))
+        for name, owner in (("places", places if verify is not None else None), ("keyframes", keyframes)):
+            if owner is not None and owner.capacity < int(capacity):
+                raise capi.RsloHipError("OdometryRunner: the %s capacity %d is below the runner's capacity %d (an entry's "
+                                        "index must equal its scan's index)" % (name, owner.capacity, int(capacity)))
         self.normals = normals
         self.normal_radius, self.normal_max_nn = float(normal_radius), int(normal_max_nn)
         if normals == "estimate" and not (3 <= self.normal_max_nn <= 32 and self.normal_radius > 0):
@@ -402,6 +432,17 @@ class OdometryRunner:
                 raise capi.RsloHipError("OdometryRunner: the place database lives on %s, the runner on %s" % (places.device, dev))
             places.reserve(int(point_capacity))         # run() must not allocate
             self._loop = torch.zeros((self.capacity, loop["top_k"], 4), dtype=torch.float64, device=dev)
+        self.keyframes, self.verify = keyframes, verify
+        self._verifier = self._edges = None
+        if keyframes is not None:
+            if keyframes.device != dev:
+                raise capi.RsloHipError("OdometryRunner: the keyframe store lives on %s, the runner on %s" % (keyframes.device, dev))
+            keyframes.reserve(int(point_capacity))      # run() must not allocate
+        if verify is not None:
+            from rslo_amd import loops as loops_mod
+            self._verifier = loops_mod.LoopVerifier(keyframes, **verify)
+            self._edges = loops_mod.EdgeList(edge_opts[0], edge_opts[1], device=dev)
+            self._checks = torch.zeros((self.capacity, loop["top_k"], loops_mod.OUT_COLS), dtype=torch.float64, device=dev)
         self.pose_graph = pose_graph
         self._optimized = self._pg_info = None
         if pose_graph is not None and pose_graph.device != dev:
@@ -421,7 +462,7 @@ class OdometryRunner:
             if cloud.shape[0] > self.encoder.point_capacity:
                 raise capi.RsloHipError("OdometryRunner.submit: the scan exceeds point_capacity = %d"
                                         % self.encoder.point_capacity)
-        keep = self.voxel_map is not None or self.places is not None
+        keep = self.voxel_map is not None or self.places is not None or self.keyframes is not None
         if keep and not (torch.is_tensor(cloud) and cloud.is_cuda and cloud.dtype == torch.float32 and cloud.dim() == 2):
             raise capi.RsloHipError("OdometryRunner.submit: a runner with a voxel map%s takes one fp32 CUDA [P, F] tensor"
                                     % ("" if self.places is None else " or a place database"))
@@ -461,6 +502,10 @@ class OdometryRunner:
             self._count2.zero_()
         if self.places is not None:
             self.places.reset()
+        if self.keyframes is not None:
+            self.keyframes.reset()
+        if self._edges is not None:
+            self._edges.reset()
         self._optimized = self._pg_info = None
 
     def close_loops(self, loops_ij, loops_Z, loops_w=None, **options):
@@ -475,6 +520,26 @@ class OdometryRunner:
         traj0 = self.refined_trajectory() if self.refine is not None else self.trajectory()
         self._optimized, self._pg_info = self.pose_graph.optimize(traj0, loops_ij, loops_Z, loops_w, **options)
         return self._optimized, self._pg_info
+
+    def close_verified_loops(self, **options):
+        """close_loops() on the runner's own edge list (verify=...): the whole fixed-size list goes to the pose graph,
+        which skips its unused rows; nothing is read on the host."""
+        if self._edges is None:
+            raise capi.RsloHipError("OdometryRunner.close_verified_loops: the runner was built without verify")
+        return self.close_loops(self._edges.ij, self._edges.Z, self._edges.w, **options)
+
+    def loop_checks(self):
+        """[n, top_k, 16] fp64 device rows (verify=...): LoopVerifier.verify's result of every scan's candidates."""
+        if self._verifier is None:
+            raise capi.RsloHipError("OdometryRunner.loop_checks: the runner was built without verify")
+        return self._checks[:min(self._n, self.capacity)]
+
+    def loop_edges(self):
+        """(ij int32 [E, 2], Z fp64 [E, 7], w fp64 [E, 2], counters int64 [2] = {n_edges, dropped_full}) on the device
+        (verify=...): the edges emitted so far; unused rows hold i = j = -1."""
+        if self._edges is None:
+            raise capi.RsloHipError("OdometryRunner.loop_edges: the runner was built without verify")
+        return self._edges.tensors()
 
     def optimized_trajectory(self):
         """[n, 7] fp64 device rows: the result of the last close_loops()."""
@@ -581,7 +646,16 @@ class OdometryRunner:
         if self.places is not None:         # describe -> query -> add: the scan is searched for before it is stored
             self.places.describe(handle.source)
             self.places.query(out=self._loop[n], **self.loop)
+            if self.keyframes is not None:  # prepare -> verify -> emit -> add: an edge's j is the store's count before add
+                self.keyframes.prepare(handle.source)
+                if self._verifier is not None:
+                    self._verifier.verify(self._loop[n], out=self._checks[n])
+                    self._edges.emit(self._checks[n], self.keyframes)
+                self.keyframes.add()
             self.places.add()
+        elif self.keyframes is not None:
+            self.keyframes.prepare(handle.source)
+            self.keyframes.add()
         self._n += 1
         self.stats["scans"] += 1
         return self._rel[n], self._traj[n]

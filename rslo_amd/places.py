@@ -30,7 +30,8 @@ rules in one place (all arithmetic IEEE double, no fused multiply-add, unless it
     distance, then index; entries at +inf are not returned; unused rows are (-1, +inf, -1, 0).  Column 3 is the
     query's heading relative to the entry.  No threshold: acceptance is the caller's comparison.
 
-Out of scope here: verifying a candidate geometrically, pose-graph optimisation, correcting the map, evicting entries.
+Verifying a candidate geometrically is rslo_amd/loops.py (KeyframeStore, LoopVerifier); pose-graph optimisation is
+rslo_amd/posegraph.py.  Out of scope here: correcting the map, evicting entries.
 """
 import numpy as np
 

@@ -11,6 +11,7 @@
     python scripts/odometry_stream.py --map --local-map-radius 100 --local-map-every 10 --scans 200 --warmup 20 [--out profiles/odometry_stream_local_map.json]
     python scripts/odometry_stream.py --places --scans 200 --warmup 20 [--out profiles/odometry_stream_places.json]
     python scripts/odometry_stream.py --pose-graph --scans 200 --warmup 20 [--out profiles/odometry_stream_posegraph.json]
+    python scripts/odometry_stream.py --verify --scans 200 --warmup 20 [--out profiles/odometry_stream_verify.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -183,6 +184,9 @@ def main():
     ap.add_argument("--local-map-every", type=int, default=10, help="prune every K scans")
     ap.add_argument("--places", action="store_true", help="also run the runner with a place-recognition database attached")
     ap.add_argument("--places-queries", type=int, default=20, help="revisit queries of the --places report")
+    ap.add_argument("--verify", action="store_true",
+                    help="also run the runner with a keyframe store and loop verification (implies --places)")
+    ap.add_argument("--verify-k", type=int, default=2048, help="points per keyframe of the --verify store")
     ap.add_argument("--pose-graph", action="store_true", help="close loops over the runner's trajectory and time the optimiser")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
@@ -193,6 +197,7 @@ def main():
     args = ap.parse_args()
     args.refine = args.refine or args.refine_levels is not None
     args.map = args.map or args.refine or args.local_map_radius is not None
+    args.places = args.places or args.verify
     if args.launches:
         res = launches(args.launches[0], args.launches[1], args.scans_a, args.scans_b)
         line = json.dumps(res)
@@ -274,6 +279,8 @@ def main():
         res.update(local_map_report(args, net, scans, res))
     if args.places:
         res.update(places_report(args, net, scans, res))
+    if args.verify:
+        res.update(verify_report(args, net, scans, res))
     line = json.dumps(res)
     print(line)
     if args.out:
@@ -534,6 +541,89 @@ def places_report(args, net, scans, res):
     out["places_revisit_distances_beyond_10m"] = [round(v, 4) for v in false_d]
     out["places_revisit_shifts"] = shifts
     out["places_revisit_entries_closer_than_the_true_match"] = ranks
+    args._revisit = (db, idx, jobs, qscans, poses)      # --verify runs the same queries again
+    return out
+
+
+def verify_report(args, net, scans, res):
+    """--verify: the runner with store and verifier beside the --places loop (already in `res`), the four calls alone,
+    and the revisit pass of places_report with verification"""
+    import numpy as np
+    import torch
+    from rslo_amd import inference, loops, places, se3
+    W, N = args.warmup, args.scans
+    dev = scans[0].device
+    out = {}
+    # exclude_recent = 1: on a drive without a revisit every scan still has a candidate (its neighbour but one), so every
+    # scan pays for a whole fit and the per-scan figure is the cost of verifying, not of finding nothing to verify
+    loop = dict(exclude_recent=1, num_candidates=10, top_k=1)
+    cap = max(1024, W + N)
+    db = places.PlaceDB(capacity=cap, device=dev)
+    store = loops.KeyframeStore(capacity=cap, K=args.verify_k, device=dev)
+    runner = inference.OdometryRunner(net, capacity=cap, places=db, loop=loop, keyframes=store, verify=dict())
+    out["verify_ms_per_scan"], out["verify_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(runner, scans, W, N)]
+    out["verify_minus_places_ms_per_scan"] = round(out["verify_ms_per_scan"] - res["places_ms_per_scan"], 3)
+    out["verify_minus_runner_ms_per_scan"] = round(out["verify_ms_per_scan"] - res["runner_ms_per_scan"], 3)
+    out["verify_options"] = {k: (v if k != "stages" else [list(st) for st in v]) for k, v in runner.verify.items()}
+    out["verify_loop"] = loop
+    out["verify_K"], out["verify_store_stats"] = store.K, store.stats()
+    checks = runner.loop_checks().cpu().numpy()
+    out["verify_runner_statuses"] = {loops.STATUS[k]: int((checks[:, :, 0] == k).sum()) for k in sorted(loops.STATUS)}
+    out["verify_runner_edges"] = runner.loop_edges()[3].tolist()
+    cands = runner.loop_candidates().clone()
+    runner.close()
+
+    # the four calls alone: the store holds the whole drive while it is verified against
+    ver, edges = loops.LoopVerifier(store), loops.EdgeList(256, device=dev)
+    row = torch.zeros((1, loops.OUT_COLS), dtype=torch.float64, device=dev)
+    out["verify_entries_when_verified"] = W + N
+    out["verify_prepare_ms"] = round(device_ms(lambda i: store.prepare(scans[W + i]), N), 4)
+    out["verify_verify_top1_ms"] = round(device_ms(lambda i: ver.verify(cands[W + i], out=row), N), 4)
+    out["verify_emit_ms"] = round(device_ms(lambda i: edges.emit(row, store), N), 4)
+    side = loops.KeyframeStore(capacity=cap, K=args.verify_k, device=dev)
+    side.prepare(scans[W])
+    out["verify_add_ms"] = round(device_ms(lambda i: side.add(), N), 4)
+
+    # revisit, as in places_report: three candidates of the exhaustive search per query, verified
+    pdb, idx, jobs, qscans, poses = args._revisit
+    pose7 = lambda x, y, yaw: np.array([x, y, 0.0, np.cos(0.5 * yaw), 0.0, 0.0, np.sin(0.5 * yaw)])
+    xy = np.array([p[:2] for p in poses])
+    rows3 = torch.zeros((3, loops.OUT_COLS), dtype=torch.float64, device=dev)
+    queries, accepted_true, accepted_false, rejected_true, t_err, r_err = [], 0, 0, 0, [], []
+    ms = []
+    for i, j, q in zip(idx, jobs, qscans):
+        qs = torch.from_numpy(q).to(dev)
+        D, key, norm = pdb.describe(qs)
+        top = pdb.query(D, key, norm, exclude_recent=0, num_candidates=0, top_k=3)
+        store.prepare(qs)
+        ms.append(device_ms(lambda _: ver.verify(top, out=rows3), 1))
+        got = rows3.cpu().numpy()
+        far = np.linalg.norm(xy - np.array(j[:2]), axis=1)
+        rec = []
+        for o in got:
+            e = int(o[1])
+            near = bool(e >= 0 and far[e] <= 5.0)
+            item = {"entry": e, "status": loops.STATUS[int(o[0])], "overlap": round(float(o[3]), 3), "within_5m": near}
+            if o[0] == 0:
+                truth = se3.between(pose7(*poses[e]), pose7(j[0], j[1], j[2]))
+                et = float(np.linalg.norm(o[6:9] - truth[:3]))
+                er = float(np.rad2deg(2.0 * np.arccos(min(abs(float(np.dot(o[9:13], truth[3:]))), 1.0))))
+                item["t_err_m"], item["r_err_deg"] = round(et, 4), round(er, 4)
+                if near:
+                    t_err.append(et)
+                    r_err.append(er)
+            accepted_true += bool(o[0] == 0 and near)
+            accepted_false += bool(o[0] == 0 and not near)
+            rejected_true += bool(o[0] != 0 and near)
+            rec.append(item)
+        queries.append(rec)
+    out["verify_revisit_queries"] = len(idx)
+    out["verify_revisit_top3_ms"] = round(float(np.mean(ms)), 4)
+    out["verify_revisit_accepted_within_5m"], out["verify_revisit_accepted_beyond_5m"] = accepted_true, accepted_false
+    out["verify_revisit_rejected_within_5m"] = rejected_true
+    out["verify_revisit_t_err_m_max"] = round(max(t_err), 4) if t_err else None
+    out["verify_revisit_r_err_deg_max"] = round(max(r_err), 4) if r_err else None
+    out["verify_revisit_rows"] = queries
     return out
 
 
