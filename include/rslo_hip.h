@@ -942,6 +942,28 @@ RSLO_API int rslo_voxel_downsample(const float *points, int stride_floats, const
  *                    distance of row.xyz to it (in double, summed left to right) < radius*radius.  Order unspecified.
  *                    counts = {matching, written}: rows beyond max_rows are counted, not written (max_rows = 0: the
  *                    outputs may be NULL).
+ *   rslo_map_insert_frames  every frame of a keyframe store ("Loop verification" below; store, store_bytes, capacity
+ *                    and K as handed to rslo_keyframe_reset) under a pose of its own: the map after loop closure.
+ *                    Let n = min(the store's n_entries, read on the device; n_poses).  The call leaves the map, every
+ *                    header counter and n_scans included, in the state that n successive rslo_map_insert calls would
+ *                    leave, call e = 0 .. n-1 inserting the first count_e rows of entry e as points (stride 4, width 4,
+ *                    N = count_e) under pose7 = poses + 7*e (device doubles, [n_poses, 7]).  So with S0 = n_scans on
+ *                    entry the point at row i of frame e has tag ((S0 + e) << 32) | i; an empty frame still counts as a
+ *                    scan; a pose row that is not finite drops that frame's valid points into dropped_range (its w is
+ *                    not finite); the map's range gate applies to keyframe points as to any other.  The equivalence is
+ *                    exact: the smallest tag wins and hits and counters are integer sums, so the content does not
+ *                    depend on the order of insertion.  Once dropped_full > 0 which cells are stored is unspecified,
+ *                    as above; each stored cell is still exact.  Three launches whatever the data, no workspace: one
+ *                    thread per (frame, row) in tiles of 256 rows, the grid sized from n_poses and K and held to 2048
+ *                    workgroups, which take further tiles in a loop and add their counters to the header once (tiles
+ *                    of frames >= n are not visited, threads >= count_e skip); the rows of new cells, by a pass over the
+ *                    table's SLOTS (a tag with a scan number in [S0, S0 + n) names its owner, whose position is
+ *                    recomputed from the store); n_scans += n.
+ *                    RSLO_EINVAL, before the first launch and writing nothing: a null map, store or poses; a store
+ *                    that is not 16-byte aligned; n_poses < 0; a capacity or K that rslo_keyframe_bytes refuses;
+ *                    store_bytes below rslo_keyframe_bytes(capacity, K); map_bytes below rslo_map_bytes(1024).
+ *                    n_poses == 0 is a success that launches nothing.  On a map that was never reset, or a store
+ *                    whose header disagrees with (capacity, K), the kernels do nothing.
  * All of them: everything on `stream`, no host read, nothing allocated: capturable.
  *
  * Rolling local map (rslo_map_prune): the one call that removes cells.  S = n_scans at the time of the call.  A stored
@@ -986,6 +1008,8 @@ RSLO_API int rslo_map_lookup(const void *map, size_t map_bytes, const float *poi
 RSLO_API int rslo_map_export(const void *map, size_t map_bytes, int min_hits, const double *center3 /*or NULL*/,
                              double radius, float *rows /*[max_rows,4]*/, uint64_t *tags /*[max_rows]*/,
                              int32_t *hits /*[max_rows]*/, int64_t max_rows, int64_t *counts /*[2]*/, void *stream);
+RSLO_API int rslo_map_insert_frames(void *map, size_t map_bytes, const void *store, size_t store_bytes, int64_t capacity,
+                                    int K, const double *poses /*[n_poses,7] device*/, int n_poses, void *stream);
 RSLO_API size_t rslo_map_prune_ws_bytes(int64_t capacity);
 RSLO_API int rslo_map_prune(void *map, size_t map_bytes, const double *center3 /*device, or NULL*/, double radius,
                             int min_hits, int grace, void *ws, size_t ws_bytes, void *stream);

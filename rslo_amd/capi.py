@@ -196,6 +196,7 @@ SIGNATURES = {
     "rslo_map_insert": (C.c_int, [_vp, _sz, _vp, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "rslo_map_lookup": (C.c_int, [_vp, _sz, _vp, _i, _i, _vp, _vp, _vp, _vp]),
     "rslo_map_export": (C.c_int, [_vp, _sz, _i, _vp, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "rslo_map_insert_frames": (C.c_int, [_vp, _sz, _vp, _sz, _i64, _i, _vp, _i, _vp]),
     "rslo_map_prune_ws_bytes": (_sz, [_i64]),
     "rslo_map_prune": (C.c_int, [_vp, _sz, _vp, C.c_double, _i, _i, _vp, _sz, _vp]),
     "rslo_map_params": (C.c_int, [_vp, _sz, _vp, _vp]),
@@ -1161,6 +1162,24 @@ def map_insert(buf, points, pose, ws):
     _chk(lib().rslo_map_insert(ptr, nbytes, src, stride, int(points.shape[1]), int(points.shape[0]),
                                _pose7(pose, "map_insert"), _ptr(ws), ws.numel() * ws.element_size(), _stream()),
          "rslo_map_insert")
+
+
+def map_insert_frames(buf, store_buf, capacity, K, poses):
+    """rslo_map_insert_frames on the current stream: every frame of the keyframe store store_buf (its capacity and K as
+    handed to keyframe_reset) under its own row of poses (float64 CUDA [n, 7], contiguous, read in place), as n
+    successive map_insert calls would leave the map; n is clamped to the store's entry count on the device.  Three
+    launches, no workspace, no host read."""
+    ptr, nbytes = _map_buf(buf)
+    sptr, sbytes = _map_buf(store_buf)
+    if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float64 and poses.dim() == 2
+            and poses.shape[1] == 7 and poses.is_contiguous()):
+        raise RsloHipError("map_insert_frames: poses must be contiguous float64 [n, 7] rows (t, q wxyz) on the GPU")
+    if poses.device != buf.device or store_buf.device != buf.device:
+        raise RsloHipError("map_insert_frames: the map, the store and the poses must live on one device")
+    if poses.shape[0] == 0:      # an empty tensor has no address to hand over; the call would launch nothing
+        return
+    _chk(lib().rslo_map_insert_frames(ptr, nbytes, sptr, sbytes, int(capacity), int(K), poses.data_ptr(),
+                                      int(poses.shape[0]), _stream()), "rslo_map_insert_frames")
 
 
 def map_lookup(buf, points, pose, hits=None, tags=None):

@@ -13,6 +13,8 @@
 // "empty" (then the CAS decides); a tag only decreases, so a stale read can only be too large (then the atomicMin is
 // issued needlessly).  The row of a new cell is written by the owner of its tag in the NEXT kernel of the call (slot
 // kept in the workspace), the scan counter is bumped by a third kernel after every reader of it has run.
+// rslo_map_insert_frames keeps that order for many scans at once: its second kernel walks the slots and finds the owner
+// in the tag itself, so it needs no workspace.
 // Keys DO change in a prune, but only in prune's own launches, each of which is a kernel boundary away from every other
 // user of the table: one launch reads the table and stages the kept records (the cursor is an atomic whose return value
 // is the record's place), the next empties every slot, the next re-inserts the staged records -- there, again, a key
@@ -20,11 +22,16 @@
 // last one writes the header.  Nothing here communicates across workgroups except through atomics and kernel
 // boundaries.
 #include "rslo_common.h"
+
+#include <cstddef>
+
 #include "map_table.h"
+#include "kf_store.h"            /* rslo_map_insert_frames reads a keyframe store */
 
 #pragma clang fp contract(off)   /* the cell of a point must not depend on FMA formation */
 
 #define MAP_SLOT_BYTES 36                /* key 8 + tag 8 + row 16 + hits 4 */
+#define MAP_FRAMES_BLOCKS 2048u          /* workgroups of rslo_map_insert_frames' points pass: eight per CU */
 
 static inline long long map_cap_of_bytes(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
   if (bytes < (size_t)MAP_HDR_BYTES + (size_t)MAP_SLOT_BYTES * MAP_MIN_CAP) return 0;
@@ -59,27 +66,23 @@ __global__ __launch_bounds__(256) void k_map_reset(void *map, long long cap, dou
   }
 }
 
-__global__ __launch_bounds__(256) void k_map_insert(void *map, long long cap_max, const float *__restrict__ points,
-                                                    int stride, int N, const double *__restrict__ pose,
-                                                    int32_t *__restrict__ slot_of) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  MapView m;
-  if (!map_view(map, cap_max, m)) {
-    slot_of[i] = -1;
-    return;
-  }
+// Point i of scan number `scan` (p: its x, y, z) under `pose` into the table: the slot's key, tag and hits, and the
+// five counters n_cells .. dropped_full of `c` -- the map's header itself (rslo_map_insert), or a workgroup's tally in
+// LDS that is added to the header once (rslo_map_insert_frames).  -> the slot, or -1 for a point that was dropped.
+// The one insert of both calls.
+template <class Counters>
+__device__ __forceinline__ int32_t map_put(const MapView &m, Counters *c, const float *__restrict__ p,
+                                           const double *__restrict__ pose, map_u64 scan, uint32_t i) {
   map_u64 key;
   double w[3];
-  const int why = map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w);
+  const int why = map_point(p, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w);
   if (why) {
     // both adds by every dropped lane, each to ONE address: the compiler then folds an add into one per wave.  (Given
     // `if (why == 1) add(a, 1); else add(b, 1);` it merges the two into one add whose address differs per lane, which
     // is issued lane by lane: 1.4 ms for a scan whose points are all dropped.)
-    atomicAdd(&m.hdr->dropped_invalid, (map_u64)(why == 1));
-    atomicAdd(&m.hdr->dropped_range, (map_u64)(why == 2));
-    slot_of[i] = -1;
-    return;
+    atomicAdd(&c->dropped_invalid, (map_u64)(why == 1));
+    atomicAdd(&c->dropped_range, (map_u64)(why == 2));
+    return -1;
   }
   const map_u64 mask = (map_u64)m.hdr->capacity - 1;
   map_u64 s = map_mix(key) & mask;
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(256) void k_map_insert(void *map, long long cap_max
     if (prev == MAP_KEY_NONE) {
       prev = atomicCAS(&m.keys[s], MAP_KEY_NONE, key);
       if (prev == MAP_KEY_NONE) {
-        atomicAdd(&m.hdr->n_cells, (map_u64)1);
+        atomicAdd(&c->n_cells, (map_u64)1);
         prev = key;
       }
     }
@@ -100,15 +103,27 @@ __global__ __launch_bounds__(256) void k_map_insert(void *map, long long cap_max
     s = (s + 1) & mask;
   }
   if (!found) {
-    atomicAdd(&m.hdr->dropped_full, (map_u64)1);
+    atomicAdd(&c->dropped_full, (map_u64)1);
+    return -1;
+  }
+  const map_u64 tag = (scan << 32) | (map_u64)i;
+  if (__builtin_nontemporal_load(&m.tags[s]) > tag) atomicMin(&m.tags[s], tag);
+  atomicAdd(&m.hits[s], 1);
+  atomicAdd(&c->n_points, (map_u64)1);
+  return (int32_t)s;      // capacity <= 2^31 slots (rslo_map_bytes)
+}
+
+__global__ __launch_bounds__(256) void k_map_insert(void *map, long long cap_max, const float *__restrict__ points,
+                                                    int stride, int N, const double *__restrict__ pose,
+                                                    int32_t *__restrict__ slot_of) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  MapView m;
+  if (!map_view(map, cap_max, m)) {
     slot_of[i] = -1;
     return;
   }
-  const map_u64 tag = (m.hdr->n_scans << 32) | (map_u64)(uint32_t)i;
-  if (__builtin_nontemporal_load(&m.tags[s]) > tag) atomicMin(&m.tags[s], tag);
-  atomicAdd(&m.hits[s], 1);
-  atomicAdd(&m.hdr->n_points, (map_u64)1);
-  slot_of[i] = (int32_t)s;      // capacity <= 2^31 slots (rslo_map_bytes)
+  slot_of[i] = map_put(m, m.hdr, points + (int64_t)i * stride, pose, m.hdr->n_scans, (uint32_t)i);
 }
 
 // behind the kernel boundary the tags are final for this scan: the owner of a cell's tag writes its row
@@ -132,6 +147,95 @@ __global__ __launch_bounds__(256) void k_map_rows(void *map, long long cap_max, 
 __global__ void k_map_scan_done(void *map, long long cap_max) {
   MapView m;
   if (threadIdx.x == 0 && map_view(map, cap_max, m)) m.hdr->n_scans = m.hdr->n_scans + 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rslo_map_insert_frames: every frame of a keyframe store under its own pose, as n successive inserts would leave the
+// map (rules: include/rslo_hip.h "World voxel map").  Three launches whatever the data, no workspace.
+// ---------------------------------------------------------------------------------------------------------------------
+// n = min(the store's entry count, read here and held to the store's capacity; n_poses)
+__device__ __forceinline__ long long map_frames_n(const KfView &v, int n_poses) {
+  long long n = v.hdr->n_entries;
+  n = n < 0 ? 0 : (n > v.hdr->capacity ? v.hdr->capacity : n);
+  return n < (long long)n_poses ? n : (long long)n_poses;
+}
+
+// the five header counters an insert adds to, in the header's order (n_cells .. dropped_full)
+struct MapTally {
+  map_u64 n_cells, n_points, dropped_invalid, dropped_range, dropped_full;
+};
+static_assert(offsetof(MapHdr, n_points) == offsetof(MapHdr, n_cells) + 8 &&
+              offsetof(MapHdr, dropped_invalid) == offsetof(MapHdr, n_cells) + 16 &&
+              offsetof(MapHdr, dropped_range) == offsetof(MapHdr, n_cells) + 24 &&
+              offsetof(MapHdr, dropped_full) == offsetof(MapHdr, n_cells) + 32, "MapTally mirrors the header's counters");
+
+// pass 1: one thread per (frame, row) in tiles of 256 rows, bpf tiles per frame; frame, pose and count are uniform over
+// a tile.  A workgroup takes tiles blockIdx.x, blockIdx.x + gridDim.x, ... and counts in LDS: with the header as the
+// sink every WAVE would add to the same few words, and adds to one address are served one after the other on the
+// memory side -- measured at 0.8 us per wave, 45 ms for 4096 frames -- so the header gets one add per workgroup and
+// non-zero counter.  The scan number of frame e is n_scans + e: the header's n_scans does not change before pass 3.
+__global__ __launch_bounds__(256) void k_map_frames_points(void *map, long long cap_max, void *store, size_t store_bytes,
+                                                           long long kf_cap, int K, const double *__restrict__ poses,
+                                                           int n_poses, int bpf) {
+  __shared__ MapTally tally;
+  if (threadIdx.x < 5) ((map_u64 *)&tally)[threadIdx.x] = 0;
+  __syncthreads();
+  MapView m;
+  KfView v;
+  if (!map_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;      // uniform over the grid
+  const long long tiles = map_frames_n(v, n_poses) * bpf;
+  const map_u64 s0 = m.hdr->n_scans;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long e = tile / bpf;
+    const int i = (int)(tile % bpf) * 256 + (int)threadIdx.x;
+    int count = v.counts[e];
+    count = count < 0 ? 0 : (count > K ? K : count);
+    if (i >= count) continue;
+    const float4 r = *(const float4 *)(v.rows + ((size_t)e * K + i) * 4);
+    const float p[3] = {r.x, r.y, r.z};
+    map_put(m, &tally, p, poses + (size_t)e * 7, s0 + (map_u64)e, (uint32_t)i);
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    const map_u64 add = ((map_u64 *)&tally)[threadIdx.x];
+    if (add) atomicAdd(&m.hdr->n_cells + threadIdx.x, add);
+  }
+}
+
+// pass 2, over the SLOTS: behind the kernel boundary the tags are final.  A tag whose scan number lies in
+// [n_scans, n_scans + n) was set by pass 1 (older cells carry smaller scan numbers and are never re-owned) and names
+// the point that owns the cell: frame (tag >> 32) - n_scans, row tag & 0xffffffff.  Its world position is recomputed
+// from the store by the same function that chose its cell.
+__global__ __launch_bounds__(256) void k_map_frames_rows(void *map, long long cap_max, void *store, size_t store_bytes,
+                                                         long long kf_cap, int K, const double *__restrict__ poses,
+                                                         int n_poses) {
+  MapView m;
+  KfView v;
+  if (!map_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;
+  const map_u64 n = (map_u64)map_frames_n(v, n_poses), s0 = m.hdr->n_scans;
+  const long long cap = m.hdr->capacity;
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    if (m.keys[s] == MAP_KEY_NONE) continue;
+    const map_u64 tag = m.tags[s];
+    const map_u64 scan = tag >> 32, i = tag & 0xffffffffull;
+    if (scan < s0 || scan - s0 >= n || i >= (map_u64)K) continue;      // (tag all-ones: a scan number no call reaches)
+    const map_u64 e = scan - s0;
+    const float4 r = *(const float4 *)(v.rows + ((size_t)e * K + i) * 4);
+    const float p[3] = {r.x, r.y, r.z};
+    map_u64 key;
+    double w[3];
+    if (map_point(p, poses + (size_t)e * 7, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w)) continue;
+    *(float4 *)(m.rows + (size_t)s * 4) = make_float4((float)w[0], (float)w[1], (float)w[2], r.w);
+  }
+}
+
+// pass 3: an empty frame still counts as a scan
+__global__ void k_map_frames_done(void *map, long long cap_max, void *store, size_t store_bytes, long long kf_cap, int K,
+                                  int n_poses) {
+  MapView m;
+  KfView v;
+  if (threadIdx.x != 0 || !map_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;
+  m.hdr->n_scans = m.hdr->n_scans + (map_u64)map_frames_n(v, n_poses);
 }
 
 __global__ __launch_bounds__(256) void k_map_lookup(void *map, long long cap_max, const float *__restrict__ points,
@@ -364,6 +468,32 @@ extern "C" int rslo_map_insert(void *map, size_t map_bytes, const float *points,
   }
   hipLaunchKernelGGL(k_map_scan_done, dim3(1), dim3(64), 0, s, map, cap_max);      // N == 0 still counts as a scan
   RSLO_CHECK_LAUNCH("map_insert");
+  return RSLO_OK;
+}
+
+extern "C" int rslo_map_insert_frames(void *map, size_t map_bytes, const void *store, size_t store_bytes, int64_t capacity,
+                                      int K, const double *poses, int n_poses, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = map_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "map_insert_frames: no map (map_bytes below rslo_map_bytes(1024))");
+  RSLO_CHECK_ARG(store && ((uintptr_t)store & 15) == 0, "map_insert_frames: store is null or not 16-byte aligned");
+  RSLO_CHECK_ARG(kf_shape_ok(capacity, K),
+                 "map_insert_frames: need capacity in 1 .. 2^16 and K a multiple of 64 in 64 .. 4096");
+  RSLO_CHECK_ARG(store_bytes >= kf_bytes_of(capacity, K), "map_insert_frames: store_bytes is smaller than rslo_keyframe_bytes");
+  RSLO_CHECK_ARG(poses, "map_insert_frames: poses is null");
+  RSLO_CHECK_ARG(n_poses >= 0, "map_insert_frames: n_poses < 0");
+  if (n_poses == 0) return RSLO_OK;
+  const int frames = n_poses < capacity ? n_poses : (int)capacity;      // the store holds no more
+  const int bpf = rslo_cdiv(K, 256);
+  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  const unsigned tiles = (unsigned)frames * (unsigned)bpf;      // <= 2^16 * 16
+  hipLaunchKernelGGL(k_map_frames_points, dim3(tiles < MAP_FRAMES_BLOCKS ? tiles : MAP_FRAMES_BLOCKS), dim3(256), 0, s, map,
+                     cap_max, (void *)store, store_bytes, (long long)capacity, K, poses, n_poses, bpf);
+  hipLaunchKernelGGL(k_map_frames_rows, dim3(nb), dim3(256), 0, s, map, cap_max, (void *)store, store_bytes,
+                     (long long)capacity, K, poses, n_poses);
+  hipLaunchKernelGGL(k_map_frames_done, dim3(1), dim3(64), 0, s, map, cap_max, (void *)store, store_bytes, (long long)capacity,
+                     K, n_poses);
+  RSLO_CHECK_LAUNCH("map_insert_frames");
   return RSLO_OK;
 }
 

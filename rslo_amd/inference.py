@@ -287,9 +287,9 @@ class OdometryRunner:
       what has been streamed: close_loops(loops_ij, loops_Z, loops_w=None, **options) optimises a COPY of
       refined_trajectory() when the runner refines, else of trajectory(), with PoseGraph.optimize's options, on the
       caller's stream; optimized_trajectory() and pose_graph_info() return the result.  trajectory(), relative() and
-      refined_trajectory() stay what they are, bit for bit, and run() does not change.  Out of scope: feeding the
-      corrected poses back into the chain state or the voxel map.  The loop measurements are the caller's, or the
-      runner's own with verify= (next).  None (the default): close_loops raises.
+      refined_trajectory() stay what they are, bit for bit, and run() does not change.  Feeding the corrected poses
+      back is rebuild_map() / adopt_loop_closure() (below), both opt-in.  The loop measurements are the caller's, or
+      the runner's own with verify= (next).  None (the default): close_loops raises.
     * Loop verification: keyframes=KeyframeStore(...) (rslo_amd/loops.py, csrc/loopverify.hip) with verify=dict(...)
       (the options of loops.check_verify -- stages, max_distance, inlier_dist, min_overlap, max_rms, min_pairs, damping
       -- plus edge_w=(1.0, 1.0) and max_edges=256; needs places) turns the candidates into measured loop edges on the
@@ -302,6 +302,20 @@ class OdometryRunner:
       the runner's capacity (an entry's index is its scan's index), and max_edges must not exceed
       pose_graph.max_loops.  keyframes= without verify= only stores the frames.  reset() empties the store and the
       edge list.  Unknown keys are an error at construction.  verify=None (the default): today's bits.
+    * The map after loop closure (needs keyframes=): rebuild_map(voxel_map=None, poses=None) resets the given VoxelMap
+      or MapPyramid (default: the runner's own) and fills it with every stored keyframe under its own row of poses
+      (default: optimized_trajectory()) in ONE call per level (VoxelMap.insert_frames, rslo_map_insert_frames: three
+      launches whatever the number of scans), on the caller's stream, with no host read.  The rebuilt map has the
+      density of the KEYFRAMES, not of the scans: voxel_size centroids of the store, at most K per scan, about one hit
+      per cell per frame.  A caller who refines with min_hits > 1, or wants a 0.2 m map, builds the store with
+      voxel_size=0.2, K=4096.  adopt_loop_closure() (refining runners, after close_loops() / close_verified_loops() of
+      everything streamed so far) takes the correction into the refined chain: the optimised rows replace rows
+      0 .. n-1 of refined_trajectory() (a later close_loops() would otherwise read the correction as one huge odometry
+      edge between n-1 and n), the chain's state becomes optimised row n-1, so that the next scan's prediction composes
+      onto the corrected pose, and rebuild_map() makes the runner's own map consistent before that scan is registered
+      against it: n_scans is n again, so the next insert is scan n and local_map's grace keeps its meaning.
+      trajectory(), relative(), the head graph, the place database, the keyframe store and the edge list are untouched.
+      Evicting keyframes is out of scope.  Neither method is called by run(): without them, today's bits.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
@@ -527,6 +541,38 @@ class OdometryRunner:
         if self._edges is None:
             raise capi.RsloHipError("OdometryRunner.close_verified_loops: the runner was built without verify")
         return self.close_loops(self._edges.ij, self._edges.Z, self._edges.w, **options)
+
+    def rebuild_map(self, voxel_map=None, poses=None):
+        """Reset voxel_map (a VoxelMap or MapPyramid; default: the runner's own) and insert every stored keyframe under
+        its own row of poses (float64 CUDA [m, 7]; default: optimized_trajectory()): the map the corrected trajectory
+        implies, at the density of the keyframes.  On the caller's stream, no host read.  Returns the map."""
+        if self.keyframes is None:
+            raise capi.RsloHipError("OdometryRunner.rebuild_map: the runner was built without keyframes")
+        vmap = self.voxel_map if voxel_map is None else voxel_map
+        if vmap is None:
+            raise capi.RsloHipError("OdometryRunner.rebuild_map: no voxel_map given and the runner was built without one")
+        if poses is None:
+            if self._optimized is None:
+                raise capi.RsloHipError("OdometryRunner.rebuild_map: no poses given and close_loops() has not run")
+            poses = self._optimized
+        vmap.reset()
+        vmap.insert_frames(self.keyframes, poses)
+        return vmap
+
+    def adopt_loop_closure(self):
+        """Take the last close_loops() into the refined chain (class docstring): its rows, its state, and the runner's
+        own map rebuilt from the keyframes.  The open-loop chain and everything else the runner streams stay."""
+        if self.refine is None or self.keyframes is None:
+            raise capi.RsloHipError("OdometryRunner.adopt_loop_closure: needs a runner built with refine= and keyframes=")
+        if self._optimized is None:
+            raise capi.RsloHipError("OdometryRunner.adopt_loop_closure: close_loops() has not run")
+        n = int(self._optimized.shape[0])
+        if n != self._n:
+            raise capi.RsloHipError("OdometryRunner.adopt_loop_closure: close_loops() optimised %d scans, %d have been "
+                                    "streamed; close the loops again first" % (n, self._n))
+        self._traj2[:n].copy_(self._optimized)
+        self._state2.copy_(self._optimized[n - 1])
+        self.rebuild_map()
 
     def loop_checks(self):
         """[n, top_k, 16] fp64 device rows (verify=...): LoopVerifier.verify's result of every scan's candidates."""

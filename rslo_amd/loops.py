@@ -38,7 +38,10 @@ place (all arithmetic IEEE double, no fused multiply-add; the pose algebra is se
     hold i = j = -1, which PoseGraph skips and counts.
 
 The nearest-neighbour search of the device is an exhaustive scan of the entry's frame held in LDS (exact by
-construction).  Out of scope here: feeding the corrected poses back into the chain or the map, evicting keyframes.
+construction).  The store is also what a consistent map is rebuilt from after loop closure: VoxelMap.insert_frames
+(rslo_amd/mapping.py) inserts every stored frame under its corrected pose in one call, and OdometryRunner.rebuild_map() /
+adopt_loop_closure() (rslo_amd/inference.py) feed the correction back into the map and the refined chain.  Out of scope
+here: evicting keyframes.
 """
 import numpy as np
 
@@ -434,6 +437,15 @@ class KeyframeStore:
         from rslo_amd import capi
         h = torch.cat([self._buf[capi.KF_HDR_ENTRIES:capi.KF_HDR_ENTRIES + 2], self._info.to(torch.int64)]).tolist()
         return dict(zip(("n_entries", "dropped_full", "count", "Q", "flags", "gated"), h))
+
+    def frames(self):
+        """(rows fp32 [capacity, K, 4], counts int32 [capacity]): device VIEWS of the store's sections, no copy and no
+        host read; entries >= n_entries are unspecified."""
+        import torch
+        N, K = self.capacity, self.K
+        raw = self._buf.view(torch.uint8)
+        o = 256 + (N * 4 + 255) // 256 * 256
+        return raw[o:o + N * K * 16].view(torch.float32).view(N, K, 4), raw[256:256 + N * 4].view(torch.int32)
 
     def entries(self):
         """(rows [n, K, 4], counts int32 [n]) of the stored frames, copied to the host (tests, tools)."""

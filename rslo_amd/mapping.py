@@ -21,6 +21,18 @@ the same rules on host arrays and the arbiter of the tests, which compare bit fo
     (dropped_full) -- a cell is stored completely or not at all.  VoxelMapRef has no capacity: it specifies a map that
     did not overflow.
 
+The map after loop closure, on both classes and on the pyramids (rslo_map_insert_frames):
+
+    vmap.reset(); vmap.insert_frames(store, poses)             # every keyframe of a loops.KeyframeStore under its own pose
+
+  * insert_frames(store, poses [m, 7]): n = min(the store's entry count, m); the map is left as the n calls
+    insert(rows_e[:count_e], poses[e]), e = 0 .. n-1, leave it -- VoxelMapRef.insert_frames IS that loop over a
+    KeyframeStoreRef -- so row i of frame e has tag ((S0 + e) << 32) | i with S0 = n_scans before the call, an empty
+    frame still counts as a scan, a pose row that is not finite drops its frame's valid points (dropped_range), and the
+    map's own range gate applies.  The device does it in three launches with no host read, one thread per (frame,
+    row): the content of a map does not depend on the order of insertion (the smallest tag wins, hits and counters are
+    integer sums), so the result is the loop's to the bit.  The rebuilt map has the density of the keyframes.
+
 Rolling local map (rules: include/rslo_hip.h "Rolling local map"), on both classes:
 
     vmap.prune(center=pose, radius=100.0)                      # forget what is not within 100 m of the sensor
@@ -369,6 +381,16 @@ class VoxelMapRef:
             self.rows = np.concatenate([self.rows, rows])[order]
         self.counters["n_cells"] = len(self.keys)
 
+    @staticmethod
+    def _frame_poses(store_ref, poses):
+        return np.asarray(poses, dtype=np.float64).reshape(-1, 7)
+
+    def insert_frames(self, store_ref, poses):
+        """Every frame of a loops.KeyframeStoreRef under its own row of poses [m, 7]: the definition (module docstring)."""
+        poses = self._frame_poses(store_ref, poses)
+        for e in range(min(len(store_ref.rows), len(poses))):
+            self.insert(store_ref.rows[e][:store_ref.counts[e]], poses[e])
+
     def lookup(self, points, pose=None, return_tags=False):
         status, key, _ = self._cells(points, pose)
         hits = np.full((len(status),), -1, np.int32)
@@ -609,6 +631,33 @@ class VoxelMap:
         self.reserve(points.shape[0])
         capi.map_insert(self._buf, points, self._pose(pose), self._ws)
 
+    def _frame_poses(self, store, poses):
+        """a float64 CUDA [m, 7] contiguous tensor on this map's device as it is; anything else that is not a device
+        tensor is copied to the device; a wrong device, dtype or shape is an error"""
+        import torch
+        from rslo_amd import capi
+        if store.device != self.device:
+            raise capi.RsloHipError("VoxelMap.insert_frames: the keyframe store lives on %s, the map on %s"
+                                    % (store.device, self.device))
+        if not (torch.is_tensor(poses) and poses.is_cuda):
+            host = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, dtype=np.float64)
+            if host.ndim != 2 or host.shape[1] != 7:
+                raise capi.RsloHipError("VoxelMap.insert_frames: poses must be [m, 7] rows (t, q wxyz), got %s" % (host.shape,))
+            return torch.as_tensor(np.ascontiguousarray(host)).to(self.device)
+        if poses.device != self.device:
+            raise capi.RsloHipError("VoxelMap.insert_frames: the poses live on %s, the map on %s" % (poses.device, self.device))
+        if poses.dtype != torch.float64 or poses.dim() != 2 or poses.shape[1] != 7:
+            raise capi.RsloHipError("VoxelMap.insert_frames: poses must be float64 [m, 7] rows (t, q wxyz), got %s %s"
+                                    % (poses.dtype, tuple(poses.shape)))
+        return poses.contiguous()
+
+    def insert_frames(self, store, poses):
+        """Every frame of `store` (a loops.KeyframeStore) under its own row of poses -- float64 CUDA [m, 7], contiguous:
+        read in place (optimized_trajectory() will do) -- as min(entries, m) successive insert() calls would leave the
+        map (module docstring).  Three launches on the current stream, no host read, nothing allocated: capturable."""
+        from rslo_amd import capi
+        capi.map_insert_frames(self._buf, store._buf, store.capacity, store.K, self._frame_poses(store, poses))
+
     def lookup(self, points, pose=None, return_tags=False):
         """hits int32 [P]: -1 for a skipped or out-of-range point, 0 for a cell that is not in the map, else its hits."""
         from rslo_amd import capi
@@ -728,6 +777,10 @@ class _PyramidBase:
     def insert(self, points, pose=None):
         self._each("insert", points, pose)
 
+    def insert_frames(self, store, poses):
+        """every level gets every frame of the keyframe store (the poses are checked, and copied if need be, once)"""
+        self._each("insert_frames", store, self.levels[-1]._frame_poses(store, poses))
+
     def reset(self):
         self._each("reset")
 
@@ -767,7 +820,7 @@ class _PyramidBase:
 
 class MapPyramidRef(_PyramidBase):
     """The numpy restatement of a pyramid: one VoxelMapRef per voxel size, ordered coarse to fine (.levels[k]).
-    insert / reset / prune / stats / prune_stats go to every level (stats: lists), points / save_ply / lookup / overlap
+    insert / insert_frames / reset / prune / stats / prune_stats go to every level (stats: lists), points / save_ply / lookup / overlap
     address the finest; register runs a schedule (module docstring)."""
 
     def __init__(self, voxel_sizes=(0.8, 0.4, 0.2), capacity=None, min_range=0.0, max_range=float("inf")):

@@ -30,7 +30,8 @@ in float64 numpy on host arrays and is the arbiter of the tests.  The rules in o
 Vectors over the nodes are [N, 6] with row 0 (the fixed node) zero.
 
 Loop measurements come from the caller or from rslo_amd/loops.py (a keyframe store and a geometric check whose edge list
-this optimiser reads as it is).  Out of scope here: feeding the corrected poses back into the chain state or the voxel map.
+this optimiser reads as it is).  Feeding the corrected poses back into a runner's refined chain and voxel map is
+OdometryRunner.adopt_loop_closure() / rebuild_map() (rslo_amd/inference.py, over VoxelMap.insert_frames).
 """
 import numpy as np
 
@@ -445,8 +446,8 @@ class PoseGraph:
     method enqueues on the current stream, reads nothing on the host and -- when the caller passes poses=, info= (and
     loops_w) -- allocates nothing, so a call can be captured.  All tensors are float64 CUDA, contiguous; loops_ij int32.
 
-    Out of scope: feeding the corrected poses back into a runner's chain state or voxel map.  (Verifying a loop
-    candidate and the keyframe store are rslo_amd/loops.py.)"""
+    Feeding the corrected poses back into a runner's chain state and voxel map is OdometryRunner.adopt_loop_closure() /
+    rebuild_map().  (Verifying a loop candidate and the keyframe store are rslo_amd/loops.py.)"""
 
     def __init__(self, capacity=8192, max_loops=256, device="cuda"):
         import torch

@@ -12,6 +12,7 @@
     python scripts/odometry_stream.py --places --scans 200 --warmup 20 [--out profiles/odometry_stream_places.json]
     python scripts/odometry_stream.py --pose-graph --scans 200 --warmup 20 [--out profiles/odometry_stream_posegraph.json]
     python scripts/odometry_stream.py --verify --scans 200 --warmup 20 [--out profiles/odometry_stream_verify.json]
+    python scripts/odometry_stream.py --rebuild-map --scans 200 --warmup 20 [--out profiles/odometry_stream_rebuild.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -59,6 +60,13 @@ of this script is untrained: its own trajectory is noise, and Gauss-Newton has n
 PoseGraphRef.synthetic_graph, N in {256, 1024, 4096, 8192} x L in {1, 16, 256}: per case the device-event time of
 optimize (6 Gauss-Newton iterations), of one iteration, of the edge launch with the sums (PoseGraph.cost; what is left
 of an iteration is the one-workgroup solve plus the update launch), and the CG iterations per Gauss-Newton iteration.
+--rebuild-map (implies --verify): a runner with keyframes, verification, a voxel map and a pose graph streams every scan
+and closes its verified loops; then the map is rebuilt from the keyframe store under the optimised trajectory (a) in one
+call (VoxelMap.insert_frames, rslo_map_insert_frames in csrc/map.hip) and (b) as one VoxelMap.insert per frame on views
+of the store's rows, the counts read back once outside the timed window -- the per-scan kernels, the baseline.  Each into
+a reset map, device events, one warm-up of both and then the two alternated five times: median, min and max.  The same at
+a second size: a store of 4096 entries (the streamed frames re-added) under two laps of a circle, a metre per frame.  Per
+size: frames, points, cells, dropped_full, the times, and whether the two maps are bit-equal.
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -188,6 +196,9 @@ def main():
                     help="also run the runner with a keyframe store and loop verification (implies --places)")
     ap.add_argument("--verify-k", type=int, default=2048, help="points per keyframe of the --verify store")
     ap.add_argument("--pose-graph", action="store_true", help="close loops over the runner's trajectory and time the optimiser")
+    ap.add_argument("--rebuild-map", action="store_true",
+                    help="rebuild the map from the keyframe store after loop closure: one call against one insert per frame "
+                         "(implies --verify)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -197,6 +208,7 @@ def main():
     args = ap.parse_args()
     args.refine = args.refine or args.refine_levels is not None
     args.map = args.map or args.refine or args.local_map_radius is not None
+    args.verify = args.verify or args.rebuild_map
     args.places = args.places or args.verify
     if args.launches:
         res = launches(args.launches[0], args.launches[1], args.scans_a, args.scans_b)
@@ -281,6 +293,8 @@ def main():
         res.update(places_report(args, net, scans, res))
     if args.verify:
         res.update(verify_report(args, net, scans, res))
+    if args.rebuild_map:
+        res.update(rebuild_report(args, net, scans, res))
     line = json.dumps(res)
     print(line)
     if args.out:
@@ -624,6 +638,75 @@ def verify_report(args, net, scans, res):
     out["verify_revisit_t_err_m_max"] = round(max(t_err), 4) if t_err else None
     out["verify_revisit_r_err_deg_max"] = round(max(r_err), 4) if r_err else None
     out["verify_revisit_rows"] = queries
+    return out
+
+
+def rebuild_report(args, net, scans, res):
+    """--rebuild-map: the map rebuilt from the keyframe store in one call beside the same rebuild as one insert per frame"""
+    import numpy as np
+    import torch
+    from rslo_amd import inference, loops, mapping, places, posegraph
+    dev = scans[0].device
+    n, K = len(scans), args.verify_k
+    cap = max(1024, n)
+    out = {}
+    store = loops.KeyframeStore(capacity=cap, K=K, device=dev)
+    runner = inference.OdometryRunner(net, capacity=cap, voxel_map=mapping.VoxelMap(args.map_voxel, args.map_capacity, device=dev),
+                                      places=places.PlaceDB(capacity=cap, device=dev),
+                                      loop=dict(exclude_recent=1, num_candidates=10, top_k=1), keyframes=store, verify=dict(),
+                                      pose_graph=posegraph.PoseGraph(capacity=max(8192, cap), max_loops=256, device=dev))
+    runner.feed(scans)
+    poses, _ = runner.close_verified_loops()
+    torch.cuda.synchronize()
+    out["rebuild_loop_edges"] = runner.loop_edges()[3].tolist()
+    runner.rebuild_map()                                       # the public path once, before the tables are taken apart
+    out["rebuild_runner_map_stats"] = runner.voxel_map.stats()
+    runner.close()
+
+    # the second size: 4096 entries, the streamed frames re-added under two laps of a circle, one metre per frame
+    F = 4096
+    rows, counts = store.frames()
+    infos = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+    infos[:, 0] = counts[:n]
+    big = loops.KeyframeStore(capacity=F, K=K, device=dev)
+    for e in range(F):
+        big.add(rows[e % n], infos[e % n])
+    a = 2.0 * (2.0 * np.pi) * np.arange(F) / F
+    R = F / (2.0 * 2.0 * np.pi)
+    lap = np.stack([R * np.sin(a), R * (1.0 - np.cos(a)), np.zeros(F), np.cos(a / 2), np.zeros(F), np.zeros(F), np.sin(a / 2)], 1)
+    reps = 5
+    for name, st, P in (("streamed", store, poses), ("4096", big, torch.from_numpy(lap).to(dev))):
+        m = int(P.shape[0])
+        slots = args.map_capacity
+        while slots < 2 * m * K:                               # room for every point in a cell of its own at half load
+            slots *= 2
+        one, per = (mapping.VoxelMap(args.map_voxel, slots, device=dev) for _ in range(2))
+        per.reserve(K)
+        frows, fcounts = st.frames()
+        chost = fcounts[:m].tolist()                           # the per-frame loop needs the counts on the host: read once, untimed
+
+        def one_call():
+            one.insert_frames(st, P)
+
+        def per_frame():
+            for e in range(m):
+                per.insert(frows[e][:chost[e]], P[e])
+        ms = {"one_call": [], "per_frame": []}
+        for rep in range(reps + 1):                            # rep 0 warms both up; then the two alternate
+            for key, vm, fn in (("one_call", one, one_call), ("per_frame", per, per_frame)):
+                vm.reset()
+                t = device_ms(lambda _: fn(), 1)
+                if rep:
+                    ms[key].append(t)
+        got = [[t.cpu().numpy().tobytes() for t in vm.points()] for vm in (one, per)]
+        st_one = one.stats()
+        rec = {"frames": m, "K": K, "map_slots": slots, "points": st_one["n_points"], "cells": st_one["n_cells"],
+               "dropped_full": st_one["dropped_full"], "dropped_range": st_one["dropped_range"], "reps": reps,
+               "bit_equal": bool(got[0] == got[1] and st_one == per.stats())}
+        for key, v in ms.items():
+            rec[key + "_ms"] = {"median": round(float(np.median(v)), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+        out["rebuild_" + name] = rec
+        del one, per, got
     return out
 
 
