@@ -13,8 +13,8 @@
 // lowest index because the scan ascends and replaces on a strict `<` only.  All lanes of a wave read the same target
 // word at the same time (an LDS broadcast, no bank conflict).  The 28 sums and the pair count are reduced in a fixed
 // order -- a thread's own points by ascending index, a shuffle tree inside each wave, the waves in wave order -- with
-// no floating-point atomic: two calls give the same bits.  Thread 0 takes the step (k_mapreg_finish's arithmetic,
-// restated here so that mapreg.hip keeps its bits) on the pose kept in LDS.
+// no floating-point atomic: two calls give the same bits.  Thread 0 takes the step on the pose kept in LDS.  The
+// addends, the reduction and the step are gauss_newton.h's, shared with scan-to-map registration (mapreg.hip).
 #include "rslo_common.h"
 
 #include <math.h>
@@ -22,9 +22,9 @@
 #pragma clang fp contract(off)   /* every sum is specified operation by operation */
 
 #include "se3.h"
+#include "gauss_newton.h"                /* after the pragma and after se3.h */
 #include "kf_store.h"                    /* the store's layout, shared with csrc/map.hip (rslo_map_insert_frames) */
 
-#define LV_NSUM 29                       /* 21 H (upper triangle, row-major) + 6 g + cost + pairs */
 #define LV_MAX_STAGES 8
 #define LV_MAX_ITERS 64
 #define LV_MAX_TOPK 16
@@ -152,64 +152,7 @@ __device__ __forceinline__ int lv_nearest(const float *__restrict__ tx, const fl
   return bj;
 }
 
-// the workgroup's sum of `v` in the fixed order, valid in every thread.  part: [waves] doubles of LDS
-__device__ __forceinline__ double lv_block_sum(double v, double *part, int n_waves) {
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
-  __syncthreads();      // the readers of an earlier sum
-  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = part[0];
-  for (int q = 1; q < n_waves; ++q) s = s + part[q];
-  return s;
-}
-
-// thread 0: the Gauss-Newton step of k_mapreg_finish on the 28 sums.  true: pose7 was advanced; nt, th its size
-__device__ bool lv_step(const double *tot, double damping, double *pose7, double &nt, double &th) {
-  double M[6][6], L[6][6], y[6], x[6];
-  int o = 0;
-  for (int a = 0; a < 6; ++a)
-    for (int b = a; b < 6; ++b) M[a][b] = M[b][a] = tot[o++];
-  for (int a = 0; a < 6; ++a) M[a][a] = M[a][a] + damping;
-  for (int a = 0; a < 6; ++a) {
-    for (int b = 0; b <= a; ++b) {
-      double sum = M[a][b];
-      for (int k = 0; k < b; ++k) sum = sum - L[a][k] * L[b][k];
-      if (a == b) {
-        if (!(sum > 0.0 && sum < (double)__builtin_inff())) return false;
-        L[a][a] = sqrt(sum);
-      } else {
-        L[a][b] = sum / L[b][b];
-      }
-    }
-  }
-  for (int a = 0; a < 6; ++a) {      // L y = g
-    double sum = tot[21 + a];
-    for (int k = 0; k < a; ++k) sum = sum - L[a][k] * y[k];
-    y[a] = sum / L[a][a];
-  }
-  for (int a = 5; a >= 0; --a) {     // L^T x = y
-    double sum = y[a];
-    for (int k = a + 1; k < 6; ++k) sum = sum - L[k][a] * x[k];
-    x[a] = sum / L[a][a];
-  }
-  const double dt[3] = {-x[0], -x[1], -x[2]}, dr[3] = {-x[3], -x[4], -x[5]};
-  nt = sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);
-  th = sqrt(dr[0] * dr[0] + dr[1] * dr[1] + dr[2] * dr[2]);
-  if (!(nt < (double)__builtin_inff() && th < (double)__builtin_inff())) return false;      // an overflowed step is no step
-  double dq[4], t[3], q[4], b[3], c[3], r[4];
-  se3_dquat(dr, th, dq);
-  for (int a = 0; a < 3; ++a) t[a] = pose7[a];
-  for (int a = 0; a < 4; ++a) q[a] = pose7[3 + a];
-  se3_cross(dq + 1, t, b);
-  se3_cross(dq + 1, b, c);
-  for (int a = 0; a < 3; ++a) pose7[a] = dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]);      // form B: see se3.h
-  se3_qmul(dq, q, r);
-  const double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
-  for (int a = 0; a < 4; ++a) pose7[3 + a] = r[a] / nr;
-  return true;
-}
-
-// dynamic LDS: tx f32 [K] | ty f32 [K] | tz f32 [K] | part f64 [waves, LV_NSUM] | tot f64 [LV_NSUM] | pose f64 [7] |
+// dynamic LDS: tx f32 [K] | ty f32 [K] | tz f32 [K] | part f64 [waves, GN_NSUM] | tot f64 [GN_NSUM] | pose f64 [7] |
 // flag i32 [2]
 __global__ __launch_bounds__(1024) void k_loop_verify(void *st, size_t st_bytes, long long cap, int K,
                                                       const float *__restrict__ frame, const int32_t *__restrict__ frame_info,
@@ -218,10 +161,9 @@ __global__ __launch_bounds__(1024) void k_loop_verify(void *st, size_t st_bytes,
                                                       int32_t *__restrict__ matches) {
   extern __shared__ double lv_lds[];
   const int b = blockIdx.x, t = threadIdx.x, n_waves = blockDim.x >> 6;
-  const int lane = t & 63, wave = t >> 6;
   double *part = lv_lds;
-  double *tot = part + (size_t)n_waves * LV_NSUM;
-  double *pose = tot + LV_NSUM;
+  double *tot = part + (size_t)n_waves * GN_NSUM;
+  double *pose = tot + GN_NSUM;
   int32_t *flag = (int32_t *)(pose + 8);
   float *tx = (float *)(pose + 10), *ty = tx + K, *tz = ty + K;
 
@@ -294,9 +236,9 @@ __global__ __launch_bounds__(1024) void k_loop_verify(void *st, size_t st_bytes,
       }
       double Z[7];
       for (int a = 0; a < 7; ++a) Z[a] = pose[a];
-      double acc[LV_NSUM];
+      double acc[GN_NSUM];
 #pragma unroll
-      for (int k = 0; k < LV_NSUM; ++k) acc[k] = 0.0;
+      for (int k = 0; k < GN_NSUM; ++k) acc[k] = 0.0;
       for (int i = t; i < nq; i += blockDim.x) {      // a thread's points by ascending index
         const float4 p4 = *(const float4 *)(frame + (size_t)i * 4);
         const double p[3] = {(double)p4.x, (double)p4.y, (double)p4.z};
@@ -306,43 +248,11 @@ __global__ __launch_bounds__(1024) void k_loop_verify(void *st, size_t st_bytes,
         const int j = lv_nearest(tx, ty, tz, nt, w, d2, m);
         if (j >= 0 && d2 < gate2) {
           const double d[3] = {w[0] - m[0], w[1] - m[1], w[2] - m[2]};
-          double J[3][6];      // J = [I | -[w]x], residual d
-          for (int a = 0; a < 3; ++a)
-            for (int c = 0; c < 3; ++c) J[a][c] = a == c ? 1.0 : 0.0;
-          J[0][3] = 0.0, J[0][4] = w[2], J[0][5] = -w[1];
-          J[1][3] = -w[2], J[1][4] = 0.0, J[1][5] = w[0];
-          J[2][3] = w[1], J[2][4] = -w[0], J[2][5] = 0.0;
-          int o = 0;
-#pragma unroll
-          for (int a = 0; a < 6; ++a) {
-#pragma unroll
-            for (int c = a; c < 6; ++c) {
-              acc[o] = acc[o] + (J[0][a] * J[0][c] + J[1][a] * J[1][c] + J[2][a] * J[2][c]);
-              ++o;
-            }
-          }
-#pragma unroll
-          for (int a = 0; a < 6; ++a) acc[21 + a] = acc[21 + a] + (J[0][a] * d[0] + J[1][a] * d[1] + J[2][a] * d[2]);
-          acc[27] = acc[27] + (d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-          acc[28] = acc[28] + 1.0;
+          gn_point_terms(w, d, acc, true);      // a point term, residual d, added to the thread's running sums
+          acc[GN_NSUM - 1] = acc[GN_NSUM - 1] + 1.0;
         }
       }
-#pragma unroll
-      for (int k = 0; k < LV_NSUM; ++k) {
-        double x = acc[k];
-        for (int off = 32; off > 0; off >>= 1) x = x + __shfl_down(x, off, 64);
-        acc[k] = x;
-      }
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < LV_NSUM; ++k) part[wave * LV_NSUM + k] = acc[k];
-      }
-      __syncthreads();
-      if (t < LV_NSUM) {
-        double x = part[t];
-        for (int q = 1; q < n_waves; ++q) x = x + part[q * LV_NSUM + t];
-        tot[t] = x;
-      }
+      gn_block_reduce(acc, part, n_waves, tot);
       __syncthreads();
       if (t == 0) {
         double nts = 0.0, th = 0.0;
@@ -350,7 +260,7 @@ __global__ __launch_bounds__(1024) void k_loop_verify(void *st, size_t st_bytes,
         if (ok) {
           double np[7];
           for (int a = 0; a < 7; ++a) np[a] = pose[a];
-          ok = lv_step(tot, P.damping, np, nts, th);
+          ok = gn_step(tot, P.damping, np, nts, th);
           bool fin = ok;
           for (int a = 0; a < 7; ++a) fin = fin && fabs(np[a]) < (double)__builtin_inff();
           ok = fin;
@@ -405,8 +315,8 @@ __global__ __launch_bounds__(1024) void k_loop_verify(void *st, size_t st_bytes,
   } else if (mrow) {
     for (int i = t; i < K; i += blockDim.x) mrow[i] = -1;
   }
-  n_in = lv_block_sum(n_in, part, n_waves);
-  sum_d2 = lv_block_sum(sum_d2, part, n_waves);
+  n_in = gn_block_sum(n_in, part, n_waves);
+  sum_d2 = gn_block_sum(sum_d2, part, n_waves);
   if (t == 0) {
     double overlap = 0.0, rms = 0.0;
     int st_out = 4;
@@ -553,7 +463,7 @@ extern "C" int rslo_keyframe_add(void *store, size_t store_bytes, int64_t capaci
 }
 
 static size_t lv_lds_bytes(int K, int threads) {
-  return ((size_t)(threads / 64) * LV_NSUM + LV_NSUM + 10) * 8 + (size_t)K * 12;
+  return ((size_t)(threads / 64) * GN_NSUM + GN_NSUM + 10) * 8 + (size_t)K * 12;
 }
 
 extern "C" int rslo_loop_verify(const void *store, size_t store_bytes, int64_t capacity, int K, const float *frame,

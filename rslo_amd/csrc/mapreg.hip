@@ -10,7 +10,8 @@
 //
 // Sums: 28 doubles and the pair count per point, reduced in a fixed order -- a shuffle tree inside each wave, the four
 // waves of a block in wave order, the blocks in block order by the second stage (one wave; lane j owns sum j).  No
-// floating-point atomic anywhere: two runs give the same bits.
+// floating-point atomic anywhere: two runs give the same bits.  The addends, the two levels inside a block and the step
+// that lane 0 of the second stage takes are gauss_newton.h's, shared with loop verification.
 //
 // Robust weights (rslo_map_normal_eq_w / _register_w / _register_sched): the accumulate kernel is one template; its
 // WEIGHTED instantiation scales the 28 addends of a matched point by the Geman-McClure weight of its cost addend, the
@@ -24,7 +25,8 @@
 
 #pragma clang fp contract(off)   /* the sums are specified operation by operation */
 
-#define MR_NSUM 29                       /* 21 H (upper triangle, row-major) + 6 g + cost + pairs */
+#include "gauss_newton.h"        /* after the pragma and after map_table.h's se3.h: the addends, the reduction, the step */
+
 #define MR_BLOCK 256
 #define MR_WS_HDR 256                    /* int32 word 0: the "converged" flag of rslo_map_register */
 #define MR_MAX_ITERS 32
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(MR_BLOCK) void k_map_nearest(const void *map, long 
   if (rows_out) *(float4 *)(rows_out + (size_t)i * 4) = row;
 }
 
-// block partial [MR_NSUM] of the addends of points blockIdx.x * 256 .. + 255 at the pose in pose7.  WEIGHTED: the 28
+// block partial [GN_NSUM] of the addends of points blockIdx.x * 256 .. + 255 at the pose in pose7.  WEIGHTED: the 28
 // addends of a matched point are multiplied by rho = u*u, u = s2 / (s2 + e), e its cost addend (s2 = scale*scale > 0).
 template <bool WEIGHTED>
 __global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long long cap_max, double voxel,
@@ -122,11 +124,11 @@ __global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long
                                                            int min_hits, int iter, const int32_t *__restrict__ flag,
                                                            double *__restrict__ partials, double s2) {
   if (iter > 0 && *flag) return;      // converged in an earlier iteration: the second stage does not read the partials
-  __shared__ double part[MR_BLOCK / 64][MR_NSUM];
+  __shared__ double part[MR_BLOCK / 64 * GN_NSUM];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  double acc[MR_NSUM];
+  double acc[GN_NSUM];
 #pragma unroll
-  for (int k = 0; k < MR_NSUM; ++k) acc[k] = 0.0;
+  for (int k = 0; k < GN_NSUM; ++k) acc[k] = 0.0;
   MapView m;
   map_u64 key;
   double w[3], mm[3], bd2;
@@ -136,72 +138,29 @@ __global__ __launch_bounds__(MR_BLOCK) void k_mapreg_accum(const void *map, long
     if (!map_point(p, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
         mr_nearest(m, key, w, min_hits, s, bd2, mm) && bd2 < max_dist * max_dist) {
       const double d[3] = {w[0] - mm[0], w[1] - mm[1], w[2] - mm[2]};
-      // the rows of the residual's Jacobian with respect to the world-frame twist (dt, dtheta): one for a plane term,
-      // three for a point term; addend of H(a, b) = J0[a]*J0[b] + J1[a]*J1[b] + J2[a]*J2[b], left to right
-      double J[3][6], r[3];
-      int rows = 3;
+      // one plane term, or the three rows of a point term; the addends are assigned, not added to the zeros
+      bool plane = false;
       if (metric == 1) {
         const double ns[3] = {(double)p[4], (double)p[5], (double)p[6]};
         if (ns[0] * ns[0] + ns[1] * ns[1] + ns[2] * ns[2] >= 0.25) {      // false for a NaN normal as well
           double n[3], wn[3];
           se3_rotate(pose + 3, ns, n);
           se3_cross(w, n, wn);
-          for (int a = 0; a < 3; ++a) {
-            J[0][a] = n[a];
-            J[0][3 + a] = wn[a];
-          }
-          r[0] = n[0] * d[0] + n[1] * d[1] + n[2] * d[2];
-          rows = 1;
+          gn_plane_terms(n, wn, n[0] * d[0] + n[1] * d[1] + n[2] * d[2], acc);
+          plane = true;
         }
       }
-      if (rows == 3) {      // J = [I | -[w]x]
-        for (int a = 0; a < 3; ++a) {
-          for (int b = 0; b < 3; ++b) J[a][b] = a == b ? 1.0 : 0.0;
-          r[a] = d[a];
-        }
-        J[0][3] = 0.0, J[0][4] = w[2], J[0][5] = -w[1];
-        J[1][3] = -w[2], J[1][4] = 0.0, J[1][5] = w[0];
-        J[2][3] = w[1], J[2][4] = -w[0], J[2][5] = 0.0;
-      }
-      int o = 0;
-      if (rows == 1) {
-        for (int a = 0; a < 6; ++a)
-          for (int b = a; b < 6; ++b) acc[o++] = J[0][a] * J[0][b];
-        for (int a = 0; a < 6; ++a) acc[o++] = J[0][a] * r[0];
-        acc[o++] = r[0] * r[0];
-      } else {
-        for (int a = 0; a < 6; ++a)
-          for (int b = a; b < 6; ++b) acc[o++] = J[0][a] * J[0][b] + J[1][a] * J[1][b] + J[2][a] * J[2][b];
-        for (int a = 0; a < 6; ++a) acc[o++] = J[0][a] * r[0] + J[1][a] * r[1] + J[2][a] * r[2];
-        acc[o++] = r[0] * r[0] + r[1] * r[1] + r[2] * r[2];
-      }
-      acc[o] = 1.0;
+      if (!plane) gn_point_terms(w, d, acc, false);
+      acc[GN_NSUM - 1] = 1.0;
       if (WEIGHTED) {      // e = acc[27] >= 0 (or NaN, which stays NaN as it would unweighted); s2 > 0: u is in [0, 1]
-        const double u = s2 / (s2 + acc[MR_NSUM - 2]);
+        const double u = s2 / (s2 + acc[GN_NSUM - 2]);
         const double rho = u * u;
 #pragma unroll
-        for (int k = 0; k < MR_NSUM - 1; ++k) acc[k] = rho * acc[k];
+        for (int k = 0; k < GN_NSUM - 1; ++k) acc[k] = rho * acc[k];
       }
     }
   }
-  // fixed order: lane l takes l + 32, then + 16, ... inside its wave; then the waves 0..3 in turn
-#pragma unroll
-  for (int k = 0; k < MR_NSUM; ++k) {
-    double v = acc[k];
-    for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
-    acc[k] = v;
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < MR_NSUM; ++k) part[wave][k] = acc[k];
-  }
-  __syncthreads();
-  if (threadIdx.x < MR_NSUM) {
-    double v = part[0][threadIdx.x];
-    for (int q = 1; q < MR_BLOCK / 64; ++q) v = v + part[q][threadIdx.x];
-    partials[(size_t)blockIdx.x * MR_NSUM + threadIdx.x] = v;
-  }
+  gn_block_reduce(acc, part, MR_BLOCK / 64, partials + (size_t)blockIdx.x * GN_NSUM);
 }
 
 struct MrSolve {
@@ -217,16 +176,16 @@ struct MrSolve {
 __global__ __launch_bounds__(64) void k_mapreg_finish(const double *__restrict__ partials, int n_blocks,
                                                       double *__restrict__ out29, double *__restrict__ pose7, int iter,
                                                       MrSolve sp, int32_t *__restrict__ flag, double *__restrict__ info) {
-  __shared__ double tot[MR_NSUM];
+  __shared__ double tot[GN_NSUM];
   double *row = info ? info + (size_t)sp.row * 8 : nullptr;
   if (pose7 && iter > 0 && *flag) {
     if (threadIdx.x < 8)
       row[threadIdx.x] = threadIdx.x == 0 ? 3.0 : threadIdx.x == 5 ? sp.stage : threadIdx.x == 6 ? sp.level : 0.0;
     return;
   }
-  if (threadIdx.x < MR_NSUM) {
+  if (threadIdx.x < GN_NSUM) {
     double v = 0.0;
-    for (int b = 0; b < n_blocks; ++b) v = v + partials[(size_t)b * MR_NSUM + threadIdx.x];
+    for (int b = 0; b < n_blocks; ++b) v = v + partials[(size_t)b * GN_NSUM + threadIdx.x];
     tot[threadIdx.x] = v;
     if (out29) out29[threadIdx.x] = v;
   }
@@ -237,58 +196,9 @@ __global__ __launch_bounds__(64) void k_mapreg_finish(const double *__restrict__
   const double pairs = tot[28], cost = tot[27];
   if (pairs < (double)sp.min_pairs) {
     status = 1;
-  } else {
-    // M = H + damping * I = L L^T, row by row
-    double M[6][6], L[6][6], y[6], x[6];
-    int o = 0;
-    for (int a = 0; a < 6; ++a)
-      for (int b = a; b < 6; ++b) M[a][b] = M[b][a] = tot[o++];
-    for (int a = 0; a < 6; ++a) M[a][a] = M[a][a] + sp.damping;
-    for (int a = 0; a < 6 && !status; ++a) {
-      for (int b = 0; b <= a; ++b) {
-        double sum = M[a][b];
-        for (int k = 0; k < b; ++k) sum = sum - L[a][k] * L[b][k];
-        if (a == b) {
-          if (!(sum > 0.0 && sum < (double)__builtin_inff())) {
-            status = 2;
-            break;
-          }
-          L[a][a] = sqrt(sum);
-        } else {
-          L[a][b] = sum / L[b][b];
-        }
-      }
-    }
-    if (!status) {
-      for (int a = 0; a < 6; ++a) {      // L y = g
-        double sum = tot[21 + a];
-        for (int k = 0; k < a; ++k) sum = sum - L[a][k] * y[k];
-        y[a] = sum / L[a][a];
-      }
-      for (int a = 5; a >= 0; --a) {     // L^T x = y
-        double sum = y[a];
-        for (int k = a + 1; k < 6; ++k) sum = sum - L[k][a] * x[k];
-        x[a] = sum / L[a][a];
-      }
-      const double dt[3] = {-x[0], -x[1], -x[2]}, dr[3] = {-x[3], -x[4], -x[5]};
-      nt = sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2]);
-      th = sqrt(dr[0] * dr[0] + dr[1] * dr[1] + dr[2] * dr[2]);
-      if (!(nt < (double)__builtin_inff() && th < (double)__builtin_inff())) {
-        status = 2;      // an overflowed step is no step
-        nt = th = 0.0;
-      } else {
-        double dq[4], t[3], q[4], b[3], c[3], r[4];
-        se3_dquat(dr, th, dq);
-        for (int a = 0; a < 3; ++a) t[a] = pose7[a];
-        for (int a = 0; a < 4; ++a) q[a] = pose7[3 + a];
-        se3_cross(dq + 1, t, b);
-        se3_cross(dq + 1, b, c);
-        for (int a = 0; a < 3; ++a) pose7[a] = dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]);      // form B: see se3.h
-        se3_qmul(dq, q, r);
-        const double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3]);
-        for (int a = 0; a < 4; ++a) pose7[3 + a] = r[a] / nr;
-      }
-    }
+  } else if (!gn_step(tot, sp.damping, pose7, nt, th)) {
+    status = 2;      // not positive definite, or an overflowed step: no step
+    nt = th = 0.0;
   }
   *flag = (status == 0 && nt < sp.tol_t && th < sp.tol_r) ? 1 : 0;
   row[0] = (double)status;
@@ -349,7 +259,7 @@ extern "C" int rslo_map_nearest(const void *map, size_t map_bytes, double voxel_
 
 extern "C" size_t rslo_map_register_ws_bytes(int N) {
   const size_t nb = N > 0 ? (size_t)rslo_cdiv(N, MR_BLOCK) : 1;
-  return MR_WS_HDR + (nb * MR_NSUM * sizeof(double) + 255) / 256 * 256;
+  return MR_WS_HDR + (nb * GN_NSUM * sizeof(double) + 255) / 256 * 256;
 }
 
 // the launches of one evaluation of the normal equations (+ the step of iteration `iter` when pose_rw is given)

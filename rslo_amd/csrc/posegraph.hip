@@ -28,6 +28,7 @@
 #pragma clang fp contract(off)
 
 #include "se3.h"      /* the pose algebra, after the pragma: uncontracted here */
+#include "gauss_newton.h"      /* gn_block_sum: the fixed-order workgroup sum, after the pragma and after se3.h */
 
 #define PG_THREADS 1024
 #define PG_EREC 84                       /* doubles per edge record (RSLO_PG_EDGE_DOUBLES) */
@@ -256,15 +257,7 @@ struct PgShared {
   int imax;
 };
 
-__device__ double pg_block_sum(double v, PgShared &sh) {
-  for (int off = 32; off > 0; off >>= 1) v = v + __shfl_down(v, off, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) sh.red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = sh.red[0];
-  for (int q = 1; q < PG_THREADS / 64; ++q) t = t + sh.red[q];
-  return t;
-}
+__device__ double pg_block_sum(double v, PgShared &sh) { return gn_block_sum(v, sh.red, PG_THREADS / 64); }
 
 __device__ double pg_block_max(double v, PgShared &sh) {
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off, 64));

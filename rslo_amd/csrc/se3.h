@@ -11,8 +11,9 @@
 // The rotation is summed in two ways in this project, and the two differ in the last bit:
 //   form A  v + (2 b w + 2 c)      se3_rotate: map_point, the normals of k_mapreg_accum, the pose graph;
 //                                  host: se3.rotate, VoxelMapRef
-//   form B  (v + 2 b w) + 2 c      the translation updates of k_pose_chain and k_mapreg_finish, which keep their own
-//                                  three lines; host: inference.pose_chain_host, mapping.gauss_newton_step
+//   form B  (v + 2 b w) + 2 c      the translation updates of k_pose_chain (pose.hip) and gn_step (gauss_newton.h), each
+//                                  written out where it is; host: inference.pose_chain_host,
+//                                  gauss_newton.gauss_newton_step
 // with b = u x v, c = u x b.  Both are correct and both are pinned by bit-equality tests against their host
 // restatements, so neither may be turned into the other.
 #pragma once

@@ -1,0 +1,99 @@
+"""The Gauss-Newton core of scan-to-map registration and loop verification on the host, numpy float64 (device twin:
+csrc/gauss_newton.h).  The 28 sums of a set of matched points are the upper triangle of H = sum J^T J (21, row-major),
+g = sum J^T r (6) and the cost sum r.r, for the world-frame twist (dt, dtheta).  terms_of gives their addends row by row
+in the operand order of gn_point_terms / gn_plane_terms; gauss_newton_step is gn_step, scalar float64 in the order of
+the device's one thread."""
+import math
+
+import numpy as np
+
+
+def point_jacobian(w):
+    """[n, 3, 6]: the rows J = [I | -[w]x] of the points at world positions w [n, 3]"""
+    J = np.zeros((len(w), 3, 6), np.float64)
+    for a in range(3):
+        J[:, a, a] = 1.0
+    J[:, 0, 4], J[:, 0, 5] = w[:, 2], -w[:, 1]
+    J[:, 1, 3], J[:, 1, 5] = -w[:, 2], w[:, 0]
+    J[:, 2, 3], J[:, 2, 4] = w[:, 1], -w[:, 0]
+    return J
+
+
+def terms_of(J, r):
+    """[K, 28]: the addends from the Jacobian rows J [K, 3, 6] and residuals r [K, 3] (rows a term lacks are zero)"""
+    terms = np.zeros((len(J), 28), np.float64)
+    o = 0
+    for a in range(6):
+        for b in range(a, 6):
+            terms[:, o] = J[:, 0, a] * J[:, 0, b] + J[:, 1, a] * J[:, 1, b] + J[:, 2, a] * J[:, 2, b]
+            o += 1
+    for a in range(6):
+        terms[:, 21 + a] = J[:, 0, a] * r[:, 0] + J[:, 1, a] * r[:, 1] + J[:, 2, a] * r[:, 2]
+    terms[:, 27] = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2]
+    return terms
+
+
+def point_terms(w, d):
+    """[n, 28]: the addends of the 28 sums of matched points at world positions w with residuals d (J = [I | -[w]x])"""
+    return terms_of(point_jacobian(w), d)
+
+
+def _cross3(a, b):
+    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
+
+
+def gauss_newton_step(sums, pose, damping=0.0):
+    """The step from the 28 sums (H upper triangle, g, cost) at pose [7]: -> (new pose [7], |dt|, theta), or None when
+    M = H + damping * I is not positive definite or the step overflows.  Scalar float64 in the order of the device's one
+    thread; the translation update is form B: see se3.py."""
+    f = [float(v) for v in sums]
+    M = [[0.0] * 6 for _ in range(6)]
+    o = 0
+    for a in range(6):
+        for b in range(a, 6):
+            M[a][b] = M[b][a] = f[o]
+            o += 1
+    for a in range(6):
+        M[a][a] = M[a][a] + float(damping)
+    L = [[0.0] * 6 for _ in range(6)]
+    for a in range(6):
+        for b in range(a + 1):
+            acc = M[a][b]
+            for k in range(b):
+                acc = acc - L[a][k] * L[b][k]
+            if a == b:
+                if not (0.0 < acc < float("inf")):
+                    return None
+                L[a][a] = math.sqrt(acc)
+            else:
+                L[a][b] = acc / L[b][b]
+    y, x = [0.0] * 6, [0.0] * 6
+    for a in range(6):
+        acc = f[21 + a]
+        for k in range(a):
+            acc = acc - L[a][k] * y[k]
+        y[a] = acc / L[a][a]
+    for a in range(5, -1, -1):
+        acc = y[a]
+        for k in range(a + 1, 6):
+            acc = acc - L[k][a] * x[k]
+        x[a] = acc / L[a][a]
+    dt, dr = [-x[0], -x[1], -x[2]], [-x[3], -x[4], -x[5]]
+    nt = math.sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2])
+    th = math.sqrt(dr[0] * dr[0] + dr[1] * dr[1] + dr[2] * dr[2])
+    if not (nt < float("inf") and th < float("inf")):
+        return None
+    if th < 1e-12:
+        dq = [1.0] + [v / 2.0 for v in dr]
+    else:
+        fac = math.sin(th / 2.0) / th
+        dq = [math.cos(th / 2.0)] + [fac * v for v in dr]
+    t, q = [float(v) for v in pose[:3]], [float(v) for v in pose[3:7]]
+    b = _cross3(dq[1:], t)
+    c = _cross3(dq[1:], b)
+    tn = [dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]) for a in range(3)]
+    vx = _cross3(dq[1:], q[1:])
+    r = [dq[0] * q[0] - (dq[1] * q[1] + dq[2] * q[2] + dq[3] * q[3])]
+    r += [dq[1 + a] * q[0] + q[1 + a] * dq[0] + vx[a] for a in range(3)]
+    nr = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3])
+    return np.array(tn + [v / nr for v in r], np.float64), nt, th

@@ -28,9 +28,9 @@ place (all arithmetic IEEE double, no fused multiply-add; the pose algebra is se
     q = (cos(h/2), 0, 0, sin(h/2)), h = heading, or at the given start row.  Match of source point i: w = rotate(q, p_i)
     + t; d2 to every target point as dx*dx + dy*dy + dz*dz; the smallest d2 wins, ties to the lowest index; accepted
     iff d2 < max_dist*max_dist.  stages [(max_dist, iters), ...]: every iteration adds the point terms
-    (J = [I | -[w]x], residual d) of the matched points to the 28 sums and takes mapping.gauss_newton_step; fewer than
-    min_pairs pairs, a matrix that is not positive definite or a step that is not finite is status 4: Z stays, the rest
-    is skipped, no fitness.  Fitness at the final Z: match again within inlier_dist; overlap = inliers / query count,
+    (J = [I | -[w]x], residual d; gauss_newton.point_terms) of the matched points to the 28 sums and takes
+    gauss_newton.gauss_newton_step; fewer than min_pairs pairs, a matrix that is not positive definite or a step that
+    is not finite is status 4: Z stays, the rest is skipped, no fitness.  Fitness at the final Z: match again within inlier_dist; overlap = inliers / query count,
     rms = sqrt(sum of d2 / inliers); status 0 iff inliers > 0, overlap >= min_overlap and rms <= max_rms, else 5.
     out row = {status, entry, pairs of the last iteration, overlap, rms, query count, Z (7), distance, heading, 0};
   * emit: among the rows with status 0 the one with the largest overlap, ties to the lowest row, is appended to the
@@ -47,6 +47,7 @@ import numpy as np
 
 from rslo_amd import se3
 from rslo_amd.downsample import voxel_down_sample_ref
+from rslo_amd.gauss_newton import gauss_newton_step, point_terms
 
 OUT_COLS = 16
 STATUS = {0: "accepted", 1: "no candidate", 2: "gated", 3: "too few points", 4: "failed", 5: "rejected"}
@@ -220,27 +221,6 @@ def nearest_exact(w, target, chunk=256):
     return idx, best
 
 
-def point_terms(w, d):
-    """[n, 28]: the addends of the 28 sums of matched points at world positions w with residuals d (J = [I | -[w]x])"""
-    n = len(w)
-    J = np.zeros((n, 3, 6), np.float64)
-    for a in range(3):
-        J[:, a, a] = 1.0
-    J[:, 0, 4], J[:, 0, 5] = w[:, 2], -w[:, 1]
-    J[:, 1, 3], J[:, 1, 5] = -w[:, 2], w[:, 0]
-    J[:, 2, 3], J[:, 2, 4] = w[:, 1], -w[:, 0]
-    terms = np.zeros((n, 28), np.float64)
-    o = 0
-    for a in range(6):
-        for b in range(a, 6):
-            terms[:, o] = J[:, 0, a] * J[:, 0, b] + J[:, 1, a] * J[:, 1, b] + J[:, 2, a] * J[:, 2, b]
-            o += 1
-    for a in range(6):
-        terms[:, 21 + a] = J[:, 0, a] * d[:, 0] + J[:, 1, a] * d[:, 1] + J[:, 2, a] * d[:, 2]
-    terms[:, 27] = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
-    return terms
-
-
 class LoopVerifierRef:
     """The verification rules on host arrays, against a KeyframeStoreRef."""
 
@@ -270,7 +250,6 @@ class LoopVerifierRef:
 
     def verify_row(self, frame, info, row, start=None):
         """-> (out [16], info [sum of iters, 8], matches int32 [K]) of one candidate row"""
-        from rslo_amd.mapping import gauss_newton_step
         o, K = self.options, self.store.K
         total = sum(it for _, it in o["stages"])
         out, rows, matches = np.zeros(OUT_COLS), np.zeros((total, 8)), np.full(K, -1, np.int32)

@@ -98,6 +98,7 @@ and on the pyramids MapPyramid (device) / MapPyramidRef (numpy):
 import numpy as np
 
 from . import se3
+from .gauss_newton import gauss_newton_step, point_jacobian, terms_of
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full")
 PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
@@ -246,68 +247,6 @@ def check_refine(refine, voxel_map):
         return refine, sum(st[1] for st in stages)
     refine.setdefault("iters", 5)
     return refine, int(refine["iters"])
-
-
-def _cross3(a, b):
-    return [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
-
-
-def gauss_newton_step(sums, pose, damping=0.0):
-    """The step of register from the 28 sums (H upper triangle, g, cost) at pose [7]: -> (new pose [7], |dt|, theta), or
-    None when M = H + damping * I is not positive definite.  Scalar float64 in the order of the device's one thread;
-    the translation update is form B: see se3.py."""
-    import math
-    f = [float(v) for v in sums]
-    M = [[0.0] * 6 for _ in range(6)]
-    o = 0
-    for a in range(6):
-        for b in range(a, 6):
-            M[a][b] = M[b][a] = f[o]
-            o += 1
-    for a in range(6):
-        M[a][a] = M[a][a] + float(damping)
-    L = [[0.0] * 6 for _ in range(6)]
-    for a in range(6):
-        for b in range(a + 1):
-            acc = M[a][b]
-            for k in range(b):
-                acc = acc - L[a][k] * L[b][k]
-            if a == b:
-                if not (0.0 < acc < float("inf")):
-                    return None
-                L[a][a] = math.sqrt(acc)
-            else:
-                L[a][b] = acc / L[b][b]
-    y, x = [0.0] * 6, [0.0] * 6
-    for a in range(6):
-        acc = f[21 + a]
-        for k in range(a):
-            acc = acc - L[a][k] * y[k]
-        y[a] = acc / L[a][a]
-    for a in range(5, -1, -1):
-        acc = y[a]
-        for k in range(a + 1, 6):
-            acc = acc - L[k][a] * x[k]
-        x[a] = acc / L[a][a]
-    dt, dr = [-x[0], -x[1], -x[2]], [-x[3], -x[4], -x[5]]
-    nt = math.sqrt(dt[0] * dt[0] + dt[1] * dt[1] + dt[2] * dt[2])
-    th = math.sqrt(dr[0] * dr[0] + dr[1] * dr[1] + dr[2] * dr[2])
-    if not (nt < float("inf") and th < float("inf")):
-        return None
-    if th < 1e-12:
-        dq = [1.0] + [v / 2.0 for v in dr]
-    else:
-        fac = math.sin(th / 2.0) / th
-        dq = [math.cos(th / 2.0)] + [fac * v for v in dr]
-    t, q = [float(v) for v in pose[:3]], [float(v) for v in pose[3:7]]
-    b = _cross3(dq[1:], t)
-    c = _cross3(dq[1:], b)
-    tn = [dt[a] + (t[a] + 2.0 * b[a] * dq[0] + 2.0 * c[a]) for a in range(3)]
-    vx = _cross3(dq[1:], q[1:])
-    r = [dq[0] * q[0] - (dq[1] * q[1] + dq[2] * q[2] + dq[3] * q[3])]
-    r += [dq[1 + a] * q[0] + q[1 + a] * dq[0] + vx[a] for a in range(3)]
-    nr = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3])
-    return np.array(tn + [v / nr for v in r], np.float64), nt, th
 
 
 class VoxelMapRef:
@@ -493,14 +432,8 @@ class VoxelMapRef:
         K = len(sel)
         w = w[sel]
         d = w - self.rows[idx[sel], :3].astype(np.float64)
-        J = np.zeros((K, 3, 6), np.float64)            # rows of the Jacobian; a plane term uses row 0 only
-        r = np.zeros((K, 3), np.float64)
-        for a in range(3):
-            J[:, a, a] = 1.0
-        J[:, 0, 4], J[:, 0, 5] = w[:, 2], -w[:, 1]
-        J[:, 1, 3], J[:, 1, 5] = -w[:, 2], w[:, 0]
-        J[:, 2, 3], J[:, 2, 4] = w[:, 1], -w[:, 0]
-        r[:] = d
+        J = point_jacobian(w)                          # rows of the Jacobian; a plane term uses row 0 only
+        r = d.copy()
         plane = np.zeros((K,), bool)
         if metric == "plane":
             with np.errstate(all="ignore"):
@@ -512,15 +445,7 @@ class VoxelMapRef:
             J[plane, 0, :3], J[plane, 0, 3:] = n, np.cross(wp, n)
             r[plane] = 0.0
             r[plane, 0] = n[:, 0] * dp[:, 0] + n[:, 1] * dp[:, 1] + n[:, 2] * dp[:, 2]
-        terms = np.zeros((K, 28), np.float64)
-        o = 0
-        for a in range(6):
-            for b in range(a, 6):
-                terms[:, o] = J[:, 0, a] * J[:, 0, b] + J[:, 1, a] * J[:, 1, b] + J[:, 2, a] * J[:, 2, b]
-                o += 1
-        for a in range(6):
-            terms[:, 21 + a] = J[:, 0, a] * r[:, 0] + J[:, 1, a] * r[:, 1] + J[:, 2, a] * r[:, 2]
-        terms[:, 27] = r[:, 0] * r[:, 0] + r[:, 1] * r[:, 1] + r[:, 2] * r[:, 2]
+        terms = terms_of(J, r)
         return (terms, plane) if return_plane else terms
 
     def _weighted_terms(self, points, pose, metric="plane", max_dist=None, min_hits=1, robust_scale=0.0):

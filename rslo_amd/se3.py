@@ -7,7 +7,7 @@ t' = t + rotate(q, rho), q' = (q (x) dq(phi)) / |.|, dq = (1, phi / 2) when |phi
 (cos(|phi| / 2), sin(|phi| / 2) / |phi| * phi).
 
 rotate sums v + (2 b w + 2 c) with b = u x v, c = u x b ("form A"), as se3_rotate of csrc/se3.h does: the two agree bit
-for bit.  The scalar restatements of one device thread, inference.pose_chain_host and mapping.gauss_newton_step, sum
+for bit.  The scalar restatements of one device thread, inference.pose_chain_host and gauss_newton.gauss_newton_step, sum
 (v + 2 b w) + 2 c ("form B") as their kernels do; the two forms differ in the last bit and both are pinned by
 bit-equality tests (tests/test_se3_host.py holds them apart).
 

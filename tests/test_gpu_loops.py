@@ -308,7 +308,7 @@ def _same_store_entries(store, ref):
 def test_one_iteration_teacher_forced(dev_street):
     """Six successive iterations; both implementations start every one of them from the DEVICE's current Z."""
     from rslo_amd import loops
-    from rslo_amd.mapping import gauss_newton_step
+    from rslo_amd.gauss_newton import gauss_newton_step
     s = street()
     q = s["queries"][0]
     row = q["rows"][q["rows"][:, 0] == q["k"] // 4]

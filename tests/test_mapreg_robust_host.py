@@ -62,7 +62,7 @@ def test_scale_zero_keeps_todays_bits(metric):
     assert ref.normal_equations(q, POSE_YAW, metric, robust_scale=0).tobytes() == want.tobytes()
     assert ref.normal_equations(q, POSE_YAW, metric, robust_scale=0.0).tobytes() == want.tobytes()
     # register: today's loop, written out with today's pieces
-    from rslo_amd.mapping import gauss_newton_step
+    from rslo_amd.gauss_newton import gauss_newton_step
     pose = POSE_YAW.copy()
     rows = []
     for _ in range(3):

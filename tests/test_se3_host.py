@@ -47,8 +47,8 @@ def test_against_the_reference_port():
 
 def test_the_two_forms_stay_apart():
     """form A, v + (2 b w + 2 c), is se3.rotate (and se3_rotate of csrc/se3.h, map_point, the pose graph); form B,
-    (v + 2 b w) + 2 c, is the translation update of k_pose_chain / k_mapreg_finish and of their scalar restatements
-    (inference.pose_chain_host, mapping.gauss_newton_step).  Both are right (within 4 ulp of R(q) v, component by
+    (v + 2 b w) + 2 c, is the translation update of k_pose_chain / gn_step and of their scalar restatements
+    (inference.pose_chain_host, gauss_newton.gauss_newton_step).  Both are right (within 4 ulp of R(q) v, component by
     component); they are NOT the same bits, and each is pinned by bit-equality tests of its kernels: whoever makes
     se3.rotate form B, or this point's two forms equal, fails here first.  (Seed 2: a point where the forms differ.)"""
     rng = np.random.default_rng(2)
