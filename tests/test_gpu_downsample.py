@@ -265,3 +265,61 @@ def test_store_round_trip(tmp_path):
     for name in ("lidar_points", "lidar_normals", "hier_lidar_points_normals_0.1", "hier_lidar_points_normals_0.8"):
         assert len(grp[name]) == 4 and len(grp[name][3]) == 0 and len(grp[name][2]) > 0
     assert (np.asarray(grp["poses"][3]) == 0).all() and (np.asarray(grp["calib.Tr_velo_to_cam"][3]) == 0).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# past every grid stride: more long runs than k_ds_reduce_long has workgroups, more points than k_ds_min has threads, and
+# the instantiations without normals on runs longer than a wave
+# ---------------------------------------------------------------------------------------------------------------------
+LONG_BLOCKS = 1024           # DS_LONG_BLOCKS of csrc/downsample.hip
+MIN_THREADS = 1024 * 256     # the launch cap of k_ds_min
+
+
+def _long_run_lattice():
+    """11 x 10 x 10 cells of 0.4 m with 65 to 70 jittered points each, shuffled; the last point, alone at the origin, pins
+    the minimum, so that the cell centres sit at multiples of the voxel size and the jitter (0.3 of a cell) stays inside"""
+    if "lattice" not in _CLOUD:
+        rng = np.random.default_rng(41)
+        centres = np.stack(np.meshgrid(np.arange(1, 12), np.arange(1, 11), np.arange(1, 11), indexing="ij"), -1).reshape(-1, 3)
+        per = rng.integers(65, 71, len(centres))
+        pts = np.repeat(centres, per, 0) * 0.4 + rng.uniform(-0.12, 0.12, (int(per.sum()), 3))
+        pts = pts[rng.permutation(len(pts))]
+        xyz = np.concatenate([pts, np.zeros((1, 3))], 0).astype(np.float32)
+        _CLOUD["lattice"] = (xyz, rng.normal(size=xyz.shape).astype(np.float32))
+    return _CLOUD["lattice"]
+
+
+def test_more_long_runs_than_workgroups():
+    xyz, nrm = _long_run_lattice()
+    ref = _ref("lattice", 0.4)
+    assert (ref[2] > 64).sum() >= LONG_BLOCKS + 1 and len(xyz) < 90000
+    assert ref[2][0] == 1 and ref[2][1:].min() >= 65 and ref[2].max() <= 70
+    _assert_same(_run(xyz, nrm, 0.4), ref, "lattice")
+    rows, vop, npts = _run(xyz, None, 0.4)
+    _assert_same((rows, vop, npts), (np.ascontiguousarray(ref[0][:, :3]), ref[1], ref[2]), "lattice, no normals")
+
+
+@pytest.mark.parametrize("size", [0.1, 0.4, 2.0])
+def test_no_normals_on_long_runs(size):
+    from rslo_amd import capi
+    xyz, _ = _cloud("patch")
+    ref = _ref("patch", size)
+    assert ref[2].max() > 64
+    want = (np.ascontiguousarray(ref[0][:, :3]), ref[1], ref[2])
+    _assert_same(_run(xyz, None, size), want, "patch without normals @ %g" % size)
+    rows = capi.voxel_downsample(torch.from_numpy(xyz).cuda(), None, size)           # neither index nor npts
+    assert np.array_equal(rows.cpu().numpy().view(np.int32), want[0].view(np.int32))
+
+
+def test_minimum_past_the_grid_stride():
+    """N = 1024 * 256 + 1: k_ds_min strides, and the point only a second trip reaches holds the minimum of all three axes"""
+    from rslo_amd.downsample import voxel_down_sample_ref
+    N = MIN_THREADS + 1
+    rng = np.random.default_rng(43)
+    xyz = rng.uniform(0.0, 20.0, (N, 3)).astype(np.float32)
+    xyz[-1] = (-0.13, -0.27, -0.31)
+    assert (xyz[:-1].min(0) >= 0).all()
+    ref = voxel_down_sample_ref(xyz, None, 0.4)
+    without = voxel_down_sample_ref(xyz[:-1], None, 0.4)
+    assert (ref[1][:-1] != without[1]).all()          # were the last point missed, every other point would move
+    _assert_same(_run(xyz, None, 0.4), ref, "N = %d" % N)
