@@ -1370,6 +1370,94 @@ RSLO_API int rslo_loop_emit(const double *out /*[top_k,16]*/, int top_k, const v
                             int64_t capacity, int K, int32_t *ij, double *Z, double *w, int64_t *counters2, int max_edges,
                             double w_t, double w_r, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Surfel map (csrc/surfel.hip): a voxel hash whose cells hold the integer moments of every point inserted into them and
+ * the plane those moments give, and point-to-plane registration against it that reads no scan normal.  The float64
+ * restatement is rslo_amd/surfels.py SurfelMapRef: keys, moments and rows are compared BIT FOR BIT.  All arithmetic is
+ * IEEE double with contraction off, in the order written; `/` and sqrt are correctly rounded.
+ *
+ * Storage: ONE caller-owned device allocation (8-byte aligned) of rslo_surfel_bytes(capacity) bytes,
+ *   header (256 bytes) | keys u64 [cap] | moments i64 [cap, 10] | rows f64 [cap, 8] | dirty i32 [cap].
+ * Header int64 words: [0] magic, [1] capacity, [2] voxel_size, [3] min_range, [4] max_range (doubles), [5] min_points
+ * (>= 3), [6] planar_ratio, [7] line_ratio (doubles, >= 0, finite), [8..14] n_scans, n_cells, n_points, dropped_invalid,
+ * dropped_range, dropped_full, n_planar.  The table is the world voxel map's: capacity a power of two in 1024 .. 2^31,
+ * linear probing from map_mix(key), at most RSLO_MAP_MAX_PROBE slots examined; a point that finds neither its key nor an
+ * empty slot is dropped and counted (dropped_full): a full table never hangs.  The ten moments of a slot are contiguous.
+ * The table only fills; rslo_surfel_reset empties it.
+ *
+ * Insert of a scan under pose7.
+ *   1. status, world position w and key of a point are those of "World voxel map" (the same function): validity, range
+ *      gate, rotation, division, |cell| < 2^20; a dropped point counts in dropped_invalid / dropped_range.
+ *   2. per axis: s = w / voxel, c = floor(s), f = s - c, q = (int64) floor(f * 16384.0), clamped to 0 .. 16383 (a tiny
+ *      negative s gives f == 1.0: the clamp is part of the rule).
+ *   3. the cell's moments grow by (1, qx, qy, qz, qx*qx, qx*qy, qx*qz, qy*qy, qy*qz, qz*qz): 64-bit INTEGER atomics only,
+ *      so the moments of a cell do not depend on the order in which points or scans arrive.
+ *   4. the sums stay exact in int64 below 2^35 points per cell and convert exactly to double below 2^25.
+ *   5. the slot's dirty word is set; the slot of every point is kept in the workspace (4 bytes per point).
+ * Then the rows of the dirty slots are derived, and n_scans grows by one (also for N == 0).
+ *
+ * Derive.  The row of a cell is a pure function of its moments (N, S_a, S_ab), its key and the header.  n = double(N);
+ * mu_a = double(S_a) / n; c_ab = double(S_ab) / n - mu_a * mu_b in the order 00 01 02 11 12 22; tr = (c00 + c11) + c22.
+ * N < min_points or !(tr > 0 && tr < inf): the row is eight zeros (flag 0).  Otherwise a_ab = c_ab / tr; six cyclic
+ * sweeps (0,1), (0,2), (1,2) of the Jacobi rotation of "Point normals" (nm_rot of csrc/normals.hip) in double, with
+ * the same formulas and the same a_pq == 0 exit; l0 is the smallest diagonal entry by k_nm_normals' comparisons (ties to
+ * the lower index), l1 <= l2 the other two (of the two remaining indices p < q: l1 = a_qq when a_qq < a_pp, else a_pp).
+ * normal = the column e of l0 divided by sqrt((ex*ex + ey*ey) + ez*ez), negated when its component of largest magnitude
+ * (ties to the lower axis) is negative.  mean_a = (double(cell_a) + (mu_a + 0.5) / 16384.0) * voxel;
+ * sigma2 = ((l0 * tr) * u) * u with u = voxel / 16384.0; flag = 2.0 (planar) when l0 <= planar_ratio * l1 &&
+ * l1 >= line_ratio * l2, else 1.0.  row = {mean.x, mean.y, mean.z, n.x, n.y, n.z, sigma2, flag}.  n_planar is the number
+ * of rows with flag 2.0.
+ *
+ * rslo_surfel_insert: three launches (moments; derive, one thread per point of the scan, the thread that takes a slot's
+ * dirty word derives it; the scan counter), one for N == 0.  rslo_surfel_insert_frames has the contract of
+ * rslo_map_insert_frames: it leaves the table and every counter as n successive inserts of the store's frames would --
+ * exactly, because everything is an integer sum and rows are functions of the sums; three launches whatever the data,
+ * the derive pass running over the table's slots.  rslo_surfel_export compacts the cells with flag >= min_flag (0, 1 or
+ * 2) -- and, with center3, whose mean lies within radius, by the test of rslo_map_export -- through one cursor: keys,
+ * moments [R, 10] and rows [R, 8] in unspecified order, counts[2] = {matching, written}.
+ *
+ * Nearest (rslo_surfel_nearest).  For a point with status 0 the candidates are the cells c + {-1,0,1}^3 (neighbours
+ * with |cell| >= 2^20 skipped) whose flag is 2.0, each found by the bounded probe.  d = w - mean,
+ * d2 = d.x*d.x + d.y*d.y + d.z*d.z; the smallest d2 wins, then the smallest key; accepted iff d2 < max_dist*max_dist.
+ * keys_out int64 [N] (-1: none), d2_out double [N] (-1.0), rows_out double [N, 8] or NULL (zeros).
+ * Normal equations (rslo_surfel_normal_eq): a matched point adds the plane term of "Scan-to-map registration" with
+ * n = the row's normal (world frame, not rotated), r = n.x*d.x + n.y*d.y + n.z*d.z, a = (n, w x n).  No point-term
+ * fallback, no scan normal, no column beyond xyz is read.  robust_scale: the weight of "Robust weight" on e = r*r; 0
+ * means no weights.  out29 and the reduction are those of rslo_map_normal_eq; no floating-point atomic.
+ * Register (rslo_surfel_register): the rules of rslo_map_register_w with the normal equations above: the step, damping,
+ * min_pairs, tol_t / tol_r, statuses 0..3, info rows [iters, 8], 2 launches per iteration and 1 for N == 0.
+ *
+ * All of them: everything on `stream`, no host read, nothing allocated, a launch count that does not depend on the data:
+ * capturable.  On an allocation that was never reset the kernels do nothing (nearest writes "none").  Errors are found
+ * before the first launch and write nothing: RSLO_EINVAL for a null pointer, a capacity, size or parameter out of range
+ * (NaN included), max_dist outside (0, voxel_size], a bad robust_scale, iters outside 1 .. 32; RSLO_EWS for a workspace
+ * below rslo_surfel_insert_ws_bytes(N) / rslo_surfel_register_ws_bytes(N).  The three *_bytes functions are host only
+ * and return 0 for arguments out of range.
+ * ------------------------------------------------------------------------------------ */
+RSLO_API size_t rslo_surfel_bytes(int64_t capacity);
+RSLO_API int rslo_surfel_reset(void *map, size_t map_bytes, int64_t capacity, double voxel_size, double min_range,
+                               double max_range, int min_points, double planar_ratio, double line_ratio, void *stream);
+RSLO_API size_t rslo_surfel_insert_ws_bytes(int N);
+RSLO_API int rslo_surfel_insert(void *map, size_t map_bytes, const float *points, int stride_floats, int N,
+                                const double *pose7, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_surfel_insert_frames(void *map, size_t map_bytes, const void *store, size_t store_bytes,
+                                       int64_t capacity, int K, const double *poses /*[n_poses,7]*/, int n_poses,
+                                       void *stream);
+RSLO_API int rslo_surfel_export(const void *map, size_t map_bytes, int min_flag, const double *center3 /*or NULL*/,
+                                double radius, uint64_t *keys, int64_t *moments /*[max_rows,10]*/,
+                                double *rows /*[max_rows,8]*/, int64_t max_rows, int64_t *counts /*[2]*/, void *stream);
+RSLO_API int rslo_surfel_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                 int stride_floats, int N, const double *pose7, double max_dist, int64_t *keys_out,
+                                 double *d2_out, double *rows_out /*[N,8] or NULL*/, void *stream);
+RSLO_API size_t rslo_surfel_register_ws_bytes(int N);
+RSLO_API int rslo_surfel_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                   int stride_floats, int N, const double *pose7, double max_dist, double robust_scale,
+                                   double *out29, void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_surfel_register(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                  int stride_floats, int N, double *pose7, int iters, double max_dist, double damping,
+                                  int min_pairs, double tol_t, double tol_r, double robust_scale, double *info /*[iters,8]*/,
+                                  void *ws, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

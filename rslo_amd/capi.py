@@ -235,6 +235,17 @@ SIGNATURES = {
                          [_i, C.c_double, _vp, _vp, _vp, _vp]),
     "rslo_loop_edges_reset": (C.c_int, [_vp, _vp, _vp, _vp, _i, _vp]),
     "rslo_loop_emit": (C.c_int, [_vp, _i, _vp, _sz, _i64, _i, _vp, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp]),
+    "rslo_surfel_bytes": (_sz, [_i64]),
+    "rslo_surfel_reset": (C.c_int, [_vp, _sz, _i64, C.c_double, C.c_double, C.c_double, _i, C.c_double, C.c_double, _vp]),
+    "rslo_surfel_insert_ws_bytes": (_sz, [_i]),
+    "rslo_surfel_insert": (C.c_int, [_vp, _sz, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "rslo_surfel_insert_frames": (C.c_int, [_vp, _sz, _vp, _sz, _i64, _i, _vp, _i, _vp]),
+    "rslo_surfel_export": (C.c_int, [_vp, _sz, _i, _vp, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp]),
+    "rslo_surfel_nearest": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "rslo_surfel_register_ws_bytes": (_sz, [_i]),
+    "rslo_surfel_normal_eq": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_surfel_register": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, _i, C.c_double, C.c_double, _i, C.c_double,
+                                       C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
 }
 
 
@@ -1395,6 +1406,150 @@ def map_register_sched(bufs, voxel_sizes, stages, points, pose, metric="plane", 
                                        float(damping), int(min_pairs), float(tol_t), float(tol_r),
                                        _ptr(info, torch.float64, "info"), ws.data_ptr(), ws.numel() * ws.element_size(),
                                        _stream()), "rslo_map_register_sched")
+    return info
+
+
+# --------------------------------------------------------------------------------------
+# surfel map (csrc/surfel.hip; rules: include/rslo_hip.h "Surfel map"); the owning class is rslo_amd/surfels.py SurfelMap
+# --------------------------------------------------------------------------------------
+SURFEL_HDR_COUNTERS = 8   # first int64 word of the seven counters in a surfel map's header
+SURFEL_COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full", "n_planar")
+
+
+def surfel_bytes(capacity):
+    """rslo_surfel_bytes: bytes of a surfel map of `capacity` slots, 0 unless capacity is a power of two >= 1024."""
+    return int(lib().rslo_surfel_bytes(int(capacity)))
+
+
+def surfel_insert_ws(n_points, device):
+    """a workspace for surfel_insert of up to n_points points"""
+    return torch.empty((int(lib().rslo_surfel_insert_ws_bytes(int(n_points))),), dtype=torch.uint8, device=device)
+
+
+def surfel_register_ws(n_points, device):
+    """a workspace for surfel_normal_eq / surfel_register over up to n_points points"""
+    return torch.empty((int(lib().rslo_surfel_register_ws_bytes(int(n_points))) // 8,), dtype=torch.int64, device=device)
+
+
+def surfel_reset(buf, capacity, voxel_size, min_range=0.0, max_range=float("inf"), min_points=5, planar_ratio=0.1,
+                 line_ratio=0.05):
+    """rslo_surfel_reset on the current stream: empties the table and writes the header."""
+    ptr, nbytes = _map_buf(buf)
+    _chk(lib().rslo_surfel_reset(ptr, nbytes, int(capacity), float(voxel_size), float(min_range), float(max_range),
+                                 int(min_points), float(planar_ratio), float(line_ratio), _stream()), "rslo_surfel_reset")
+
+
+def surfel_insert(buf, points, pose, ws):
+    """rslo_surfel_insert: one scan (fp32 CUDA [P, F >= 3], read in place, only x y z are read) under pose (float64 CUDA
+    [7]) on the current stream.  ws: >= rslo_surfel_insert_ws_bytes(P) bytes.  Three launches, no host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    _chk(lib().rslo_surfel_insert(ptr, nbytes, src, stride, int(points.shape[0]), _pose7(pose, "surfel_insert"), _ptr(ws),
+                                  ws.numel() * ws.element_size(), _stream()), "rslo_surfel_insert")
+
+
+def surfel_insert_frames(buf, store_buf, capacity, K, poses):
+    """rslo_surfel_insert_frames: every frame of the keyframe store store_buf under its own row of poses (float64 CUDA
+    [n, 7], contiguous), as n successive surfel_insert calls would leave the table.  Three launches, no host read."""
+    ptr, nbytes = _map_buf(buf)
+    sptr, sbytes = _map_buf(store_buf)
+    if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float64 and poses.dim() == 2
+            and poses.shape[1] == 7 and poses.is_contiguous()):
+        raise RsloHipError("surfel_insert_frames: poses must be contiguous float64 [n, 7] rows (t, q wxyz) on the GPU")
+    if poses.device != buf.device or store_buf.device != buf.device:
+        raise RsloHipError("surfel_insert_frames: the map, the store and the poses must live on one device")
+    if poses.shape[0] == 0:      # an empty tensor has no address to hand over; the call would launch nothing
+        return
+    _chk(lib().rslo_surfel_insert_frames(ptr, nbytes, sptr, sbytes, int(capacity), int(K), poses.data_ptr(),
+                                         int(poses.shape[0]), _stream()), "rslo_surfel_insert_frames")
+
+
+def surfel_export(buf, min_flag=1, center=None, radius=0.0, keys=None, moments=None, rows=None, counts=None):
+    """rslo_surfel_export into preallocated keys int64 [R], moments int64 [R, 10], rows float64 [R, 8] (all None: R = 0,
+    count only); center: None or float64 CUDA [3].  Returns counts, int64 CUDA [2] = {matching, written}.  No host read."""
+    ptr, nbytes = _map_buf(buf)
+    R = 0 if keys is None else keys.shape[0]
+    if R and (keys.shape != (R,) or moments is None or rows is None or moments.shape != (R, 10) or rows.shape != (R, 8)):
+        raise RsloHipError("surfel_export: keys [R], moments [R, 10] and rows [R, 8] go together")
+    if center is not None and not (center.is_cuda and center.dtype == torch.float64 and center.numel() == 3
+                                   and center.is_contiguous()):
+        raise RsloHipError("surfel_export: center must be 3 contiguous float64 values on the GPU")
+    if counts is None:
+        counts = torch.empty((2,), dtype=torch.int64, device=buf.device)
+    _chk(lib().rslo_surfel_export(ptr, nbytes, int(min_flag), _dp(center), float(radius),
+                                  _ptr(keys, torch.int64, "keys") if R else None,
+                                  _ptr(moments, torch.int64, "moments") if R else None,
+                                  _ptr(rows, torch.float64, "rows") if R else None, R,
+                                  _ptr(counts, torch.int64, "counts"), _stream()), "rslo_surfel_export")
+    return counts
+
+
+def surfel_nearest(buf, points, pose, voxel_size, max_dist=None, rows=None, keys=None, d2=None):
+    """rslo_surfel_nearest: the planar cell whose mean is nearest to every point (fp32 CUDA [P, F >= 3]) under pose within
+    max_dist (None: voxel_size).  Returns (keys int64 [P], d2 float64 [P]) -- -1 / -1.0 without a match -- and, with
+    rows=True or a float64 [P, 8] tensor, the matched rows (zeros without a match).  Read-only, no host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if keys is None:
+        keys = torch.empty((P,), dtype=torch.int64, device=points.device)
+    if d2 is None:
+        d2 = torch.empty((P,), dtype=torch.float64, device=points.device)
+    if rows is True:
+        rows = torch.empty((P, 8), dtype=torch.float64, device=points.device)
+    if keys.shape != (P,) or d2.shape != (P,) or (rows is not None and rows.shape != (P, 8)):
+        raise RsloHipError("surfel_nearest: keys and d2 must be [P], rows [P, 8]")
+    _chk(lib().rslo_surfel_nearest(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_nearest"),
+                                   float(voxel_size if max_dist is None else max_dist), _ptr(keys, torch.int64, "keys"),
+                                   _ptr(d2, torch.float64, "d2"), _ptr(rows, torch.float64, "rows"), _stream()),
+         "rslo_surfel_nearest")
+    return (keys, d2) if rows is None else (keys, d2, rows)
+
+
+def _surfel_ws(ws, P, device):
+    if ws is None:
+        return surfel_register_ws(P, device)
+    if not (ws.is_cuda and ws.is_contiguous()):
+        raise RsloHipError("surfel: the workspace must be a contiguous CUDA tensor")
+    return ws
+
+
+def surfel_normal_eq(buf, points, pose, voxel_size, max_dist=None, robust_scale=0.0, out=None, ws=None):
+    """rslo_surfel_normal_eq: out float64 CUDA [29] = the upper triangle of H (21), g (6), cost, pairs of the plane terms
+    of the matches of surfel_nearest at pose; robust_scale > 0: Geman-McClure weights.  No host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if out is None:
+        out = torch.empty((29,), dtype=torch.float64, device=points.device)
+    if out.shape != (29,):
+        raise RsloHipError("surfel_normal_eq: out must be [29]")
+    ws = _surfel_ws(ws, P, points.device)
+    _chk(lib().rslo_surfel_normal_eq(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_normal_eq"),
+                                     float(voxel_size if max_dist is None else max_dist), float(robust_scale),
+                                     _ptr(out, torch.float64, "out"), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                     _stream()), "rslo_surfel_normal_eq")
+    return out
+
+
+def surfel_register(buf, points, pose, voxel_size, iters=4, max_dist=None, damping=0.0, min_pairs=50, tol_t=0.0, tol_r=0.0,
+                    robust_scale=0.0, info=None, ws=None):
+    """rslo_surfel_register: `iters` Gauss-Newton iterations of points against the surfel map; pose (float64 CUDA [7]) is
+    updated IN PLACE.  Returns info float64 CUDA [iters, 8]: rows {status, pairs, cost, |dt|, theta, 0, 0, 0}, statuses
+    as map_register.  No host read, a fixed number of launches: capturable."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    iters = int(iters)
+    if info is None:
+        info = torch.empty((max(iters, 0), 8), dtype=torch.float64, device=points.device)
+    if info.shape != (iters, 8):
+        raise RsloHipError("surfel_register: info must be [iters, 8]")
+    ws = _surfel_ws(ws, P, points.device)
+    _chk(lib().rslo_surfel_register(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_register"), iters,
+                                    float(voxel_size if max_dist is None else max_dist), float(damping), int(min_pairs),
+                                    float(tol_t), float(tol_r), float(robust_scale), _ptr(info, torch.float64, "info"),
+                                    ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_surfel_register")
     return info
 
 

@@ -1,0 +1,768 @@
+// Surfel map: a voxel hash whose cells hold the integer moments of every point ever inserted into them, and the plane
+// (mean, normal, variance along the normal) those moments give; a registration target for the plane metric that needs
+// no scan normals (rules: include/rslo_hip.h "Surfel map"; float64 restatement: rslo_amd/surfels.py SurfelMapRef).
+//
+// One caller-owned allocation: header (256 bytes) | keys u64 [cap] | moments i64 [cap, 10] | rows f64 [cap, 8] |
+// dirty i32 [cap].  The table is the world voxel map's (map_table.h: map_point, map_mix, the bounded probe).
+//
+// Order freedom.  A point adds fixed-point INTEGERS to its cell -- count, the three first and the six second moments of
+// its position inside the cell in units of voxel / 16384 -- by 64-bit integer atomics (the lanes of a wave that follow
+// one another into the same slot add up first: sf_add).  Integer sums do not depend on the order or the grouping of
+// the adds, so the moments of a cell are a function of the SET of points inserted; the row of a cell is a function of
+// its moments, its key and the header, computed by one thread in a fixed order of IEEE double operations.
+// No floating-point atomic anywhere.
+//
+// Visibility: inside the moments kernel every decision rests on the return value of an atomic (the CAS on the key);
+// moments are only added to, never read.  The derive kernel is a kernel boundary later: there the moments are final for
+// the call, and the one thread that takes a slot's dirty word (atomicExch per scan point, or the slot's own thread in
+// the per-slot pass of rslo_surfel_insert_frames) reads them and writes the row.  The search kernels only READ the
+// table.  Nothing communicates across workgroups except through integer atomics and kernel boundaries.
+#include "rslo_common.h"
+
+#include <cstddef>
+#include <math.h>
+
+#include "map_table.h"
+#include "kf_store.h"            /* rslo_surfel_insert_frames reads a keyframe store */
+
+#pragma clang fp contract(off)   /* every rule is stated operation by operation */
+
+#include "gauss_newton.h"        /* after the pragma and after map_table.h's se3.h */
+
+#define SF_MAGIC 0x52534c4f53524631ull   /* "RSLOSRF1" */
+#define SF_HDR_BYTES 256
+#define SF_SLOT_BYTES 156                /* key 8 + moments 80 + row 64 + dirty 4 */
+#define SF_Q 16384.0                     /* fixed-point steps per cell edge */
+#define SF_BLOCK 256
+#define SF_WS_HDR 256                    /* register workspace: int32 word 0 is the "converged" flag */
+#define SF_MAX_ITERS 32
+#define SF_FRAMES_BLOCKS 2048u
+
+struct SurfHdr {                         // int64 words: 0 magic, 1 capacity, 2-4 map parameters, 5-7 plane parameters, 8-14 counters
+  map_u64 magic;
+  long long capacity;
+  double voxel, min_range, max_range;
+  long long min_points;
+  double planar_ratio, line_ratio;
+  map_u64 n_scans, n_cells, n_points, dropped_invalid, dropped_range, dropped_full, n_planar;
+};
+static_assert(sizeof(SurfHdr) <= SF_HDR_BYTES, "surfel header");
+
+struct SurfView {
+  SurfHdr *hdr;
+  map_u64 *keys;
+  long long *mom;
+  double *rows;
+  int32_t *dirty;
+};
+
+__device__ __forceinline__ bool sf_view(void *map, long long cap_max, SurfView &v) {
+  SurfHdr *h = (SurfHdr *)map;
+  const long long cap = h->capacity;
+  if (h->magic != SF_MAGIC || cap < MAP_MIN_CAP || cap > cap_max || (cap & (cap - 1))) return false;
+  unsigned char *p = (unsigned char *)map + SF_HDR_BYTES;
+  v.hdr = h;
+  v.keys = (map_u64 *)p;
+  v.mom = (long long *)(p + (size_t)cap * 8);
+  v.rows = (double *)(p + (size_t)cap * 88);
+  v.dirty = (int32_t *)(p + (size_t)cap * 152);
+  return true;
+}
+
+// reset, and with the cell edge the caller was checked against
+__device__ __forceinline__ bool sf_view_of(const void *map, long long cap_max, double voxel, SurfView &v) {
+  return sf_view((void *)map, cap_max, v) && v.hdr->voxel == voxel;
+}
+
+extern "C" size_t rslo_surfel_bytes(int64_t capacity) {
+  if (capacity < MAP_MIN_CAP || capacity > ((int64_t)1 << 31) || (capacity & (capacity - 1))) return 0;
+  return (size_t)SF_HDR_BYTES + (size_t)SF_SLOT_BYTES * (size_t)capacity;
+}
+
+static long long sf_cap_of_bytes(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
+  long long cap = 0;
+  for (long long c = MAP_MIN_CAP; c <= ((long long)1 << 31) && rslo_surfel_bytes(c) <= bytes; c *= 2) cap = c;
+  return cap;
+}
+
+__global__ __launch_bounds__(256) void k_surfel_reset(void *map, long long cap, double voxel, double min_range,
+                                                      double max_range, int min_points, double planar_ratio,
+                                                      double line_ratio) {
+  unsigned char *p = (unsigned char *)map + SF_HDR_BYTES;
+  map_u64 *keys = (map_u64 *)p;
+  long long *mom = (long long *)(p + (size_t)cap * 8);
+  double *rows = (double *)(p + (size_t)cap * 88);
+  int32_t *dirty = (int32_t *)(p + (size_t)cap * 152);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    SurfHdr *h = (SurfHdr *)map;
+    h->magic = SF_MAGIC;
+    h->capacity = cap;
+    h->voxel = voxel;
+    h->min_range = min_range;
+    h->max_range = max_range;
+    h->min_points = min_points;
+    h->planar_ratio = planar_ratio;
+    h->line_ratio = line_ratio;
+    h->n_scans = h->n_cells = h->n_points = h->dropped_invalid = h->dropped_range = h->dropped_full = h->n_planar = 0;
+  }
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    keys[s] = MAP_KEY_NONE;
+    for (int k = 0; k < 10; ++k) mom[s * 10 + k] = 0;
+    for (int k = 0; k < 8; ++k) rows[s * 8 + k] = 0.0;
+    dirty[s] = 0;
+  }
+}
+
+// the five header counters an insert adds to, in the header's order (n_cells .. dropped_full)
+struct SurfTally {
+  map_u64 n_cells, n_points, dropped_invalid, dropped_range, dropped_full;
+};
+static_assert(offsetof(SurfHdr, n_points) == offsetof(SurfHdr, n_cells) + 8 &&
+              offsetof(SurfHdr, dropped_invalid) == offsetof(SurfHdr, n_cells) + 16 &&
+              offsetof(SurfHdr, dropped_range) == offsetof(SurfHdr, n_cells) + 24 &&
+              offsetof(SurfHdr, dropped_full) == offsetof(SurfHdr, n_cells) + 32, "SurfTally mirrors the header's counters");
+
+// One point (p: x, y, z) under `pose` into the table: the probe of map.hip's map_put; counters go to `c`, the header
+// itself or a workgroup's tally in LDS.  -> the slot and the point's fixed-point position q in its cell, or -1 for a
+// point that was dropped.  The one probe of both calls.
+template <class Counters>
+__device__ __forceinline__ int32_t sf_slot(const SurfView &m, Counters *c, const float *__restrict__ p,
+                                           const double *__restrict__ pose, long long *q) {
+  map_u64 key;
+  double w[3];
+  const double voxel = m.hdr->voxel;
+  const int why = map_point(p, pose, voxel, m.hdr->min_range, m.hdr->max_range, key, w);
+  if (why) {      // both adds by every dropped lane, each to one address (see map_put)
+    atomicAdd(&c->dropped_invalid, (map_u64)(why == 1));
+    atomicAdd(&c->dropped_range, (map_u64)(why == 2));
+    return -1;
+  }
+  const map_u64 mask = (map_u64)m.hdr->capacity - 1;
+  map_u64 s = map_mix(key) & mask;
+  int found = 0;
+  for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
+    map_u64 prev = __builtin_nontemporal_load(&m.keys[s]);      // a stale read can only show "empty": then the CAS decides
+    if (prev == MAP_KEY_NONE) {
+      prev = atomicCAS(&m.keys[s], MAP_KEY_NONE, key);
+      if (prev == MAP_KEY_NONE) {
+        atomicAdd(&c->n_cells, (map_u64)1);
+        prev = key;
+      }
+    }
+    if (prev == key) {
+      found = 1;
+      break;
+    }
+    s = (s + 1) & mask;
+  }
+  if (!found) {
+    atomicAdd(&c->dropped_full, (map_u64)1);
+    return -1;
+  }
+  for (int a = 0; a < 3; ++a) {
+    const double sc = w[a] / voxel;
+    const double f = sc - floor(sc);                     // 1.0 for a tiny negative sc: the clamp below is part of the rule
+    long long v = (long long)floor(f * SF_Q);
+    q[a] = v < 0 ? 0 : (v > 16383 ? 16383 : v);
+  }
+  atomicAdd(&c->n_points, (map_u64)1);
+  return (int32_t)s;      // capacity <= 2^31 slots
+}
+
+// The ten adds of a wave's points, called by EVERY lane of the wave (s = -1: nothing to add).  Consecutive points of a
+// scan mostly share a cell (a beam sweeps 3 cm per point at 10 m), and adds to one address are served one after the
+// other on the memory side: measured, the plain ten atomics per point took 110 us per 119k-point scan at 0.4 m cells
+// and 193 us at 0.8 m, against 30 us for the voxel map's insert -- the time grew with the cell, not with the bytes.  So
+// the lanes of a RUN of equal slots (adjacent lanes only) add up inside the wave, by a segmented inclusive scan, and
+// the last lane of a run issues the run's ten atomics.  Integer sums: no bit of the table depends on the grouping.
+__device__ __forceinline__ void sf_add(const SurfView &m, int32_t s, const long long *q) {
+  const int lane = threadIdx.x & 63;
+  const int32_t before = __shfl_up(s, 1, 64);
+  const map_u64 heads = __ballot(lane == 0 || before != s);             // bit l: lane l starts a run (bit 0 always)
+  const int start = 63 - __builtin_clzll(heads & (~(map_u64)0 >> (63 - lane)));      // first lane of this lane's run
+  map_u64 v[10] = {1, (map_u64)q[0], (map_u64)q[1], (map_u64)q[2], (map_u64)(q[0] * q[0]), (map_u64)(q[0] * q[1]),
+                   (map_u64)(q[0] * q[2]), (map_u64)(q[1] * q[1]), (map_u64)(q[1] * q[2]), (map_u64)(q[2] * q[2])};
+  for (int off = 1; off < 64; off <<= 1) {
+    const bool take = lane - off >= start;
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      const map_u64 t = __shfl_up(v[k], off, 64);
+      if (take) v[k] += t;
+    }
+  }
+  const bool tail = lane == 63 || ((heads >> (lane + 1)) & 1);
+  if (tail && s >= 0) {
+    map_u64 *mo = (map_u64 *)(m.mom + (size_t)s * 10);      // two's complement: the unsigned add is the signed add
+#pragma unroll
+    for (int k = 0; k < 10; ++k) atomicAdd(mo + k, v[k]);
+    m.dirty[s] = 1;      // every writer stores the same word; the kernel boundary publishes it
+  }
+}
+
+// nm_rot of csrc/normals.hip in double: one cyclic-Jacobi rotation that annihilates a_pq (r is the third index)
+__device__ __forceinline__ void sf_rot(double &app, double &aqq, double &apq, double &arp, double &arq, double &v0p,
+                                       double &v0q, double &v1p, double &v1q, double &v2p, double &v2q) {
+  if (apq == 0.0) return;
+  const double theta = (aqq - app) / (2.0 * apq);
+  const double t = copysign(1.0, theta) / (fabs(theta) + sqrt(theta * theta + 1.0));
+  const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+  app = app - t * apq;
+  aqq = aqq + t * apq;
+  apq = 0.0;
+  double u = arp;
+  arp = c * u - s * arq;
+  arq = s * u + c * arq;
+  u = v0p; v0p = c * u - s * v0q; v0q = s * u + c * v0q;
+  u = v1p; v1p = c * u - s * v1q; v1q = s * u + c * v1q;
+  u = v2p; v2p = c * u - s * v2q; v2q = s * u + c * v2q;
+}
+
+// The row of slot s from its moments, its key and the header (rules: "Derive"), written in place.  -> the change of
+// the slot's "planar" bit (new flag == 2) - (old flag == 2).  Shared by the per-scan and the per-slot pass.
+__device__ __forceinline__ int sf_derive(const SurfView &m, size_t s) {
+  const long long *mo = m.mom + s * 10;
+  double *row = m.rows + s * 8;
+  const int was = row[7] == 2.0;
+  const long long N = mo[0];
+  const double n = (double)N;
+  const double mu0 = (double)mo[1] / n, mu1 = (double)mo[2] / n, mu2 = (double)mo[3] / n;
+  double a00 = (double)mo[4] / n - mu0 * mu0, a01 = (double)mo[5] / n - mu0 * mu1, a02 = (double)mo[6] / n - mu0 * mu2;
+  double a11 = (double)mo[7] / n - mu1 * mu1, a12 = (double)mo[8] / n - mu1 * mu2, a22 = (double)mo[9] / n - mu2 * mu2;
+  const double tr = (a00 + a11) + a22;
+  if (N < m.hdr->min_points || !(tr > 0.0 && tr < (double)__builtin_inff())) {
+    for (int k = 0; k < 8; ++k) row[k] = 0.0;
+    return 0 - was;
+  }
+  a00 = a00 / tr; a01 = a01 / tr; a02 = a02 / tr; a11 = a11 / tr; a12 = a12 / tr; a22 = a22 / tr;
+  double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
+  for (int sweep = 0; sweep < 6; ++sweep) {
+    sf_rot(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);     // (p, q, r) = (0, 1, 2)
+    sf_rot(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);     // (0, 2, 1)
+    sf_rot(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);     // (1, 2, 0)
+  }
+  const bool c1 = a11 < a00;                       // smallest eigenvalue, ties to the lower index (k_nm_normals)
+  const bool c2 = a22 < (c1 ? a11 : a00);
+  const double l0 = c2 ? a22 : (c1 ? a11 : a00);
+  const double ra = c2 ? a00 : (c1 ? a00 : a11), rb = c2 ? a11 : a22;      // the other two, lower index first
+  const bool c3 = rb < ra;
+  const double l1 = c3 ? rb : ra, l2 = c3 ? ra : rb;
+  const double ex = c2 ? v02 : (c1 ? v01 : v00), ey = c2 ? v12 : (c1 ? v11 : v10), ez = c2 ? v22 : (c1 ? v21 : v20);
+  const double nn = sqrt((ex * ex + ey * ey) + ez * ez);
+  double nx = ex / nn, ny = ey / nn, nz = ez / nn;
+  double big = nx;                                 // the component of largest magnitude, ties to the lower axis
+  if (fabs(ny) > fabs(big)) big = ny;
+  if (fabs(nz) > fabs(big)) big = nz;
+  if (big < 0.0) {
+    nx = -nx; ny = -ny; nz = -nz;
+  }
+  const map_u64 key = m.keys[s];
+  const double voxel = m.hdr->voxel;
+  const double cx = (double)((long long)((key >> 42) & 0x1fffff) - 1048576);
+  const double cy = (double)((long long)((key >> 21) & 0x1fffff) - 1048576);
+  const double cz = (double)((long long)(key & 0x1fffff) - 1048576);
+  const double u = voxel / SF_Q;
+  const int planar = l0 <= m.hdr->planar_ratio * l1 && l1 >= m.hdr->line_ratio * l2;
+  row[0] = (cx + (mu0 + 0.5) / SF_Q) * voxel;
+  row[1] = (cy + (mu1 + 0.5) / SF_Q) * voxel;
+  row[2] = (cz + (mu2 + 0.5) / SF_Q) * voxel;
+  row[3] = nx;
+  row[4] = ny;
+  row[5] = nz;
+  row[6] = ((l0 * tr) * u) * u;
+  row[7] = planar ? 2.0 : 1.0;
+  return planar - was;
+}
+
+__global__ __launch_bounds__(256) void k_surfel_moments(void *map, long long cap_max, const float *__restrict__ points,
+                                                        int stride, int N, const double *__restrict__ pose,
+                                                        int32_t *__restrict__ slot_of) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  SurfView m;
+  if (!sf_view(map, cap_max, m)) {      // uniform over the grid
+    if (i < N) slot_of[i] = -1;
+    return;
+  }
+  int32_t s = -1;
+  long long q[3] = {0, 0, 0};
+  if (i < N) {
+    s = sf_slot(m, m.hdr, points + (int64_t)i * stride, pose, q);
+    slot_of[i] = s;
+  }
+  sf_add(m, s, q);      // every lane of the wave, the ones past N included
+}
+
+// behind the kernel boundary the moments are final for this scan: whoever takes a slot's dirty word derives its row.
+// n_planar moves by the workgroup's integer sum, one add per workgroup.
+__global__ __launch_bounds__(256) void k_surfel_derive_scan(void *map, long long cap_max, int N,
+                                                            const int32_t *__restrict__ slot_of) {
+  __shared__ int moved;
+  if (threadIdx.x == 0) moved = 0;
+  __syncthreads();
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  SurfView m;
+  const bool ok = sf_view(map, cap_max, m);      // uniform over the grid
+  if (ok && i < N) {
+    const int32_t s = slot_of[i];
+    // (a plain pre-read of the dirty word in front of the exchange was tried: 28 us per 119k-point scan with and without)
+    if (s >= 0 && (long long)s < m.hdr->capacity && atomicExch(&m.dirty[s], 0) == 1) {
+      const int d = sf_derive(m, (size_t)s);
+      if (d) atomicAdd(&moved, d);
+    }
+  }
+  __syncthreads();
+  if (ok && threadIdx.x == 0 && moved) atomicAdd(&m.hdr->n_planar, (map_u64)(long long)moved);
+}
+
+__global__ void k_surfel_scan_done(void *map, long long cap_max) {
+  SurfView m;
+  if (threadIdx.x == 0 && sf_view(map, cap_max, m)) m.hdr->n_scans = m.hdr->n_scans + 1;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rslo_surfel_insert_frames: every frame of a keyframe store under its own pose.  Three launches whatever the data.
+// ---------------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ long long sf_frames_n(const KfView &v, int n_poses) {
+  long long n = v.hdr->n_entries;
+  n = n < 0 ? 0 : (n > v.hdr->capacity ? v.hdr->capacity : n);
+  return n < (long long)n_poses ? n : (long long)n_poses;
+}
+
+// pass 1: one thread per (frame, row) in tiles of 256 rows, bpf tiles per frame; a workgroup takes tiles blockIdx.x,
+// blockIdx.x + gridDim.x, ... and counts in LDS: the header gets one add per workgroup and non-zero counter (map.hip).
+__global__ __launch_bounds__(256) void k_surfel_frames_points(void *map, long long cap_max, void *store, size_t store_bytes,
+                                                              long long kf_cap, int K, const double *__restrict__ poses,
+                                                              int n_poses, int bpf) {
+  __shared__ SurfTally tally;
+  if (threadIdx.x < 5) ((map_u64 *)&tally)[threadIdx.x] = 0;
+  __syncthreads();
+  SurfView m;
+  KfView v;
+  if (!sf_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;      // uniform over the grid
+  const long long tiles = sf_frames_n(v, n_poses) * bpf;
+  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+    const long long e = tile / bpf;
+    const int i = (int)(tile % bpf) * 256 + (int)threadIdx.x;
+    int count = v.counts[e];
+    count = count < 0 ? 0 : (count > K ? K : count);
+    int32_t s = -1;
+    long long q[3] = {0, 0, 0};
+    if (i < count) {
+      const float4 r = *(const float4 *)(v.rows + ((size_t)e * K + i) * 4);
+      const float p[3] = {r.x, r.y, r.z};
+      s = sf_slot(m, &tally, p, poses + (size_t)e * 7, q);
+    }
+    sf_add(m, s, q);      // every lane of the wave
+  }
+  __syncthreads();
+  if (threadIdx.x < 5) {
+    const map_u64 add = ((map_u64 *)&tally)[threadIdx.x];
+    if (add) atomicAdd(&m.hdr->n_cells + threadIdx.x, add);
+  }
+}
+
+// pass 2, over the SLOTS: a slot belongs to one thread, which clears its dirty word and derives its row
+__global__ __launch_bounds__(256) void k_surfel_derive_slots(void *map, long long cap_max) {
+  __shared__ int moved;
+  if (threadIdx.x == 0) moved = 0;
+  __syncthreads();
+  SurfView m;
+  const bool ok = sf_view(map, cap_max, m);      // uniform over the grid
+  if (ok) {
+    const long long cap = m.hdr->capacity;
+    for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+      if (m.dirty[s] == 0) continue;
+      m.dirty[s] = 0;
+      const int d = sf_derive(m, (size_t)s);
+      if (d) atomicAdd(&moved, d);
+    }
+  }
+  __syncthreads();
+  if (ok && threadIdx.x == 0 && moved) atomicAdd(&m.hdr->n_planar, (map_u64)(long long)moved);
+}
+
+// pass 3: an empty frame still counts as a scan
+__global__ void k_surfel_frames_done(void *map, long long cap_max, void *store, size_t store_bytes, long long kf_cap, int K,
+                                     int n_poses) {
+  SurfView m;
+  KfView v;
+  if (threadIdx.x != 0 || !sf_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;
+  m.hdr->n_scans = m.hdr->n_scans + (map_u64)sf_frames_n(v, n_poses);
+}
+
+__global__ __launch_bounds__(256) void k_surfel_export(void *map, long long cap_max, int min_flag,
+                                                       const double *__restrict__ center, double radius,
+                                                       map_u64 *__restrict__ keys, long long *__restrict__ moments,
+                                                       double *__restrict__ rows, long long max_rows,
+                                                       map_u64 *__restrict__ counts) {
+  SurfView m;
+  if (!sf_view(map, cap_max, m)) return;
+  const long long cap = m.hdr->capacity;
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    const map_u64 key = m.keys[s];
+    if (key == MAP_KEY_NONE) continue;
+    const double *row = m.rows + (size_t)s * 8;
+    if (!(row[7] >= (double)min_flag)) continue;
+    if (center) {
+      const double dx = row[0] - center[0], dy = row[1] - center[1], dz = row[2] - center[2];
+      if (!(dx * dx + dy * dy + dz * dz < radius * radius)) continue;
+    }
+    const map_u64 o = atomicAdd(&counts[0], (map_u64)1);
+    if ((long long)o < max_rows) {
+      atomicAdd(&counts[1], (map_u64)1);
+      keys[o] = key;
+      for (int k = 0; k < 10; ++k) moments[o * 10 + k] = m.mom[(size_t)s * 10 + k];
+      for (int k = 0; k < 8; ++k) rows[o * 8 + k] = row[k];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Search and registration (rules: "Nearest", "Normal equations", "Register").  Read-only on the table.
+// ---------------------------------------------------------------------------------------------------------------------
+// The planar cell whose mean is nearest to w among the cells key + {-1,0,1}^3: slot, key and d2 of the winner (smallest
+// d2, then smallest key), d = w - mean.  The first-slot keys of all 27 chains are loaded before any is examined
+// (mapreg.hip's mr_nearest); rows are read for matching cells only.
+__device__ __forceinline__ bool sf_nearest(const SurfView &m, map_u64 key, const double *w, uint32_t &bslot, map_u64 &bkey,
+                                           double &bd2, double *d) {
+  const uint32_t mask = (uint32_t)((map_u64)m.hdr->capacity - 1);      // capacity <= 2^31
+  const int c[3] = {(int)(key >> 42) & 0x1fffff, (int)(key >> 21) & 0x1fffff, (int)key & 0x1fffff};
+  map_u64 k0[27];
+  uint32_t s0[27];
+#pragma unroll
+  for (int j = 0; j < 27; ++j) {
+    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
+    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
+    s0[j] = (uint32_t)map_mix(nk) & mask;      // (a neighbour outside the key space is not examined below; its slot is in range)
+    k0[j] = m.keys[s0[j]];
+  }
+  bool found = false;
+#pragma unroll
+  for (int j = 0; j < 27; ++j) {
+    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
+    if (x < 1 || x > 0x1fffff || y < 1 || y > 0x1fffff || z < 1 || z > 0x1fffff) continue;      // |cell| >= 2^20
+    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
+    map_u64 k = k0[j];
+    uint32_t s = s0[j];
+    for (int probe = 1; k != nk && k != MAP_KEY_NONE && probe < RSLO_MAP_MAX_PROBE; ++probe) {
+      s = (s + 1) & mask;
+      k = m.keys[s];
+    }
+    if (k != nk) continue;
+    const double *row = m.rows + (size_t)s * 8;
+    if (row[7] != 2.0) continue;
+    const double dx = w[0] - row[0], dy = w[1] - row[1], dz = w[2] - row[2];
+    const double d2 = dx * dx + dy * dy + dz * dz;
+    if (!found || d2 < bd2 || (d2 == bd2 && nk < bkey)) {
+      found = true;
+      bslot = s;
+      bkey = nk;
+      bd2 = d2;
+      d[0] = dx;
+      d[1] = dy;
+      d[2] = dz;
+    }
+  }
+  return found;
+}
+
+__global__ __launch_bounds__(SF_BLOCK) void k_surfel_nearest(const void *map, long long cap_max, double voxel,
+                                                             const float *__restrict__ points, int stride, int N,
+                                                             const double *__restrict__ pose, double max_dist,
+                                                             long long *__restrict__ keys_out, double *__restrict__ d2_out,
+                                                             double *__restrict__ rows_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  SurfView m;
+  long long kout = -1;
+  double d2 = -1.0;
+  map_u64 key, bkey;
+  double w[3], d[3], bd2;
+  uint32_t s;
+  const double *row = nullptr;
+  if (sf_view_of(map, cap_max, voxel, m) &&
+      !map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
+      sf_nearest(m, key, w, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
+    kout = (long long)bkey;
+    d2 = bd2;
+    row = m.rows + (size_t)s * 8;
+  }
+  keys_out[i] = kout;
+  d2_out[i] = d2;
+  if (rows_out)
+    for (int k = 0; k < 8; ++k) rows_out[(size_t)i * 8 + k] = row ? row[k] : 0.0;
+}
+
+// block partial [GN_NSUM] of the plane terms of points blockIdx.x * 256 .. + 255 at the pose in pose7.  WEIGHTED: the
+// 28 addends of a matched point are multiplied by rho = u*u, u = s2 / (s2 + e), e = r*r (s2 = scale*scale > 0).
+template <bool WEIGHTED>
+__global__ __launch_bounds__(SF_BLOCK) void k_surfel_accum(const void *map, long long cap_max, double voxel,
+                                                           const float *__restrict__ points, int stride, int N,
+                                                           const double *__restrict__ pose, double max_dist, int iter,
+                                                           const int32_t *__restrict__ flag,
+                                                           double *__restrict__ partials, double s2) {
+  if (iter > 0 && *flag) return;      // converged in an earlier iteration: the second stage does not read the partials
+  __shared__ double part[SF_BLOCK / 64 * GN_NSUM];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double acc[GN_NSUM];
+#pragma unroll
+  for (int k = 0; k < GN_NSUM; ++k) acc[k] = 0.0;
+  SurfView m;
+  map_u64 key, bkey;
+  double w[3], d[3], bd2;
+  uint32_t s;
+  if (i < N && sf_view_of(map, cap_max, voxel, m)) {
+    if (!map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
+        sf_nearest(m, key, w, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
+      const double *row = m.rows + (size_t)s * 8;
+      const double n[3] = {row[3], row[4], row[5]};      // already in the world frame
+      double wn[3];
+      se3_cross(w, n, wn);
+      gn_plane_terms(n, wn, n[0] * d[0] + n[1] * d[1] + n[2] * d[2], acc);
+      acc[GN_NSUM - 1] = 1.0;
+      if (WEIGHTED) {
+        const double u = s2 / (s2 + acc[GN_NSUM - 2]);
+        const double rho = u * u;
+#pragma unroll
+        for (int k = 0; k < GN_NSUM - 1; ++k) acc[k] = rho * acc[k];
+      }
+    }
+  }
+  gn_block_reduce(acc, part, SF_BLOCK / 64, partials + (size_t)blockIdx.x * GN_NSUM);
+}
+
+struct SfSolve {
+  int min_pairs;
+  double damping, tol_t, tol_r;
+};
+
+// Second stage, one wave, as mapreg.hip's: lane j sums partial j of the blocks in block order.  out29
+// (rslo_surfel_normal_eq) receives the sums; with pose7 (rslo_surfel_register) lane 0 then takes the Gauss-Newton step
+// of iteration `iter` and writes its info row.  Iteration 0 does not read the flag and rewrites it: that clears it.
+__global__ __launch_bounds__(64) void k_surfel_finish(const double *__restrict__ partials, int n_blocks,
+                                                      double *__restrict__ out29, double *__restrict__ pose7, int iter,
+                                                      SfSolve sp, int32_t *__restrict__ flag, double *__restrict__ info) {
+  __shared__ double tot[GN_NSUM];
+  double *row = info ? info + (size_t)iter * 8 : nullptr;
+  if (pose7 && iter > 0 && *flag) {
+    if (threadIdx.x < 8) row[threadIdx.x] = threadIdx.x == 0 ? 3.0 : 0.0;
+    return;
+  }
+  if (threadIdx.x < GN_NSUM) {
+    double v = 0.0;
+    for (int b = 0; b < n_blocks; ++b) v = v + partials[(size_t)b * GN_NSUM + threadIdx.x];
+    tot[threadIdx.x] = v;
+    if (out29) out29[threadIdx.x] = v;
+  }
+  __syncthreads();
+  if (!pose7 || threadIdx.x != 0) return;
+  int status = 0;
+  double nt = 0.0, th = 0.0;
+  const double pairs = tot[28], cost = tot[27];
+  if (pairs < (double)sp.min_pairs) {
+    status = 1;
+  } else if (!gn_step(tot, sp.damping, pose7, nt, th)) {
+    status = 2;      // not positive definite, or an overflowed step: no step
+    nt = th = 0.0;
+  }
+  *flag = (status == 0 && nt < sp.tol_t && th < sp.tol_r) ? 1 : 0;
+  row[0] = (double)status;
+  row[1] = pairs;
+  row[2] = cost;
+  row[3] = nt;
+  row[4] = th;
+  row[5] = row[6] = row[7] = 0.0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int rslo_surfel_reset(void *map, size_t map_bytes, int64_t capacity, double voxel_size, double min_range,
+                                 double max_range, int min_points, double planar_ratio, double line_ratio, void *stream) {
+  RSLO_CHECK_ARG(map && ((uintptr_t)map & 7) == 0, "surfel_reset: map is null or not 8-byte aligned");
+  RSLO_CHECK_ARG(rslo_surfel_bytes(capacity) != 0, "surfel_reset: capacity must be a power of two in 1024 .. 2^31");
+  RSLO_CHECK_ARG(map_bytes >= rslo_surfel_bytes(capacity), "surfel_reset: map_bytes is smaller than rslo_surfel_bytes(capacity)");
+  RSLO_CHECK_ARG(voxel_size > 0.0 && voxel_size < (double)__builtin_inff(),
+                 "surfel_reset: voxel_size must be positive and finite");
+  RSLO_CHECK_ARG(min_range >= 0.0 && min_range < max_range, "surfel_reset: need 0 <= min_range < max_range");
+  RSLO_CHECK_ARG(min_points >= 3, "surfel_reset: min_points must be >= 3");
+  RSLO_CHECK_ARG(planar_ratio >= 0.0 && planar_ratio < (double)__builtin_inff() && line_ratio >= 0.0 &&
+                     line_ratio < (double)__builtin_inff(),
+                 "surfel_reset: planar_ratio and line_ratio must be >= 0 and finite (NaN is refused)");
+  const unsigned nb = (unsigned)(capacity / 256 < 4096 ? capacity / 256 : 4096);
+  hipLaunchKernelGGL(k_surfel_reset, dim3(nb), dim3(256), 0, (hipStream_t)stream, map, (long long)capacity, voxel_size,
+                     min_range, max_range, min_points, planar_ratio, line_ratio);
+  RSLO_CHECK_LAUNCH("surfel_reset");
+  return RSLO_OK;
+}
+
+extern "C" size_t rslo_surfel_insert_ws_bytes(int N) {
+  return N < 0 ? 0 : 256 + ((size_t)N * 4 + 255) / 256 * 256;
+}
+
+extern "C" int rslo_surfel_insert(void *map, size_t map_bytes, const float *points, int stride_floats, int N,
+                                  const double *pose7, void *ws, size_t ws_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "surfel_insert: no map (map_bytes below rslo_surfel_bytes(1024))");
+  RSLO_CHECK_ARG(N >= 0 && stride_floats >= 3, "surfel_insert: N < 0 or stride_floats < 3");
+  RSLO_CHECK_ARG(pose7, "surfel_insert: pose7 is null");
+  if (N > 0) {
+    RSLO_CHECK_ARG(points && ws, "surfel_insert: null pointer");
+    if (ws_bytes < rslo_surfel_insert_ws_bytes(N)) {
+      rslo_set_error("surfel_insert: workspace too small");
+      return RSLO_EWS;
+    }
+    int32_t *slot_of = (int32_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    const unsigned nb = (unsigned)rslo_cdiv(N, 256);
+    hipLaunchKernelGGL(k_surfel_moments, dim3(nb), dim3(256), 0, s, map, cap_max, points, stride_floats, N, pose7, slot_of);
+    hipLaunchKernelGGL(k_surfel_derive_scan, dim3(nb), dim3(256), 0, s, map, cap_max, N, (const int32_t *)slot_of);
+  }
+  hipLaunchKernelGGL(k_surfel_scan_done, dim3(1), dim3(64), 0, s, map, cap_max);      // N == 0 still counts as a scan
+  RSLO_CHECK_LAUNCH("surfel_insert");
+  return RSLO_OK;
+}
+
+extern "C" int rslo_surfel_insert_frames(void *map, size_t map_bytes, const void *store, size_t store_bytes,
+                                         int64_t capacity, int K, const double *poses, int n_poses, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "surfel_insert_frames: no map (map_bytes below rslo_surfel_bytes(1024))");
+  RSLO_CHECK_ARG(store && ((uintptr_t)store & 15) == 0, "surfel_insert_frames: store is null or not 16-byte aligned");
+  RSLO_CHECK_ARG(kf_shape_ok(capacity, K),
+                 "surfel_insert_frames: need capacity in 1 .. 2^16 and K a multiple of 64 in 64 .. 4096");
+  RSLO_CHECK_ARG(store_bytes >= kf_bytes_of(capacity, K), "surfel_insert_frames: store_bytes is smaller than rslo_keyframe_bytes");
+  RSLO_CHECK_ARG(poses, "surfel_insert_frames: poses is null");
+  RSLO_CHECK_ARG(n_poses >= 0, "surfel_insert_frames: n_poses < 0");
+  if (n_poses == 0) return RSLO_OK;
+  const int frames = n_poses < capacity ? n_poses : (int)capacity;      // the store holds no more
+  const int bpf = (int)rslo_cdiv(K, 256);
+  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  const unsigned tiles = (unsigned)frames * (unsigned)bpf;      // <= 2^16 * 16
+  hipLaunchKernelGGL(k_surfel_frames_points, dim3(tiles < SF_FRAMES_BLOCKS ? tiles : SF_FRAMES_BLOCKS), dim3(256), 0, s,
+                     map, cap_max, (void *)store, store_bytes, (long long)capacity, K, poses, n_poses, bpf);
+  hipLaunchKernelGGL(k_surfel_derive_slots, dim3(nb), dim3(256), 0, s, map, cap_max);
+  hipLaunchKernelGGL(k_surfel_frames_done, dim3(1), dim3(64), 0, s, map, cap_max, (void *)store, store_bytes,
+                     (long long)capacity, K, n_poses);
+  RSLO_CHECK_LAUNCH("surfel_insert_frames");
+  return RSLO_OK;
+}
+
+extern "C" int rslo_surfel_export(const void *map, size_t map_bytes, int min_flag, const double *center3, double radius,
+                                  uint64_t *keys, int64_t *moments, double *rows, int64_t max_rows, int64_t *counts,
+                                  void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "surfel_export: no map (map_bytes below rslo_surfel_bytes(1024))");
+  RSLO_CHECK_ARG(min_flag >= 0 && min_flag <= 2, "surfel_export: min_flag must be 0, 1 or 2");
+  RSLO_CHECK_ARG(counts && max_rows >= 0, "surfel_export: counts is null or max_rows < 0");
+  RSLO_CHECK_ARG(max_rows == 0 || (keys && moments && rows), "surfel_export: null output");
+  RSLO_CHECK_ARG(!center3 || radius >= 0.0, "surfel_export: radius must be >= 0 (NaN is refused)");
+  RSLO_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s));
+  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  hipLaunchKernelGGL(k_surfel_export, dim3(nb), dim3(256), 0, s, (void *)map, cap_max, min_flag, center3, radius,
+                     (map_u64 *)keys, (long long *)moments, rows, (long long)max_rows, (map_u64 *)counts);
+  RSLO_CHECK_LAUNCH("surfel_export");
+  return RSLO_OK;
+}
+
+static int sf_check(const char *name, const void *map, long long cap_max, double voxel, int stride, int N,
+                    const double *pose7, double max_dist) {
+  RSLO_CHECK_ARG(map && cap_max > 0, "%s: no map (map_bytes below rslo_surfel_bytes(1024))", name);
+  RSLO_CHECK_ARG(N >= 0 && stride >= 3, "%s: N < 0 or stride_floats < 3", name);
+  RSLO_CHECK_ARG(pose7, "%s: pose7 is null", name);
+  RSLO_CHECK_ARG(voxel > 0.0 && voxel < (double)__builtin_inff(), "%s: voxel_size must be positive and finite", name);
+  RSLO_CHECK_ARG(max_dist > 0.0 && max_dist <= voxel, "%s: need 0 < max_dist <= voxel_size (NaN is refused)", name);
+  return RSLO_OK;
+}
+
+extern "C" int rslo_surfel_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                   int stride_floats, int N, const double *pose7, double max_dist, int64_t *keys_out,
+                                   double *d2_out, double *rows_out, void *stream) {
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  const int rc = sf_check("surfel_nearest", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  if (N == 0) return RSLO_OK;
+  RSLO_CHECK_ARG(points && keys_out && d2_out, "surfel_nearest: null pointer");
+  hipLaunchKernelGGL(k_surfel_nearest, dim3((unsigned)rslo_cdiv(N, SF_BLOCK)), dim3(SF_BLOCK), 0, (hipStream_t)stream, map,
+                     cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, (long long *)keys_out, d2_out,
+                     rows_out);
+  RSLO_CHECK_LAUNCH("surfel_nearest");
+  return RSLO_OK;
+}
+
+extern "C" size_t rslo_surfel_register_ws_bytes(int N) {
+  if (N < 0) return 0;
+  const size_t nb = N > 0 ? (size_t)rslo_cdiv(N, SF_BLOCK) : 1;
+  return SF_WS_HDR + (nb * GN_NSUM * sizeof(double) + 255) / 256 * 256;
+}
+
+static bool sf_scale_ok(double scale) {      // the rule of "Robust weight"
+  const double s2 = scale * scale;
+  return scale == 0.0 || (scale > 0.0 && s2 > 0.0 && s2 < (double)__builtin_inff());
+}
+
+static int sf_check_sums(const char *name, const float *points, int N, double scale, void *ws, size_t ws_bytes) {
+  RSLO_CHECK_ARG(sf_scale_ok(scale), "%s: robust_scale must be 0 (no weights) or positive with a finite, non-zero square", name);
+  RSLO_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && (N == 0 || points),
+                 "%s: null pointer, or a workspace that is not 8-byte aligned", name);
+  if (ws_bytes < rslo_surfel_register_ws_bytes(N)) {
+    rslo_set_error("%s: workspace too small", name);
+    return RSLO_EWS;
+  }
+  return RSLO_OK;
+}
+
+// the launches of one evaluation of the normal equations (+ the step of iteration `iter` when pose_rw is given)
+static void sf_launch(const void *map, long long cap_max, double voxel, const float *points, int stride, int N,
+                      const double *pose, double max_dist, double scale, double *out29, double *pose_rw, int iter,
+                      const SfSolve &sp, double *info, void *ws, hipStream_t s) {
+  int32_t *flag = (int32_t *)ws;
+  double *partials = (double *)((unsigned char *)ws + SF_WS_HDR);
+  const int nb = (int)rslo_cdiv(N, SF_BLOCK);
+  if (nb > 0 && scale == 0.0)
+    hipLaunchKernelGGL(k_surfel_accum<false>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points, stride,
+                       N, pose, max_dist, iter, (const int32_t *)flag, partials, 0.0);
+  else if (nb > 0)
+    hipLaunchKernelGGL(k_surfel_accum<true>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points, stride,
+                       N, pose, max_dist, iter, (const int32_t *)flag, partials, scale * scale);
+  hipLaunchKernelGGL(k_surfel_finish, dim3(1), dim3(64), 0, s, (const double *)partials, nb, out29, pose_rw, iter, sp, flag,
+                     info);
+}
+
+extern "C" int rslo_surfel_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                     int stride_floats, int N, const double *pose7, double max_dist, double robust_scale,
+                                     double *out29, void *ws, size_t ws_bytes, void *stream) {
+  const char *name = "surfel_normal_eq";
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(out29, "%s: out29 is null", name);
+  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
+  if (rc) return rc;
+  const SfSolve sp = {0, 0.0, 0.0, 0.0};
+  sf_launch(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, out29, nullptr, 0, sp,
+            nullptr, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
+extern "C" int rslo_surfel_register(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                    int stride_floats, int N, double *pose7, int iters, double max_dist, double damping,
+                                    int min_pairs, double tol_t, double tol_r, double robust_scale, double *info, void *ws,
+                                    size_t ws_bytes, void *stream) {
+  const char *name = "surfel_register";
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(iters >= 1 && iters <= SF_MAX_ITERS, "%s: iters must be in 1 .. 32", name);
+  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "%s: tol_t and tol_r must be >= 0 (NaN is refused)", name);
+  RSLO_CHECK_ARG(info, "%s: info is null", name);
+  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
+  if (rc) return rc;
+  const SfSolve sp = {min_pairs, damping, tol_t, tol_r};
+  for (int it = 0; it < iters; ++it)
+    sf_launch(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, nullptr, pose7, it, sp,
+              info, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}

@@ -316,11 +316,22 @@ class OdometryRunner:
       against it: n_scans is n again, so the next insert is scan n and local_map's grace keeps its meaning.
       trajectory(), relative(), the head graph, the place database, the keyframe store and the edge list are untouched.
       Evicting keyframes is out of scope.  Neither method is called by run(): without them, today's bits.
+    * Surfel map: surfels=SurfelMap(...) (rslo_amd/surfels.py, csrc/surfel.hip) receives every scan beside the voxel map
+      (or alone): run() inserts the tensor passed to submit() under the row the voxel map uses -- the refined chain
+      when there is one, else the open-loop chain.  surfel_refine=dict(iters=4, max_dist=None, robust_scale=0.2,
+      damping=1e-6, min_pairs=50, tol_t=0.0, tol_r=0.0) (these defaults; needs surfels) adds a registration stage
+      against the surfel map's planes (SurfelMap.register: no scan normal is read, so raw scans get a plane metric): it
+      creates the refined chain when refine= is absent, and corrects row n of it in place behind refine's own stage
+      (if any); then the chain state is set and both maps are filled.  Scan 0 meets an empty table (status 1) and
+      stays the identity.  surfel_refine_info() is the [n, iters, 8] info.  reset() empties the surfel map;
+      rebuild_map() on the runner's own maps and adopt_loop_closure() also reset it and refill it from the keyframe
+      store under the same poses (SurfelMap.insert_frames).  trajectory() and relative() are untouched.  None (the
+      default): the launches of before.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
                  normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None,
-                 places=None, loop=None, pose_graph=None, keyframes=None, verify=None):
+                 places=None, loop=None, pose_graph=None, keyframes=None, verify=None, surfels=None, surfel_refine=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -328,6 +339,14 @@ class OdometryRunner:
             from rslo_amd import mapping
             try:
                 refine, info_rows = mapping.check_refine(refine, voxel_map)
+            except ValueError as e:
+                raise capi.RsloHipError("OdometryRunner: %s" % e)
+        if surfel_refine is not None:
+            from rslo_amd import surfels as surfels_mod
+            if surfels is None:
+                raise capi.RsloHipError("OdometryRunner: surfel_refine needs surfels=SurfelMap(...) to register against")
+            try:
+                surfel_refine = surfels_mod.check_surfel_refine(surfel_refine, surfels)
             except ValueError as e:
                 raise capi.RsloHipError("OdometryRunner: %s" % e)
         if loop is not None and places is None:
@@ -409,16 +428,25 @@ class OdometryRunner:
             if voxel_map.device != dev:
                 raise capi.RsloHipError("OdometryRunner: the voxel map lives on %s, the runner on %s" % (voxel_map.device, dev))
             voxel_map.reserve(int(point_capacity))      # run() must not allocate
+        self.surfels, self.surfel_refine = surfels, surfel_refine
+        if surfels is not None:
+            if surfels.device != dev:
+                raise capi.RsloHipError("OdometryRunner: the surfel map lives on %s, the runner on %s" % (surfels.device, dev))
+            surfels.reserve(int(point_capacity))        # run() must not allocate
         self.refine = None
-        if refine is not None:
-            if voxel_map is None:
-                raise capi.RsloHipError("OdometryRunner: refine needs a voxel_map to register against")
-            self.refine = refine
+        if refine is not None and voxel_map is None:
+            raise capi.RsloHipError("OdometryRunner: refine needs a voxel_map to register against")
+        self._refined = refine is not None or surfel_refine is not None      # the second chain exists
+        if self._refined:
             self._state2 = torch.zeros((7,), dtype=torch.float64, device=dev)
             self._count2 = torch.zeros((1,), dtype=torch.int32, device=dev)
             self._rel2 = torch.zeros((self.capacity, 7), dtype=torch.float32, device=dev)
             self._traj2 = torch.zeros((self.capacity, 7), dtype=torch.float64, device=dev)
+        if refine is not None:
+            self.refine = refine
             self._info2 = torch.zeros((self.capacity, info_rows, 8), dtype=torch.float64, device=dev)
+        if surfel_refine is not None:
+            self._info3 = torch.zeros((self.capacity, surfel_refine["iters"], 8), dtype=torch.float64, device=dev)
         self.local_map = None
         if local_map is not None:
             if voxel_map is None:
@@ -476,7 +504,8 @@ class OdometryRunner:
             if cloud.shape[0] > self.encoder.point_capacity:
                 raise capi.RsloHipError("OdometryRunner.submit: the scan exceeds point_capacity = %d"
                                         % self.encoder.point_capacity)
-        keep = self.voxel_map is not None or self.places is not None or self.keyframes is not None
+        keep = (self.voxel_map is not None or self.places is not None or self.keyframes is not None
+                or self.surfels is not None)
         if keep and not (torch.is_tensor(cloud) and cloud.is_cuda and cloud.dtype == torch.float32 and cloud.dim() == 2):
             raise capi.RsloHipError("OdometryRunner.submit: a runner with a voxel map%s takes one fp32 CUDA [P, F] tensor"
                                     % ("" if self.places is None else " or a place database"))
@@ -512,7 +541,9 @@ class OdometryRunner:
         self._n = 0
         if self.voxel_map is not None:
             self.voxel_map.reset()
-        if self.refine is not None:
+        if self.surfels is not None:
+            self.surfels.reset()
+        if self._refined:
             self._count2.zero_()
         if self.places is not None:
             self.places.reset()
@@ -531,7 +562,7 @@ class OdometryRunner:
             raise capi.RsloHipError("OdometryRunner.close_loops: the runner was built without pose_graph")
         if "poses" in options:
             raise capi.RsloHipError("OdometryRunner.close_loops: the start is the runner's own trajectory")
-        traj0 = self.refined_trajectory() if self.refine is not None else self.trajectory()
+        traj0 = self.refined_trajectory() if self._refined else self.trajectory()
         self._optimized, self._pg_info = self.pose_graph.optimize(traj0, loops_ij, loops_Z, loops_w, **options)
         return self._optimized, self._pg_info
 
@@ -545,24 +576,31 @@ class OdometryRunner:
     def rebuild_map(self, voxel_map=None, poses=None):
         """Reset voxel_map (a VoxelMap or MapPyramid; default: the runner's own) and insert every stored keyframe under
         its own row of poses (float64 CUDA [m, 7]; default: optimized_trajectory()): the map the corrected trajectory
-        implies, at the density of the keyframes.  On the caller's stream, no host read.  Returns the map."""
+        implies, at the density of the keyframes.  On the caller's stream, no host read.  Returns the map.  With the
+        runner's own map as the target (voxel_map=None) an attached SurfelMap is reset and refilled the same way; a
+        runner with surfels= and no voxel_map rebuilds the surfel map alone (and returns None)."""
         if self.keyframes is None:
             raise capi.RsloHipError("OdometryRunner.rebuild_map: the runner was built without keyframes")
         vmap = self.voxel_map if voxel_map is None else voxel_map
-        if vmap is None:
+        own_surfels = self.surfels if voxel_map is None else None      # the runner's own maps are rebuilt together
+        if vmap is None and own_surfels is None:
             raise capi.RsloHipError("OdometryRunner.rebuild_map: no voxel_map given and the runner was built without one")
         if poses is None:
             if self._optimized is None:
                 raise capi.RsloHipError("OdometryRunner.rebuild_map: no poses given and close_loops() has not run")
             poses = self._optimized
-        vmap.reset()
-        vmap.insert_frames(self.keyframes, poses)
+        if vmap is not None:
+            vmap.reset()
+            vmap.insert_frames(self.keyframes, poses)
+        if own_surfels is not None:
+            own_surfels.reset()
+            own_surfels.insert_frames(self.keyframes, poses)
         return vmap
 
     def adopt_loop_closure(self):
         """Take the last close_loops() into the refined chain (class docstring): its rows, its state, and the runner's
         own map rebuilt from the keyframes.  The open-loop chain and everything else the runner streams stay."""
-        if self.refine is None or self.keyframes is None:
+        if not self._refined or self.keyframes is None:
             raise capi.RsloHipError("OdometryRunner.adopt_loop_closure: needs a runner built with refine= and keyframes=")
         if self._optimized is None:
             raise capi.RsloHipError("OdometryRunner.adopt_loop_closure: close_loops() has not run")
@@ -609,9 +647,15 @@ class OdometryRunner:
 
     def refined_trajectory(self):
         """[n, 7] fp64 device rows of the refined chain (refine=...): row i = register(refined[i-1] o rel[i])."""
-        if self.refine is None:
+        if not self._refined:
             raise capi.RsloHipError("OdometryRunner.refined_trajectory: the runner was built without refine")
         return self._traj2[:min(self._n, self.capacity)]
+
+    def surfel_refine_info(self):
+        """[n, iters, 8] fp64 device rows (surfel_refine=...): SurfelMap.register's info of every scan."""
+        if self.surfel_refine is None:
+            raise capi.RsloHipError("OdometryRunner.surfel_refine_info: the runner was built without surfel_refine")
+        return self._info3[:min(self._n, self.capacity)]
 
     def refine_info(self):
         """[n, iters, 8] fp64 device rows: VoxelMap.register's info of every scan."""
@@ -677,18 +721,22 @@ class OdometryRunner:
             self._head_and_chain()
             self.stats["head_eager"] += 1
         n = self._n
-        if self.refine is not None:         # the second chain: predict from the refined pose, register, compose onto the result
+        chain = self._traj2 if self._refined else self._traj      # the chain whose row n places this scan in the maps
+        if self._refined:                   # the second chain: predict from the refined pose, register, compose onto the result
             rel = self._rel[n]
             capi.pose_chain(rel[:3], rel[3:], self._state2, self._count2, self._rel2, self._traj2)
-            self.voxel_map.register(handle.source, self._traj2[n], info=self._info2[n], **self.refine)
+            if self.refine is not None:
+                self.voxel_map.register(handle.source, self._traj2[n], info=self._info2[n], **self.refine)
+            if self.surfel_refine is not None:      # behind refine's own stage, on the same row
+                self.surfels.register(handle.source, self._traj2[n], info=self._info3[n], **self.surfel_refine)
             self._state2.copy_(self._traj2[n])
-            self.voxel_map.insert(handle.source, self._traj2[n])
-        elif self.voxel_map is not None:    # behind the pose chain that wrote row n, on this stream
-            self.voxel_map.insert(handle.source, self._traj[n])
+        if self.voxel_map is not None:      # behind the pose chain (and the registration) that wrote row n, on this stream
+            self.voxel_map.insert(handle.source, chain[n])
+        if self.surfels is not None:
+            self.surfels.insert(handle.source, chain[n])
         if self.local_map is not None and (n + 1) % self.local_map["every"] == 0:
             lm = self.local_map
-            self.voxel_map.prune((self._traj if self.refine is None else self._traj2)[n], lm["radius"], lm["min_hits"],
-                                 lm["grace"])
+            self.voxel_map.prune(chain[n], lm["radius"], lm["min_hits"], lm["grace"])
         if self.places is not None:         # describe -> query -> add: the scan is searched for before it is stored
             self.places.describe(handle.source)
             self.places.query(out=self._loop[n], **self.loop)

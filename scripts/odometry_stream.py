@@ -13,6 +13,7 @@
     python scripts/odometry_stream.py --pose-graph --scans 200 --warmup 20 [--out profiles/odometry_stream_posegraph.json]
     python scripts/odometry_stream.py --verify --scans 200 --warmup 20 [--out profiles/odometry_stream_verify.json]
     python scripts/odometry_stream.py --rebuild-map --scans 200 --warmup 20 [--out profiles/odometry_stream_rebuild.json]
+    python scripts/odometry_stream.py --surfels --scans 200 --warmup 20 [--surfel-voxel 0.4] [--surfel-iters 4] [--out profiles/odometry_stream_surfels.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -199,6 +200,10 @@ def main():
     ap.add_argument("--rebuild-map", action="store_true",
                     help="rebuild the map from the keyframe store after loop closure: one call against one insert per frame "
                          "(implies --verify)")
+    ap.add_argument("--surfels", action="store_true",
+                    help="also run the runner with a surfel map and its registration stage, and the registration-alone rows")
+    ap.add_argument("--surfel-voxel", type=float, default=0.4)
+    ap.add_argument("--surfel-iters", type=int, default=4, help="Gauss-Newton iterations of the surfel stage")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -295,6 +300,8 @@ def main():
         res.update(verify_report(args, net, scans, res))
     if args.rebuild_map:
         res.update(rebuild_report(args, net, scans, res))
+    if args.surfels:
+        res.update(surfel_report(args, net, scans, res))
     line = json.dumps(res)
     print(line)
     if args.out:
@@ -856,7 +863,7 @@ def register_alone(args, scans, target, call, name, pairs_row=0):
     pose = torch.zeros((7,), dtype=torch.float64, device=dev)
     refined = true[0].copy()
     target.insert(scans[0], refined)
-    before, after, pairs, status, ms = [], [], [], [], []
+    before, after, pairs, status, ms, left = [], [], [], [], [], []
     for i in range(1, W + N):
         axis = rng.normal(size=3)
         ang = np.deg2rad(0.1) * rng.uniform(0.5, 1.5)
@@ -872,6 +879,7 @@ def register_alone(args, scans, target, call, name, pairs_row=0):
         target.insert(scans[i], pose)
         before.append(_pose_error(pred, true[i]))
         after.append(_pose_error(refined, true[i]))
+        left.append(refined[:3] - true[i][:3])      # world frame: x runs along the synthetic street, y across it, z up
         info = info.cpu().numpy()
         pairs.append(float(info[pairs_row, 1]))
         status.append(info[:, 0].tolist())
@@ -886,7 +894,74 @@ def register_alone(args, scans, target, call, name, pairs_row=0):
         out["%s_%s_trans_m_max" % (name, which)] = round(float(e[:, 0].max()), 5)
         out["%s_%s_rot_deg_mean" % (name, which)] = round(float(e[:, 1].mean()), 5)
         out["%s_%s_rot_deg_max" % (name, which)] = round(float(e[:, 1].max()), 5)
+    left = np.array(left)
+    out[name + "_after_err_xyz_mean_abs_m"] = [round(float(v), 5) for v in np.abs(left).mean(axis=0)]
+    out[name + "_after_err_xyz_last_m"] = [round(float(v), 5) for v in left[-1]]
     out[name + "_map_stats"] = target.stats()
+    return out
+
+
+class _Targets:
+    """several registration targets that receive the same scans (register_alone's `target`)"""
+
+    def __init__(self, *targets):
+        self.targets = targets
+
+    def reset(self):
+        for t in self.targets:
+            t.reset()
+
+    def insert(self, points, pose):
+        for t in self.targets:
+            t.insert(points, pose)
+
+    def stats(self):
+        return [t.stats() for t in self.targets]
+
+
+def surfel_report(args, net, scans, res):
+    """--surfels: the runner with a surfel map and its registration stage; surfel inserts beside voxel-map inserts under
+    the drive's own poses; and the registration-alone pass with the parent's best row (pyramid, factor 0.5), the
+    surfels alone, and the pyramid followed by the surfel stage, in this one process."""
+    import torch
+    from rslo_amd import inference, mapping, surfels, synthetic
+    dev = scans[0].device
+    W, N, K = args.warmup, args.scans, args.surfel_iters
+    opts = dict(surfels.SURFEL_REFINE_DEFAULTS, iters=K)
+    out = {"surfel_voxel": args.surfel_voxel, "surfel_refine": opts}
+    smap = surfels.SurfelMap(args.surfel_voxel, 1 << 20, dev)
+    plain = inference.OdometryRunner(net)
+    out["surfel_plain_ms_per_scan"], _ = [round(v, 3) for v in timed_feed(plain, scans, W, N)]
+    plain.close()
+    runner = inference.OdometryRunner(net, surfels=smap, surfel_refine=opts)
+    out["surfel_ms_per_scan"], out["surfel_host_ms_per_scan"] = [round(v, 3) for v in timed_feed(runner, scans, W, N)]
+    info = runner.surfel_refine_info().cpu().numpy()
+    out["surfel_runner_status_counts"] = [int((info[:, :, 0] == k).sum()) for k in range(4)]
+    out["surfel_runner_map_stats"] = smap.stats()
+    runner.close()
+    # the inserts alone under the drive's own poses, each beside the voxel map's insert at the same cell edge
+    true = [torch.from_numpy(synthetic.sequence_pose(i, args.seed)).to(dev) for i in range(W + N)]
+    for voxel in sorted({args.surfel_voxel, 0.8}):
+        targets = (("surfel_insert_alone_v%g_ms_per_scan" % voxel, surfels.SurfelMap(voxel, 1 << 20, dev)),
+                   ("map_insert_alone_v%g_ms_per_scan" % voxel, mapping.VoxelMap(voxel, 1 << 20, dev)))
+        for name, target in targets:
+            target.reserve(max(s.shape[0] for s in scans))
+            for i in range(W):
+                target.insert(scans[i], true[i])
+            out[name] = round(device_ms(lambda i: target.insert(scans[W + i], true[W + i]), N), 4)
+            out[name.replace("_ms_per_scan", "_stats")] = target.stats()
+    # the registration-alone pass: the same seeded disturbance for every row
+    smap.reserve(max(s.shape[0] for s in scans))
+    pyr = mapping.MapPyramid((0.8, 0.4, 0.2), args.map_capacity, dev)
+    pyr.reserve(max(s.shape[0] for s in scans))
+    sch = pyr.default_schedule(4, 0.5)
+    kw = {k: v for k, v in opts.items() if k != "iters"}
+    out.update(register_alone(args, scans, pyr, lambda s, p: pyr.register(s, p, sch)[1], "pyramid_alone_f0.5", pairs_row=-1))
+    out.update(register_alone(args, scans, smap, lambda s, p: smap.register(s, p, iters=K, **kw)[1], "surfel_alone"))
+    out["surfel_alone_ms_per_iteration"] = round(out["surfel_alone_ms_per_call"] / K, 4)
+    out.update(register_alone(args, scans, _Targets(pyr, smap),
+                              lambda s, p: torch.cat([pyr.register(s, p, sch)[1], smap.register(s, p, iters=K, **kw)[1]]),
+                              "pyramid_then_surfel", pairs_row=-1))
     return out
 
 
