@@ -363,7 +363,8 @@ __global__ __launch_bounds__(256) void k_resid_gather(const unsigned long long *
 
 // one wave per long run: lane l adds elements l, l + 64, ... in order, then the 64 lane sums are added in a fixed tree.
 // (Four waves per run measured 34 -> ~15 us on the bench's random-init state, where a few partners collect thousands of
-// sources -- not kept: another summation order is another weight trajectory, and the parity tests pin this one.)
+// sources -- not kept: another summation order is another weight trajectory, and tests/test_gpu_closs_kernels.py pins this
+// one bit for bit.)
 __global__ __launch_bounds__(64) void k_resid_gather_long(const unsigned long long *__restrict__ skeys, int64_t n,
                                                           const float *__restrict__ contrib, float *__restrict__ gtgt,
                                                           float *__restrict__ gcov2, const int *__restrict__ n_long,
@@ -540,6 +541,16 @@ __device__ void svd3_jacobi(const double H[9], double U[9], double S[3], double 
       U[0 * 3 + 2] = U[1 * 3 + 0] * U[2 * 3 + 1] - U[2 * 3 + 0] * U[1 * 3 + 1];
       U[1 * 3 + 2] = U[2 * 3 + 0] * U[0 * 3 + 1] - U[0 * 3 + 0] * U[2 * 3 + 1];
       U[2 * 3 + 2] = U[0 * 3 + 0] * U[1 * 3 + 1] - U[1 * 3 + 0] * U[0 * 3 + 1];
+    } else if (k == 1) {   // rank one (two correspondences): the axis column 0 leans on least, made orthogonal to column 0
+      int ax = 0;          // (the unit vector e_1 itself is orthogonal to column 0 only when H = 0, where this still gives it)
+      for (int r = 1; r < 3; ++r)
+        if (fabs(U[r * 3 + 0]) < fabs(U[ax * 3 + 0])) ax = r;
+      double v[3], nn = 0.0;
+      for (int r = 0; r < 3; ++r) {
+        v[r] = (r == ax ? 1.0 : 0.0) - U[ax * 3 + 0] * U[r * 3 + 0];
+        nn += v[r] * v[r];
+      }
+      for (int r = 0; r < 3; ++r) U[r * 3 + 1] = v[r] / sqrt(nn);      // nn >= 2 / 3
     } else {
       for (int r = 0; r < 3; ++r) U[r * 3 + k] = (r == k) ? 1.0 : 0.0;
     }
