@@ -1380,10 +1380,11 @@ RSLO_API int rslo_loop_emit(const double *out /*[top_k,16]*/, int top_k, const v
  *   header (256 bytes) | keys u64 [cap] | moments i64 [cap, 10] | rows f64 [cap, 8] | dirty i32 [cap].
  * Header int64 words: [0] magic, [1] capacity, [2] voxel_size, [3] min_range, [4] max_range (doubles), [5] min_points
  * (>= 3), [6] planar_ratio, [7] line_ratio (doubles, >= 0, finite), [8..14] n_scans, n_cells, n_points, dropped_invalid,
- * dropped_range, dropped_full, n_planar.  The table is the world voxel map's: capacity a power of two in 1024 .. 2^31,
+ * dropped_range, dropped_full, n_planar, [RSLO_SURFEL_HDR_PRUNE + 0..2] n_prunes, n_evicted, n_lost ("Rolling local surfel
+ * map" below).  The table is the world voxel map's: capacity a power of two in 1024 .. 2^31,
  * linear probing from map_mix(key), at most RSLO_MAP_MAX_PROBE slots examined; a point that finds neither its key nor an
  * empty slot is dropped and counted (dropped_full): a full table never hangs.  The ten moments of a slot are contiguous.
- * The table only fills; rslo_surfel_reset empties it.
+ * Between two prunes (below) the table only fills; rslo_surfel_reset empties it.
  *
  * Insert of a scan under pose7.
  *   1. status, world position w and key of a point are those of "World voxel map" (the same function): validity, range
@@ -1427,13 +1428,50 @@ RSLO_API int rslo_loop_emit(const double *out /*[top_k,16]*/, int top_k, const v
  * Register (rslo_surfel_register): the rules of rslo_map_register_w with the normal equations above: the step, damping,
  * min_pairs, tol_t / tol_r, statuses 0..3, info rows [iters, 8], 2 launches per iteration and 1 for N == 0.
  *
+ * Rolling local surfel map (rslo_surfel_prune): the one call that removes surfel cells.  A cell carries no creation
+ * scan and the slot layout does not change (156 bytes per slot), so the rule uses only the key, the count
+ * N = moments[0], the header's voxel and the arguments.  For a stored cell, cell_a is unpacked from the key (3 x 21
+ * bits, x most significant, minus 2^20); then, in this order,
+ *   cc_a = (double(cell_a) + 0.5) * voxel      the cell's CENTRE, not the row's mean: a cell with flag 0 (a row of
+ *                                              zeros) is judged by where it is
+ *   dx = cc_x - c[0], dy, dz likewise;  d2 = dx*dx + dy*dy + dz*dz, summed left to right.
+ * The cell is KEPT iff both hold:
+ *   1. near:  center3 is NULL, or d2 < radius*radius.  A comparison that is false evicts (a NaN centre coordinate,
+ *      radius == 0); radius = +inf keeps every cell.
+ *   2. not sparse:  N >= min_count, or (center3 is given and d2 < inner_radius*inner_radius): the sensor's own
+ *      neighbourhood is still being filled and is exempt; cells the sensor has left behind that never collected
+ *      min_count points -- stray returns, the trails of moving objects -- go.  With center3 == NULL there is no
+ *      exemption, and radius and inner_radius are ignored.  min_count = 1 makes nothing sparse.
+ * Every other cell is EVICTED: its key, moments and row are gone, rslo_surfel_nearest / _normal_eq / _register /
+ * _export do not see it, and a later insert into it starts its moments from zero.  Kept cells keep key, moments and
+ * row to the bit (rows are copied, not derived again); all dirty words are 0 afterwards, as between any two calls.
+ * n_cells becomes kept - lost, n_planar the number of surviving rows with flag 2.0; n_scans, n_points and the dropped_*
+ * counters are cumulative and do not change.  Header words [RSLO_SURFEL_HDR_PRUNE + 0..2] = n_prunes (calls),
+ * n_evicted (cumulative), n_lost (cumulative, below); rslo_surfel_reset zeroes them.
+ * The table is REBUILT in place, as by rslo_map_prune: the kept records (152 bytes: key, moments, row) are staged in
+ * the caller-owned workspace of rslo_surfel_prune_ws_bytes(capacity) bytes (control block | keys | moments | rows),
+ * the sections are returned to the state rslo_surfel_reset leaves, and the records are inserted again under the same
+ * bounded probe.  A record that finds no empty slot among RSLO_MAP_MAX_PROBE is dropped whole and counted in n_lost:
+ * impossible while the survivors' longest run of occupied slots, wrap-around included, is below RSLO_MAP_MAX_PROBE;
+ * beyond that the surviving set is unspecified.  A call that evicts nothing leaves every byte of the allocation as it
+ * is, except n_prunes.
+ *   rslo_surfel_prune_ws_bytes  host only; 0 for a capacity rslo_surfel_bytes refuses.
+ *   rslo_surfel_prune  center3: 3 DEVICE doubles (a trajectory row will do) or NULL.  A null map, map_bytes below
+ *                    rslo_surfel_bytes(1024), with a centre a radius that is negative or NaN or an inner_radius that
+ *                    is negative, NaN or greater than radius, min_count < 1, a null or misaligned (16 bytes)
+ *                    workspace: RSLO_EINVAL; ws_bytes below rslo_surfel_prune_ws_bytes of the largest capacity
+ *                    map_bytes can hold: RSLO_EWS.  Five launches whatever the data (begin, scan, clear, re-insert,
+ *                    done); the scan pass reads keys and counts only and takes the staging cursor once per wave; no
+ *                    floating-point atomic.
+ *
  * All of them: everything on `stream`, no host read, nothing allocated, a launch count that does not depend on the data:
  * capturable.  On an allocation that was never reset the kernels do nothing (nearest writes "none").  Errors are found
  * before the first launch and write nothing: RSLO_EINVAL for a null pointer, a capacity, size or parameter out of range
  * (NaN included), max_dist outside (0, voxel_size], a bad robust_scale, iters outside 1 .. 32; RSLO_EWS for a workspace
- * below rslo_surfel_insert_ws_bytes(N) / rslo_surfel_register_ws_bytes(N).  The three *_bytes functions are host only
+ * below rslo_surfel_insert_ws_bytes(N) / rslo_surfel_register_ws_bytes(N).  The four *_bytes functions are host only
  * and return 0 for arguments out of range.
  * ------------------------------------------------------------------------------------ */
+#define RSLO_SURFEL_HDR_PRUNE 15
 RSLO_API size_t rslo_surfel_bytes(int64_t capacity);
 RSLO_API int rslo_surfel_reset(void *map, size_t map_bytes, int64_t capacity, double voxel_size, double min_range,
                                double max_range, int min_points, double planar_ratio, double line_ratio, void *stream);
@@ -1449,6 +1487,9 @@ RSLO_API int rslo_surfel_export(const void *map, size_t map_bytes, int min_flag,
 RSLO_API int rslo_surfel_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
                                  int stride_floats, int N, const double *pose7, double max_dist, int64_t *keys_out,
                                  double *d2_out, double *rows_out /*[N,8] or NULL*/, void *stream);
+RSLO_API size_t rslo_surfel_prune_ws_bytes(int64_t capacity);
+RSLO_API int rslo_surfel_prune(void *map, size_t map_bytes, const double *center3 /*device, or NULL*/, double radius,
+                               double inner_radius, int min_count, void *ws, size_t ws_bytes, void *stream);
 RSLO_API size_t rslo_surfel_register_ws_bytes(int N);
 RSLO_API int rslo_surfel_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
                                    int stride_floats, int N, const double *pose7, double max_dist, double robust_scale,

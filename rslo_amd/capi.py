@@ -242,6 +242,8 @@ SIGNATURES = {
     "rslo_surfel_insert_frames": (C.c_int, [_vp, _sz, _vp, _sz, _i64, _i, _vp, _i, _vp]),
     "rslo_surfel_export": (C.c_int, [_vp, _sz, _i, _vp, C.c_double, _vp, _vp, _vp, _i64, _vp, _vp]),
     "rslo_surfel_nearest": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, _vp, _vp, _vp, _vp]),
+    "rslo_surfel_prune_ws_bytes": (_sz, [_i64]),
+    "rslo_surfel_prune": (C.c_int, [_vp, _sz, _vp, C.c_double, C.c_double, _i, _vp, _sz, _vp]),
     "rslo_surfel_register_ws_bytes": (_sz, [_i]),
     "rslo_surfel_normal_eq": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
     "rslo_surfel_register": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, _i, C.c_double, C.c_double, _i, C.c_double,
@@ -1482,6 +1484,34 @@ def surfel_export(buf, min_flag=1, center=None, radius=0.0, keys=None, moments=N
                                   _ptr(rows, torch.float64, "rows") if R else None, R,
                                   _ptr(counts, torch.int64, "counts"), _stream()), "rslo_surfel_export")
     return counts
+
+
+SURFEL_HDR_PRUNE = 15     # first int64 word of n_prunes, n_evicted, n_lost in a surfel map's header
+SURFEL_PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
+
+
+def surfel_prune_ws(capacity, device):
+    """a workspace for surfel_prune on a map of `capacity` slots: rslo_surfel_prune_ws_bytes(capacity) bytes"""
+    nbytes = int(lib().rslo_surfel_prune_ws_bytes(int(capacity)))
+    if nbytes == 0:
+        raise RsloHipError("surfel_prune_ws: capacity must be a power of two >= 1024, got %r" % (capacity,))
+    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+
+
+def surfel_prune(buf, ws, center=None, radius=0.0, inner_radius=0.0, min_count=1):
+    """rslo_surfel_prune on the current stream: evict the cells whose centre is not within radius of center (None: no
+    such test; else float64 CUDA, contiguous, >= 3 elements, read in place: a [7] trajectory row will do) or that hold
+    fewer than min_count points and lie at least inner_radius from it, by rebuilding the table through ws
+    (surfel_prune_ws).  Five launches, no host read."""
+    ptr, nbytes = _map_buf(buf)
+    if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64
+                                   and center.numel() >= 3 and center.is_contiguous()):
+        raise RsloHipError("surfel_prune: center must be >= 3 contiguous float64 values on the GPU")
+    if not (torch.is_tensor(ws) and ws.is_cuda and ws.is_contiguous()):
+        raise RsloHipError("surfel_prune: ws must be a contiguous CUDA tensor (surfel_prune_ws)")
+    _chk(lib().rslo_surfel_prune(ptr, nbytes, None if center is None else center.data_ptr(), float(radius),
+                                 float(inner_radius), int(min_count), ws.data_ptr(), ws.numel() * ws.element_size(),
+                                 _stream()), "rslo_surfel_prune")
 
 
 def surfel_nearest(buf, points, pose, voxel_size, max_dist=None, rows=None, keys=None, d2=None):

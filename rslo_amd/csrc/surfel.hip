@@ -38,15 +38,17 @@
 #define SF_MAX_ITERS 32
 #define SF_FRAMES_BLOCKS 2048u
 
-struct SurfHdr {                         // int64 words: 0 magic, 1 capacity, 2-4 map parameters, 5-7 plane parameters, 8-14 counters
+struct SurfHdr {      // int64 words: 0 magic, 1 capacity, 2-4 map parameters, 5-7 plane parameters, 8-14 counters, 15-17 prune
   map_u64 magic;
   long long capacity;
   double voxel, min_range, max_range;
   long long min_points;
   double planar_ratio, line_ratio;
   map_u64 n_scans, n_cells, n_points, dropped_invalid, dropped_range, dropped_full, n_planar;
+  map_u64 n_prunes, n_evicted, n_lost;
 };
 static_assert(sizeof(SurfHdr) <= SF_HDR_BYTES, "surfel header");
+static_assert(offsetof(SurfHdr, n_prunes) == 8 * RSLO_SURFEL_HDR_PRUNE, "the prune counters are header words 15 .. 17");
 
 struct SurfView {
   SurfHdr *hdr;
@@ -104,6 +106,7 @@ __global__ __launch_bounds__(256) void k_surfel_reset(void *map, long long cap, 
     h->planar_ratio = planar_ratio;
     h->line_ratio = line_ratio;
     h->n_scans = h->n_cells = h->n_points = h->dropped_invalid = h->dropped_range = h->dropped_full = h->n_planar = 0;
+    h->n_prunes = h->n_evicted = h->n_lost = 0;
   }
   for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
     keys[s] = MAP_KEY_NONE;
@@ -417,6 +420,186 @@ __global__ __launch_bounds__(256) void k_surfel_export(void *map, long long cap_
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
+// rslo_surfel_prune: evict far and sparse cells by rebuilding the table (rules: "Rolling local surfel map").  Five
+// launches whatever the data.  Workspace: control block (256 bytes, zeroed by the first, one-thread launch) | staged
+// keys u64 [cap] | moments i64 [cap, 10] | rows f64 [cap, 8] -- the table's own section layout without the dirty words.
+// Rows are copied as 64-bit words, never re-derived.
+// ---------------------------------------------------------------------------------------------------------------------
+#define SF_PRUNE_CTL_BYTES 256
+#define SF_STAGE_BYTES 152               /* key 8 + moments 80 + row 64 */
+struct SfPruneCtl {
+  map_u64 kept, evicted, lost, planar;
+};
+
+struct SfStage {
+  SfPruneCtl *ctl;
+  map_u64 *keys, *mom, *rows;
+};
+
+__device__ __forceinline__ SfStage sf_stage(void *ws, long long cap) {
+  unsigned char *p = (unsigned char *)ws + SF_PRUNE_CTL_BYTES;
+  SfStage st;
+  st.ctl = (SfPruneCtl *)ws;
+  st.keys = (map_u64 *)p;
+  st.mom = (map_u64 *)(p + (size_t)cap * 8);
+  st.rows = (map_u64 *)(p + (size_t)cap * 88);
+  return st;
+}
+
+// the control block starts every call at zero
+__global__ void k_surfel_prune_begin(void *ws) {
+  if (threadIdx.x == 0) {
+    SfPruneCtl *ctl = (SfPruneCtl *)ws;
+    ctl->kept = ctl->evicted = ctl->lost = ctl->planar = 0;
+  }
+}
+
+// pass 1: keep or evict every stored cell from its key and its count alone; the other 144 bytes are read for kept cells
+// only.  A wave walks SF_PRUNE_STEP * 64 consecutive slots at a time, SF_PRUNE_STEP per lane (the capacity is a
+// multiple of that, so every lane of the wave is in range and takes part in the ballots).  The staging cursor moves
+// ONCE per wave and step, by the number of kept slots among those 512: adds to one address are served one after the
+// other, about 13 ns each (measured: one add per 64 slots made this launch 211 us at 2^20 slots, and a second add per
+// wave for the evictions 77 us more), so the evictions are summed over the workgroup in LDS and added once.
+#define SF_PRUNE_STEP 8
+static_assert(MAP_MIN_CAP % (SF_PRUNE_STEP * 64) == 0, "a wave's step divides every capacity");
+
+__global__ __launch_bounds__(256) void k_surfel_prune_scan(void *map, long long cap_max, const double *__restrict__ center,
+                                                           double radius, double inner_radius, int min_count, void *ws) {
+  __shared__ unsigned int gone_wg;
+  if (threadIdx.x == 0) gone_wg = 0;
+  __syncthreads();
+  SurfView m;
+  if (!sf_view(map, cap_max, m)) return;      // uniform over the grid
+  const long long cap = m.hdr->capacity;
+  const SfStage st = sf_stage(ws, cap);
+  const double voxel = m.hdr->voxel;
+  double c[3] = {0.0, 0.0, 0.0};
+  if (center) c[0] = center[0], c[1] = center[1], c[2] = center[2];
+  const int lane = threadIdx.x & 63;
+  const map_u64 below = ((map_u64)1 << lane) - 1;      // the lanes in front of this one
+  unsigned int gone = 0;
+  for (long long s0 = ((long long)blockIdx.x * blockDim.x + (threadIdx.x & ~63u)) * SF_PRUNE_STEP; s0 < cap;
+       s0 += (long long)gridDim.x * blockDim.x * SF_PRUNE_STEP) {
+    map_u64 key[SF_PRUNE_STEP], kept[SF_PRUNE_STEP];
+    long long N[SF_PRUNE_STEP];
+#pragma unroll
+    for (int j = 0; j < SF_PRUNE_STEP; ++j) key[j] = m.keys[(size_t)s0 + j * 64 + lane];
+#pragma unroll
+    for (int j = 0; j < SF_PRUNE_STEP; ++j) N[j] = key[j] != MAP_KEY_NONE ? m.mom[((size_t)s0 + j * 64 + lane) * 10] : 0;
+    unsigned int total = 0;
+#pragma unroll
+    for (int j = 0; j < SF_PRUNE_STEP; ++j) {
+      const bool stored = key[j] != MAP_KEY_NONE;
+      bool keep = stored && N[j] >= (long long)min_count;
+      if (stored && center) {      // the cell's centre, not the row's mean: a comparison that is false evicts
+        const double cx = ((double)((long long)((key[j] >> 42) & 0x1fffff) - 1048576) + 0.5) * voxel;
+        const double cy = ((double)((long long)((key[j] >> 21) & 0x1fffff) - 1048576) + 0.5) * voxel;
+        const double cz = ((double)((long long)(key[j] & 0x1fffff) - 1048576) + 0.5) * voxel;
+        const double dx = cx - c[0], dy = cy - c[1], dz = cz - c[2];
+        const double d2 = dx * dx + dy * dy + dz * dz;
+        keep = (keep || d2 < inner_radius * inner_radius) && d2 < radius * radius;
+      }
+      kept[j] = __ballot(keep);
+      total += (unsigned int)__popcll(kept[j]);
+      gone += (unsigned int)__popcll(__ballot(stored && !keep));
+    }
+    if (total == 0) continue;      // uniform over the wave
+    map_u64 base = 0;
+    if (lane == 0) base = atomicAdd(&st.ctl->kept, (map_u64)total);
+    base = __shfl(base, 0, 64);
+#pragma unroll
+    for (int j = 0; j < SF_PRUNE_STEP; ++j) {
+      const map_u64 o = base + (map_u64)__popcll(kept[j] & below);
+      base += (map_u64)__popcll(kept[j]);
+      if (((kept[j] >> lane) & 1) && o < (map_u64)cap) {      // always: one record per slot at most, the cursor starts at 0
+        const size_t s = (size_t)s0 + j * 64 + lane;
+        const map_u64 *mo = (const map_u64 *)m.mom + s * 10, *row = (const map_u64 *)m.rows + s * 8;
+        st.keys[o] = key[j];
+        st.mom[o * 10] = (map_u64)N[j];
+        for (int k = 1; k < 10; ++k) st.mom[o * 10 + k] = mo[k];
+        for (int k = 0; k < 8; ++k) st.rows[o * 8 + k] = row[k];
+      }
+    }
+  }
+  if (lane == 0 && gone) atomicAdd(&gone_wg, gone);      // every wave counted the same slots on all its lanes
+  __syncthreads();
+  if (threadIdx.x == 0 && gone_wg) atomicAdd(&st.ctl->evicted, (map_u64)gone_wg);
+}
+
+// pass 2: the state k_surfel_reset leaves in the sections.  An empty slot is in that state already (a slot gets moments,
+// a row or a dirty word only behind its key), so only the stored slots are written: the pass reads the keys and
+// writes 156 bytes per stored cell.  Nothing evicted: the table stays as it is, to the byte.
+__global__ __launch_bounds__(256) void k_surfel_prune_clear(void *map, long long cap_max, const void *ws) {
+  SurfView m;
+  if (!sf_view(map, cap_max, m)) return;
+  if (((const SfPruneCtl *)ws)->evicted == 0) return;
+  const long long cap = m.hdr->capacity;
+  for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
+    if (m.keys[s] == MAP_KEY_NONE) continue;
+    m.keys[s] = MAP_KEY_NONE;
+    for (int k = 0; k < 10; ++k) m.mom[s * 10 + k] = 0;
+    for (int k = 0; k < 8; ++k) m.rows[s * 8 + k] = 0.0;
+    m.dirty[s] = 0;
+  }
+}
+
+// pass 3: the staged keys are distinct, so whoever wins the CAS on a slot owns it and writes moments and row with plain
+// stores; the kernel boundary publishes them.  The insert's bounded probe: a record without a slot is lost whole.  The
+// lost records and the planar rows are counted per thread, summed in LDS and added once per workgroup.
+__global__ __launch_bounds__(256) void k_surfel_prune_reinsert(void *map, long long cap_max, void *ws) {
+  __shared__ unsigned int tally[2];      // lost, planar
+  if (threadIdx.x < 2) tally[threadIdx.x] = 0;
+  __syncthreads();
+  SurfView m;
+  if (!sf_view(map, cap_max, m)) return;      // uniform over the grid
+  const long long cap = m.hdr->capacity;
+  const SfStage st = sf_stage(ws, cap);
+  if (st.ctl->evicted == 0) return;           // uniform over the grid
+  const long long n = (long long)st.ctl->kept < cap ? (long long)st.ctl->kept : cap;
+  const map_u64 mask = (map_u64)cap - 1;
+  unsigned int lost = 0, planar = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const map_u64 key = st.keys[i];
+    map_u64 s = map_mix(key) & mask;
+    bool found = false;
+    for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
+      // a stale read can only show "empty": in this launch a key goes from empty to set and never back
+      if (__builtin_nontemporal_load(&m.keys[s]) == MAP_KEY_NONE &&
+          atomicCAS(&m.keys[s], MAP_KEY_NONE, key) == MAP_KEY_NONE) {
+        found = true;
+        break;
+      }
+      s = (s + 1) & mask;
+    }
+    if (!found) {
+      ++lost;
+      continue;
+    }
+    map_u64 *mo = (map_u64 *)m.mom + (size_t)s * 10, *row = (map_u64 *)m.rows + (size_t)s * 8;
+    for (int k = 0; k < 10; ++k) mo[k] = st.mom[(size_t)i * 10 + k];
+    for (int k = 0; k < 8; ++k) row[k] = st.rows[(size_t)i * 8 + k];
+    planar += st.rows[(size_t)i * 8 + 7] == 0x4000000000000000ull;      // the bits of 2.0
+  }
+  if (lost) atomicAdd(&tally[0], lost);
+  if (planar) atomicAdd(&tally[1], planar);
+  __syncthreads();
+  if (threadIdx.x == 0 && tally[0]) atomicAdd(&st.ctl->lost, (map_u64)tally[0]);
+  if (threadIdx.x == 1 && tally[1]) atomicAdd(&st.ctl->planar, (map_u64)tally[1]);
+}
+
+__global__ void k_surfel_prune_done(void *map, long long cap_max, const void *ws) {
+  SurfView m;
+  if (threadIdx.x != 0 || !sf_view(map, cap_max, m)) return;
+  const SfPruneCtl *ctl = (const SfPruneCtl *)ws;
+  m.hdr->n_prunes = m.hdr->n_prunes + 1;
+  if (ctl->evicted == 0) return;
+  m.hdr->n_cells = ctl->kept - ctl->lost;
+  m.hdr->n_planar = ctl->planar;
+  m.hdr->n_evicted = m.hdr->n_evicted + ctl->evicted;
+  m.hdr->n_lost = m.hdr->n_lost + ctl->lost;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
 // Search and registration (rules: "Nearest", "Normal equations", "Register").  Read-only on the table.
 // ---------------------------------------------------------------------------------------------------------------------
 // The planar cell whose mean is nearest to w among the cells key + {-1,0,1}^3: slot, key and d2 of the winner (smallest
@@ -662,6 +845,38 @@ extern "C" int rslo_surfel_export(const void *map, size_t map_bytes, int min_fla
   hipLaunchKernelGGL(k_surfel_export, dim3(nb), dim3(256), 0, s, (void *)map, cap_max, min_flag, center3, radius,
                      (map_u64 *)keys, (long long *)moments, rows, (long long)max_rows, (map_u64 *)counts);
   RSLO_CHECK_LAUNCH("surfel_export");
+  return RSLO_OK;
+}
+
+extern "C" size_t rslo_surfel_prune_ws_bytes(int64_t capacity) {
+  if (rslo_surfel_bytes(capacity) == 0) return 0;
+  return (size_t)SF_PRUNE_CTL_BYTES + (size_t)SF_STAGE_BYTES * (size_t)capacity;
+}
+
+extern "C" int rslo_surfel_prune(void *map, size_t map_bytes, const double *center3, double radius, double inner_radius,
+                                 int min_count, void *ws, size_t ws_bytes, void *stream) {
+  hipStream_t s = (hipStream_t)stream;
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  RSLO_CHECK_ARG(map && cap_max > 0, "surfel_prune: no map (map_bytes below rslo_surfel_bytes(1024))");
+  RSLO_CHECK_ARG(!center3 || radius >= 0.0, "surfel_prune: radius must be >= 0 (NaN is refused)");
+  RSLO_CHECK_ARG(!center3 || (inner_radius >= 0.0 && inner_radius <= radius),
+                 "surfel_prune: need 0 <= inner_radius <= radius (NaN is refused)");
+  RSLO_CHECK_ARG(min_count >= 1, "surfel_prune: min_count must be >= 1");
+  RSLO_CHECK_ARG(ws && ((uintptr_t)ws & 15) == 0, "surfel_prune: the workspace is null or not 16-byte aligned");
+  if (ws_bytes < rslo_surfel_prune_ws_bytes(cap_max)) {      // the header's capacity is at most cap_max
+    rslo_set_error("surfel_prune: workspace too small");
+    return RSLO_EWS;
+  }
+  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  const long long scan_wg = cap_max / (256 * SF_PRUNE_STEP);      // a workgroup of the scan pass takes 2048 slots per step
+  const unsigned nb_scan = (unsigned)(scan_wg < 1 ? 1 : (scan_wg < 256 ? scan_wg : 256));
+  hipLaunchKernelGGL(k_surfel_prune_begin, dim3(1), dim3(64), 0, s, ws);
+  hipLaunchKernelGGL(k_surfel_prune_scan, dim3(nb_scan), dim3(256), 0, s, map, cap_max, center3, radius, inner_radius,
+                     min_count, ws);
+  hipLaunchKernelGGL(k_surfel_prune_clear, dim3(nb), dim3(256), 0, s, map, cap_max, (const void *)ws);
+  hipLaunchKernelGGL(k_surfel_prune_reinsert, dim3(nb), dim3(256), 0, s, map, cap_max, ws);
+  hipLaunchKernelGGL(k_surfel_prune_done, dim3(1), dim3(64), 0, s, map, cap_max, (const void *)ws);
+  RSLO_CHECK_LAUNCH("surfel_prune");
   return RSLO_OK;
 }
 

@@ -273,7 +273,11 @@ class OdometryRunner:
       voxel_map.prune(center=row n of the chain that fed the insert, radius=R, min_hits=, grace=) -- the refined chain
       with refine, else the open-loop one (VoxelMap.prune; include/rslo_hip.h "Rolling local map").  The decision is
       the host's own scan count: no device read.  The workspace (about one more table) is reserved here, so run()
-      allocates nothing.  trajectory() / relative() are untouched.  None (the default): the map only grows.
+      allocates nothing.  trajectory() / relative() are untouched.  None (the default): the map only grows.  One more,
+      optional key, surfels=True or surfels=dict(min_count=1, inner_radius=None) (needs surfels=; a voxel_map is then
+      no longer required), prunes the surfel map too: behind the surfel insert of the same scans run() calls
+      surfels.prune(the same row, R, inner_radius, min_count) (SurfelMap.prune; "Rolling local surfel map"), with its
+      workspace reserved here as well.  Without the key the surfel map is never pruned and the launches are today's.
     * Place recognition: places=PlaceDB(...) (rslo_amd/places.py, csrc/places.hip) with
       loop=dict(exclude_recent=50, num_candidates=10, top_k=1) (these defaults; keyword arguments of PlaceDB.query):
       behind everything above, run() describes the tensor passed to submit() (sensor frame, its first three columns),
@@ -325,8 +329,9 @@ class OdometryRunner:
       (if any); then the chain state is set and both maps are filled.  Scan 0 meets an empty table (status 1) and
       stays the identity.  surfel_refine_info() is the [n, iters, 8] info.  reset() empties the surfel map;
       rebuild_map() on the runner's own maps and adopt_loop_closure() also reset it and refill it from the keyframe
-      store under the same poses (SurfelMap.insert_frames).  trajectory() and relative() are untouched.  None (the
-      default): the launches of before.
+      store under the same poses (SurfelMap.insert_frames).  The table only fills unless local_map= carries the
+      surfels key (above): then it is pruned about the sensor every K scans and a long drive runs in a fixed table.
+      trajectory() and relative() are untouched.  None (the default): the launches of before.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
@@ -449,12 +454,23 @@ class OdometryRunner:
             self._info3 = torch.zeros((self.capacity, surfel_refine["iters"], 8), dtype=torch.float64, device=dev)
         self.local_map = None
         if local_map is not None:
-            if voxel_map is None:
-                raise capi.RsloHipError("OdometryRunner: local_map needs a voxel_map to prune")
             local_map = dict(local_map)
+            surfel_prune = local_map.pop("surfels", None)
+            if surfel_prune is None or surfel_prune is False:
+                surfel_prune = None
+                if voxel_map is None:
+                    raise capi.RsloHipError("OdometryRunner: local_map needs a voxel_map to prune")
+            else:
+                if surfels is None:
+                    raise capi.RsloHipError("OdometryRunner: local_map's surfels key needs surfels=SurfelMap(...) to prune")
+                surfel_prune = {} if surfel_prune is True else dict(surfel_prune)
+                unknown = set(surfel_prune) - {"min_count", "inner_radius"}
+                if unknown:
+                    raise capi.RsloHipError("OdometryRunner: local_map surfels takes min_count and inner_radius; got %s"
+                                            % sorted(unknown))
             unknown = set(local_map) - {"radius", "every", "min_hits", "grace"}
             if unknown:
-                raise capi.RsloHipError("OdometryRunner: local_map takes radius, every, min_hits and grace; got %s"
+                raise capi.RsloHipError("OdometryRunner: local_map takes radius, every, min_hits, grace and surfels; got %s"
                                         % sorted(unknown))
             if "radius" not in local_map:
                 raise capi.RsloHipError("OdometryRunner: local_map needs a radius")
@@ -466,8 +482,15 @@ class OdometryRunner:
                                          has_center=True)
             local_map = dict(radius=radius, every=int(every), min_hits=int(local_map.get("min_hits", 1)),
                              grace=int(local_map.get("grace", 0)))
+            if surfel_prune is not None:
+                from rslo_amd import surfels as surfels_mod
+                _, inner, min_count = surfels_mod.check_surfel_prune(None, radius, surfel_prune.get("inner_radius"),
+                                                                     surfel_prune.get("min_count", 1), has_center=True)
+                local_map["surfels"] = dict(min_count=min_count, inner_radius=inner)
+                surfels.reserve_prune()                 # run() must not allocate
             self.local_map = local_map
-            voxel_map.reserve_prune()                   # run() must not allocate
+            if voxel_map is not None:
+                voxel_map.reserve_prune()               # run() must not allocate
         self.places, self.loop = places, loop
         if places is not None:
             if places.device != dev:
@@ -736,7 +759,10 @@ class OdometryRunner:
             self.surfels.insert(handle.source, chain[n])
         if self.local_map is not None and (n + 1) % self.local_map["every"] == 0:
             lm = self.local_map
-            self.voxel_map.prune(chain[n], lm["radius"], lm["min_hits"], lm["grace"])
+            if self.voxel_map is not None:
+                self.voxel_map.prune(chain[n], lm["radius"], lm["min_hits"], lm["grace"])
+            if "surfels" in lm:                 # the same row and the same radius
+                self.surfels.prune(chain[n], lm["radius"], lm["surfels"]["inner_radius"], lm["surfels"]["min_count"])
         if self.places is not None:         # describe -> query -> add: the scan is searched for before it is stored
             self.places.describe(handle.source)
             self.places.query(out=self._loop[n], **self.loop)

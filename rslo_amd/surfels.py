@@ -25,7 +25,14 @@ bit.  The rules in one place:
     no scan normal is read and there is no point-term fallback; robust weights and the Gauss-Newton step are those of
     mapping.py (gauss_newton.py);
   * the device table probes at most 128 slots and drops what finds no slot (dropped_full); SurfelMapRef has no capacity.
-    The table only fills: reset() empties it.
+    Between two prunes the table only fills: reset() empties it;
+  * prune(center=None, radius=None, inner_radius=None, min_count=1) is the one call that removes cells (include/
+    rslo_hip.h "Rolling local surfel map").  With cc = (float64(cell) + 0.5) * voxel_size, the cell's centre, d = cc -
+    center and d2 = dx*dx + dy*dy + dz*dz, a cell is KEPT iff it is near (center is None, or d2 < radius*radius) and not
+    sparse (N = moments[0] >= min_count, or a center is given and d2 < inner_radius*inner_radius; inner_radius=None
+    means radius).  A comparison that is false evicts.  Kept cells keep key, moments and row to the bit; n_cells and
+    n_planar are recounted, the other counters stay.  prune_stats() -> {n_prunes, n_evicted, n_lost}: calls, cells
+    evicted so far, and -- device map only -- kept records that found no slot when the table was rebuilt.
 """
 import numpy as np
 
@@ -33,6 +40,7 @@ from .gauss_newton import gauss_newton_step, terms_of
 from .mapping import VoxelMapRef, _check_params, _check_register, _max_dist_of, check_scale
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full", "n_planar")
+PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
 Q = 16384.0
 _MAXC = 1 << 20
 
@@ -61,6 +69,26 @@ def check_surfel_refine(options, surfel_map):
     _max_dist_of(opts["max_dist"], surfel_map.voxel_size)
     check_scale(opts["robust_scale"])
     return opts
+
+
+def check_surfel_prune(center, radius, inner_radius, min_count, has_center=None):
+    """The argument errors of prune (ValueError), raised before anything is written, next to mapping.check_prune; ->
+    (radius, inner_radius, min_count) as two floats and an int (radius 0.0 when None, inner_radius = radius when None).
+    has_center: whether a centre will be given, for callers that validate before they have one.  Stricter than
+    rslo_surfel_prune in one point: the radii are checked without a centre too, where the C call ignores them."""
+    if has_center is None:
+        has_center = center is not None
+    if has_center and radius is None:
+        raise ValueError("prune: a center needs a radius")
+    r = 0.0 if radius is None else float(radius)
+    if not r >= 0.0:
+        raise ValueError("prune: radius must be >= 0 (NaN is refused), got %r" % (radius,))
+    ri = r if inner_radius is None else float(inner_radius)
+    if not 0.0 <= ri <= r:
+        raise ValueError("prune: need 0 <= inner_radius <= radius (NaN is refused), got %r and %r" % (inner_radius, radius))
+    if int(min_count) != min_count or min_count < 1:
+        raise ValueError("prune: min_count must be an integer >= 1, got %r" % (min_count,))
+    return r, ri, int(min_count)
 
 
 def _rot(app, aqq, apq, arp, arq, v0p, v0q, v1p, v1q, v2p, v2q):
@@ -174,6 +202,7 @@ class SurfelMapRef:
         self.moments = np.zeros((0, 10), np.int64)
         self.rows = np.zeros((0, 8), np.float64)
         self.counters = dict.fromkeys(COUNTERS, 0)
+        self.prune_counters = dict.fromkeys(PRUNE_COUNTERS, 0)
 
     def _cells(self, points, pose):
         return self._grid._cells(points, pose)
@@ -227,6 +256,27 @@ class SurfelMapRef:
         poses = np.asarray(poses, dtype=np.float64).reshape(-1, 7)
         for e in range(min(len(store_ref.rows), len(poses))):
             self.insert(store_ref.rows[e][:store_ref.counts[e]], poses[e])
+
+    def prune(self, center=None, radius=None, inner_radius=None, min_count=1):
+        """Evict the cells that are not near or that are sparse (module docstring): the sorted arrays are filtered.
+        No probe limit here, so n_lost stays 0."""
+        r, ri, mc = check_surfel_prune(center, radius, inner_radius, min_count)
+        keep = self.moments[:, 0] >= mc
+        if center is not None:
+            c = np.asarray(center, dtype=np.float64).reshape(-1)[:3]
+            cell = np.stack([(self.keys >> 42) & 0x1fffff, (self.keys >> 21) & 0x1fffff, self.keys & 0x1fffff], axis=1) - _MAXC
+            with np.errstate(all="ignore"):
+                d = (cell.astype(np.float64) + 0.5) * self.voxel_size - c[None, :]
+                d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
+                keep = (keep | (d2 < ri * ri)) & (d2 < r * r)
+        self.prune_counters["n_prunes"] += 1
+        self.prune_counters["n_evicted"] += int((~keep).sum())
+        self.keys, self.moments, self.rows = self.keys[keep], self.moments[keep], self.rows[keep]
+        self.counters["n_cells"] = len(self.keys)
+        self.counters["n_planar"] = int((self.rows[:, 7] == 2.0).sum())
+
+    def prune_stats(self):
+        return dict(self.prune_counters)
 
     def cells(self, min_flag=1):
         """(keys int64 [M], moments int64 [M, 10], rows float64 [M, 8]) of the cells with flag >= min_flag, sorted by key"""
@@ -342,9 +392,10 @@ class SurfelMapRef:
 
 class SurfelMap:
     """The device surfel map: owns the table (one allocation of rslo_surfel_bytes(capacity) bytes) and the insert and
-    registration workspaces, which grow only when a larger scan arrives.  insert / insert_frames / nearest /
-    normal_equations / register enqueue on the current stream and read nothing on the host; cells() and stats() make
-    one host read each."""
+    registration workspaces, which grow only when a larger scan arrives, and prune's workspace (about one more table),
+    allocated by the first prune() or by reserve_prune().  insert / insert_frames / nearest / normal_equations /
+    register / prune enqueue on the current stream and read nothing on the host; cells(), stats() and prune_stats()
+    make one host read each."""
 
     def __init__(self, voxel_size=0.4, capacity=1 << 20, device="cuda", min_range=0.0, max_range=float("inf"),
                  min_points=5, planar_ratio=0.1, line_ratio=0.05):
@@ -362,6 +413,7 @@ class SurfelMap:
         self._buf = torch.empty((nbytes // 8,), dtype=torch.int64, device=self.device)
         self._ws = None
         self._ws_points = -1
+        self._prune_ws = None
         self._identity = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float64, device=self.device)
         self.reserve(0)
         self.reset()
@@ -440,6 +492,31 @@ class SurfelMap:
         info = capi.surfel_register(self._buf, points, pose, self.voxel_size, iters, md, damping, min_pairs, tol_t, tol_r,
                                     scale, info=info, ws=self._reg_ws)
         return pose, info
+
+    def reserve_prune(self):
+        """Allocate prune's workspace (152 bytes per slot) now, so that a later prune() allocates nothing."""
+        from rslo_amd import capi
+        if self._prune_ws is None:
+            self._prune_ws = capi.surfel_prune_ws(self.capacity, self.device)
+
+    def prune(self, center=None, radius=None, inner_radius=None, min_count=1):
+        """Evict the cells whose centre is not within radius of center, or that hold fewer than min_count points and
+        lie at least inner_radius (None: radius) from it (module docstring).  center: None, a sequence, or a float64
+        CUDA tensor of >= 3 elements that is read in place (a [7] trajectory row).  Enqueued on the current stream; no
+        host read, and nothing allocated after reserve_prune() when center is a device tensor (or None): capturable."""
+        import torch
+        from rslo_amd import capi
+        r, ri, mc = check_surfel_prune(center, radius, inner_radius, min_count)
+        if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
+            center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(-1)[:3].copy()).to(self.device)
+        self.reserve_prune()
+        capi.surfel_prune(self._buf, self._prune_ws, center, r, ri, mc)
+
+    def prune_stats(self):
+        """{n_prunes, n_evicted, n_lost} of the map's header (one host read)."""
+        from rslo_amd import capi
+        vals = self._buf[capi.SURFEL_HDR_PRUNE:capi.SURFEL_HDR_PRUNE + len(PRUNE_COUNTERS)].tolist()
+        return dict(zip(PRUNE_COUNTERS, (int(v) for v in vals)))
 
     def cells(self, min_flag=1, center=None, radius=None):
         """(keys int64 [M], moments int64 [M, 10], rows float64 [M, 8]) of the cells with flag >= min_flag (and whose mean

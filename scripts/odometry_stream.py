@@ -14,6 +14,7 @@
     python scripts/odometry_stream.py --verify --scans 200 --warmup 20 [--out profiles/odometry_stream_verify.json]
     python scripts/odometry_stream.py --rebuild-map --scans 200 --warmup 20 [--out profiles/odometry_stream_rebuild.json]
     python scripts/odometry_stream.py --surfels --scans 200 --warmup 20 [--surfel-voxel 0.4] [--surfel-iters 4] [--out profiles/odometry_stream_surfels.json]
+    python scripts/odometry_stream.py --surfels --local-map-radius 50 --surfel-min-count 2 --surfel-inner-radius 25 --scans 180 --warmup 20
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -68,6 +69,10 @@ of the store's rows, the counts read back once outside the timed window -- the p
 a reset map, device events, one warm-up of both and then the two alternated five times: median, min and max.  The same at
 a second size: a store of 4096 entries (the streamed frames re-added) under two laps of a circle, a metre per frame.  Per
 size: frames, points, cells, dropped_full, the times, and whether the two maps are bit-equal.
+--surfels --local-map-radius R [--local-map-every K --surfel-min-count M --surfel-inner-radius r]: also the surfel map
+filled under the drive's own poses unpruned and pruned (SurfelMap.prune about the scan's pose every K scans;
+rslo_surfel_prune in csrc/surfel.hip): n_cells, n_planar, dropped_full and the prune counters side by side, and the
+device-event time of the prune call at capacity 2^20 beside VoxelMap.prune's (surfel_local_map_report).
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -204,6 +209,11 @@ def main():
                     help="also run the runner with a surfel map and its registration stage, and the registration-alone rows")
     ap.add_argument("--surfel-voxel", type=float, default=0.4)
     ap.add_argument("--surfel-iters", type=int, default=4, help="Gauss-Newton iterations of the surfel stage")
+    ap.add_argument("--surfel-min-count", type=int, default=1,
+                    help="with --surfels --local-map-radius: evict surfel cells with fewer points beyond the inner radius")
+    ap.add_argument("--surfel-inner-radius", type=float, default=None,
+                    help="with --surfels --local-map-radius: cells nearer than this are exempt from --surfel-min-count "
+                         "(default: the radius)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -302,6 +312,8 @@ def main():
         res.update(rebuild_report(args, net, scans, res))
     if args.surfels:
         res.update(surfel_report(args, net, scans, res))
+        if args.local_map_radius is not None:
+            res.update(surfel_local_map_report(args, scans))
     line = json.dumps(res)
     print(line)
     if args.out:
@@ -962,6 +974,76 @@ def surfel_report(args, net, scans, res):
     out.update(register_alone(args, scans, _Targets(pyr, smap),
                               lambda s, p: torch.cat([pyr.register(s, p, sch)[1], smap.register(s, p, iters=K, **kw)[1]]),
                               "pyramid_then_surfel", pairs_row=-1))
+    return out
+
+
+def surfel_local_map_report(args, scans, reps=11, pruned_drive=True):
+    """--surfels with --local-map-radius R: the surfel map (capacity 2^20) filled under the drive's own poses without
+    pruning, and once more pruned about the scan's pose every K scans (SurfelMap.prune, rslo_surfel_prune in
+    csrc/surfel.hip): counters, prune counters and the largest n_cells seen, side by side.  Then the prune call itself on
+    the table the unpruned drive left, about the last pose: the table is put back from a copy in front of every timed
+    call (outside the events), one warm-up, the median, min and max of `reps` calls and the survivors' count; beside it
+    VoxelMap.prune at the same capacity, cell edge, centre and radius, timed the same way in the same process; and a call
+    of each that evicts nothing.  Needs only the scans (--seed must be the drive's)."""
+    import statistics
+    import torch
+    from rslo_amd import mapping, surfels, synthetic
+    dev = scans[0].device
+    R, K, M, ri = args.local_map_radius, args.local_map_every, args.surfel_min_count, args.surfel_inner_radius
+    voxel, cap, n = args.surfel_voxel, 1 << 20, len(scans)
+    true = [torch.from_numpy(synthetic.sequence_pose(i, args.seed)).to(dev) for i in range(n)]
+    out = {"surfel_local_map": dict(radius=R, every=K, min_count=M, inner_radius=R if ri is None else ri),
+           "surfel_local_map_scans": n, "surfel_local_map_capacity": cap}
+
+    def drive(target, prune):
+        target.reserve(max(s.shape[0] for s in scans))
+        peak = 0
+        for i in range(n):
+            target.insert(scans[i], true[i])
+            if prune and (i + 1) % K == 0:
+                peak = max(peak, target.stats()["n_cells"])
+                prune(target, true[i])
+        return max(peak, target.stats()["n_cells"])
+
+    def timed(target, prune):
+        """ms of prune(target, last pose) on the table as it is now: (median, min, max, n_cells afterwards)"""
+        table, ms = target._buf.clone(), []
+        for rep in range(reps + 1):
+            target._buf.copy_(table)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            prune(target, true[-1])
+            e1.record()
+            e1.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        ms = ms[1:]
+        return [round(statistics.median(ms), 4), round(min(ms), 4), round(max(ms), 4), target.stats()["n_cells"]]
+
+    def surfel_prune(t, c):
+        t.prune(c, R, ri, M)
+
+    def map_prune(t, c):
+        t.prune(c, R)
+    smap = surfels.SurfelMap(voxel, cap, dev)
+    smap.reserve_prune()
+    out["surfel_unpruned_peak_cells"] = drive(smap, None)
+    out["surfel_unpruned_stats"] = smap.stats()
+    if pruned_drive:
+        local = surfels.SurfelMap(voxel, cap, dev)
+        local.reserve_prune()
+        out["surfel_local_map_peak_cells"] = drive(local, surfel_prune)
+        out["surfel_local_map_stats"], out["surfel_local_map_prune_stats"] = local.stats(), local.prune_stats()
+        del local
+    vmap = mapping.VoxelMap(voxel, cap, dev)
+    vmap.reserve_prune()
+    drive(vmap, None)
+    out["map_unpruned_stats"] = vmap.stats()
+    for name, target, prune in (("surfel_prune", smap, surfel_prune), ("map_prune", vmap, map_prune)):
+        out[name + "_cells_before"] = target.stats()["n_cells"]
+        out[name + "_no_evict_ms_median_min_max_survivors"] = timed(target, lambda t, c: t.prune(c, float("inf")))
+        out[name + "_ms_median_min_max_survivors"] = timed(target, prune)
+    out["surfel_prune_staged_bytes_per_survivor"] = 2 * 152
     return out
 
 
