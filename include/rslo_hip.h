@@ -1499,6 +1499,66 @@ RSLO_API int rslo_surfel_register(const void *map, size_t map_bytes, double voxe
                                   int min_pairs, double tol_t, double tol_r, double robust_scale, double *info /*[iters,8]*/,
                                   void *ws, size_t ws_bytes, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Scan de-skewing (csrc/deskew.hip; float64 restatement: rslo_amd/deskew.py)
+ *
+ * A spinning LiDAR does not take a rigid snapshot: while the sweep lasts the sensor moves by M = (t, q).  Under the
+ * constant-velocity model of LOAM / LIO-SAM the sensor pose at sweep fraction s in [0, 1] is (s t, R^s), and
+ * rslo_deskew moves every point from the sensor frame at its own time to the sensor frame at `stamp`: with stamp = 1 a
+ * point seen at s = 0 is moved by M^-1, with stamp = 0 a point seen at s = 1 by M.
+ *
+ * points fp32 [N, stride_floats], of which n_cols columns are a row: x, y, z, then anything; normal_col (-1: none) is
+ * the first of three columns that hold a direction and are rotated with the point.  out fp32 [N, out_stride_floats]
+ * receives the n_cols columns; its padding floats are not written.  out == points with equal strides is allowed (a
+ * thread reads what it needs of its row before it writes it); any other overlap is the caller's error.
+ *
+ * The motion is rel7 (DEVICE fp32 [7]: t, q wxyz, widened to double), or se3_between(pose_a, pose_b) = A^-1 o B of two
+ * DEVICE double [7] poses, or -- all three NULL -- none.  All pointers are read when the kernel runs: a captured call
+ * follows a motion that changes between replays.
+ *
+ * All arithmetic is IEEE double without contraction, in the order written; the result is rounded to float once, at
+ * the store.  rotate is se3_rotate of csrc/se3.h (form A).
+ *
+ * Motion block (once per call): t = M[0..2], q = M[3..6]; n2 = ((q0*q0 + q1*q1) + q2*q2) + q3*q3.  !(n2 > 0 && n2 < inf)
+ * or a component of t not finite: status 2.  Otherwise q /= sqrt(n2), negated when q0 < 0; su = sqrt((q1*q1 + q2*q2) +
+ * q3*q3); theta = 2 * atan2(su, q0) -- the only libm transcendental; a = u / su, or 0 when su == 0.  theta > max_angle:
+ * status 3.  Otherwise t' = rotate(qs, t) with qs = (cosP(h), sinP(h) * a), h = ((-stamp) * theta) * 0.5.
+ *   motion_out double [8] (or NULL) = {a.x, a.y, a.z, theta, t'.x, t'.y, t'.z, status}
+ *   status 0 applied, 1 no motion given, 2 invalid motion, 3 angle above max_angle; for a status other than 0 the
+ *   first seven words are 0 and every row is copied unchanged, all n_cols floats bit for bit.
+ *
+ * Per point: s = times[i] (fp32 [N], widened), or the sweep fraction of its azimuth (below).  The row is copied
+ * unchanged when x, y, z or s is not finite or, in azimuth mode, when x == 0 && y == 0.  Otherwise s is clamped to
+ * [0, 1] and
+ *   alpha = s - stamp;  h = (alpha * theta) * 0.5;  qp = (cosP(h), sinP(h) * a)
+ *   o = rotate(qp, p) + alpha * t'        (the rotation, then the addition)
+ *   the three floats at normal_col become rotate(qp, n); every other column is copied bit for bit.
+ *
+ * sinP(x) = x * (S1 + z * (S3 + ... + z * S15)), cosP(x) = C0 + z * (C2 + ... + z * C16), z = x*x: the Taylor
+ * polynomials in Horner form with the doubles nearest +-1/k!, within 2^-53 of sin and cos for |x| <= pi/4 -- hence
+ * max_angle <= pi/2, as |alpha| <= 1.  A fixed polynomial makes the per-point result reproducible to the bit on the host.
+ *
+ * Sweep fraction from the azimuth: ax = |x|, ay = |y|, r = min(ax, ay) / max(ax, ay); phi = atanP(r); ay > ax:
+ * phi = HALF_PI - phi; x < 0: phi = PI - phi; y < 0: phi = -phi; f = phi / TWO_PI - az_start_turn (a division: the
+ * axis directions give exact quarters); az_clockwise: f = -f; s = f - floor(f).  atanP(r) = r * (A0 + z * (A1 + ... +
+ * z * A8)), z = r*r, with the coefficients of Abramowitz & Stegun 4.4.49 (1, -0.3333314528, 0.1999355085, -0.1420889944,
+ * 0.1065626393, -0.0752896400, 0.0429096138, -0.0161657367, 0.0028662257): within 2e-8 rad, 3e-9 of a turn.
+ * az_start_turn = -0.5, counter-clockwise, is a sweep that starts and ends at the -x axis.
+ *
+ * One launch whatever the data (256 threads per workgroup, one thread per row; N == 0: one workgroup that only writes
+ * motion_out); every workgroup derives the motion block again (one lane, LDS, a barrier) and workgroup 0 stores it.
+ * Everything on `stream`, no host read, no allocation, no atomic: capturable.  Errors are found before the launch and
+ * write nothing, RSLO_EINVAL: a null points or out with N > 0, N < 0, n_cols outside 3 .. stride_floats or
+ * 3 .. out_stride_floats, a normal_col other than -1 outside 3 .. n_cols - 3, stamp outside [0, 1] or NaN, max_angle
+ * outside (0, pi/2], a non-finite az_start_turn, rel7 together with a pose, only one of pose_a and pose_b.
+ * ------------------------------------------------------------------------------------ */
+RSLO_API int rslo_deskew(const float *points, int stride_floats, int N, int n_cols, int normal_col /* -1: none */,
+                         const float *times /* [N] sweep fractions, or NULL: from the azimuth */,
+                         const float *rel7 /* device fp32 (t, q wxyz), or NULL */,
+                         const double *pose_a, const double *pose_b /* device [7] each, both or neither: motion = A^-1 o B */,
+                         double stamp, double az_start_turn, int az_clockwise, double max_angle,
+                         float *out, int out_stride_floats, double *motion_out /* device [8], or NULL */, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

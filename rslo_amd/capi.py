@@ -248,6 +248,8 @@ SIGNATURES = {
     "rslo_surfel_normal_eq": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
     "rslo_surfel_register": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, _i, C.c_double, C.c_double, _i, C.c_double,
                                        C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_deskew": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i, C.c_double, _vp, _i, _vp,
+                              _vp]),
 }
 
 
@@ -1581,6 +1583,42 @@ def surfel_register(buf, points, pose, voxel_size, iters=4, max_dist=None, dampi
                                     float(tol_t), float(tol_r), float(robust_scale), _ptr(info, torch.float64, "info"),
                                     ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_surfel_register")
     return info
+
+
+def _rows_of(t, name):
+    """(pointer, stride in floats) of an fp32 CUDA [N, F] tensor whose rows are contiguous and evenly spaced"""
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.dim() == 2
+            and (t.shape[1] == 0 or t.stride(1) == 1) and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1])):
+        raise RsloHipError("%s must be an fp32 CUDA [N, F] tensor with contiguous rows" % name)
+    return t.data_ptr(), int(t.stride(0)) if t.shape[0] > 1 else int(max(t.stride(0), t.shape[1]))
+
+
+def deskew(points, out, times=None, rel7=None, pose_a=None, pose_b=None, stamp=0.5, az_start_turn=-0.5, az_clockwise=False,
+           max_angle=1.5707963267948966, normal_col=-1, motion_out=None):
+    """rslo_deskew on the current stream: the rows of points (fp32 CUDA [N, F], rows contiguous, any row stride) moved to
+    the sensor frame at sweep fraction `stamp` into out (the same shape; may be points itself).  times: fp32 CUDA [N]
+    sweep fractions, or None: from the azimuth.  Motion: rel7 (fp32 CUDA [7]), or pose_a and pose_b (float64 CUDA [7]
+    each: A^-1 o B), or none of them (a copy).  motion_out: float64 CUDA [8] or None.  One launch, no host read."""
+    src, stride = _rows_of(points, "deskew: points")
+    dst, ostride = _rows_of(out, "deskew: out")
+    if out.shape != points.shape or out.device != points.device:
+        raise RsloHipError("deskew: out must have the shape and the device of points")
+    N, F = points.shape
+    if times is not None and not (torch.is_tensor(times) and times.is_cuda and times.dtype == torch.float32
+                                  and times.shape == (N,) and times.is_contiguous()):
+        raise RsloHipError("deskew: times must be a contiguous fp32 CUDA [N] tensor")
+    if rel7 is not None and not (torch.is_tensor(rel7) and rel7.is_cuda and rel7.dtype == torch.float32
+                                 and rel7.numel() == 7 and rel7.is_contiguous()):
+        raise RsloHipError("deskew: rel7 must be 7 contiguous fp32 values on the GPU")
+    if motion_out is not None and not (torch.is_tensor(motion_out) and motion_out.is_cuda and motion_out.shape == (8,)
+                                       and motion_out.dtype == torch.float64 and motion_out.is_contiguous()):
+        raise RsloHipError("deskew: motion_out must be a contiguous float64 CUDA [8] tensor")
+    _chk(lib().rslo_deskew(src if N else None, stride, N, F, int(normal_col), _dp(times), _dp(rel7),
+                           None if pose_a is None else _pose7(pose_a, "deskew"),
+                           None if pose_b is None else _pose7(pose_b, "deskew"), float(stamp), float(az_start_turn),
+                           int(bool(az_clockwise)), float(max_angle), dst if N else None, ostride, _dp(motion_out), _stream()),
+         "rslo_deskew")
+    return out
 
 
 def chamfer_grad(xyz1, xyz2, graddist1, idx1, g1=None, g2=None):

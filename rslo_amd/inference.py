@@ -26,11 +26,12 @@ from rslo_amd.plan import EncoderPlanner
 
 
 class _Handle:
-    __slots__ = ("slot", "job", "error", "issued", "source")
+    __slots__ = ("slot", "job", "error", "issued", "source", "times")
 
     def __init__(self, slot):
         self.slot, self.job, self.error, self.issued = slot, None, None, threading.Event()
         self.source = None      # OdometryRunner with a voxel map: the tensor the caller passed to submit()
+        self.times = None       # OdometryRunner with deskew=dict(times="input"): the scan's sweep fractions
 
 
 class EncoderGraphRunner:
@@ -332,11 +333,29 @@ class OdometryRunner:
       store under the same poses (SurfelMap.insert_frames).  The table only fills unless local_map= carries the
       surfels key (above): then it is pruned about the sensor every K scans and a long drive runs in a fixed table.
       trajectory() and relative() are untouched.  None (the default): the launches of before.
+    * De-skewing: deskew=dict(motion="network", times="azimuth", stamp=0.5, az_start_turn=-0.5, az_clockwise=False,
+      max_angle=pi/2) (these defaults; rslo_amd/deskew.py, csrc/deskew.hip) motion-compensates every sweep before the
+      back end sees it: behind the head replay (or the eager head) and before the second chain, run() de-skews the
+      tensor passed to submit() into a runner-owned [point_capacity, F] buffer -- the normals are rotated when F >= 7,
+      the caller's tensor is not written, the encoder's arena cloud is not read -- and both register stages, both map
+      inserts, places.describe and keyframes.prepare read that buffer instead of the submitted tensor.  One launch per
+      scan, no synchronisation, nothing allocated (the buffer is made by the first submit(), which fixes F).  The
+      motion of the sweep: motion="network" uses rel[n], and none for n == 0 (the pair is the scan with itself);
+      motion="refined" (needs refine= or surfel_refine=, whose chain starts at the identity) uses
+      between(refined[n-2], refined[n-1]), the constant-velocity model on the corrected chain, and none for n < 2.
+      Whether a motion is given is decided by the host's own scan count.  times="azimuth" dates a return by its
+      azimuth (a sweep from az_start_turn, in turns, counter-clockwise unless az_clockwise); times="input" takes
+      submit(cloud, times) / feed(scans, times): one contiguous fp32 CUDA [P] tensor of sweep fractions per scan.
+      deskew_info() is the [n, 8] motion blocks {axis, angle, t', status} on the device, deskewed() the view of the
+      last scan.  The ENCODER's input is deliberately not de-skewed: its job is planned one scan ahead on the helper
+      thread, before any motion for that scan exists.  trajectory() and relative() stay bit for bit.  Unknown keys
+      are errors at construction.  None (the default): every launch and every bit of before.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
                  normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None,
-                 places=None, loop=None, pose_graph=None, keyframes=None, verify=None, surfels=None, surfel_refine=None):
+                 places=None, loop=None, pose_graph=None, keyframes=None, verify=None, surfels=None, surfel_refine=None,
+                 deskew=None):
         from rslo_amd import synthetic
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
@@ -354,6 +373,15 @@ class OdometryRunner:
                 surfel_refine = surfels_mod.check_surfel_refine(surfel_refine, surfels)
             except ValueError as e:
                 raise capi.RsloHipError("OdometryRunner: %s" % e)
+        if deskew is not None:
+            from rslo_amd import deskew as deskew_mod
+            try:
+                deskew = deskew_mod.check_deskew(deskew)
+            except ValueError as e:
+                raise capi.RsloHipError("OdometryRunner: %s" % e)
+            if deskew["motion"] == "refined" and refine is None and surfel_refine is None:
+                raise capi.RsloHipError("OdometryRunner: deskew motion=\"refined\" needs refine= or surfel_refine= (the "
+                                        "chain it reads)")
         if loop is not None and places is None:
             raise capi.RsloHipError("OdometryRunner: loop needs places=PlaceDB(...) to search")
         if places is not None:
@@ -508,6 +536,10 @@ class OdometryRunner:
             self._verifier = loops_mod.LoopVerifier(keyframes, **verify)
             self._edges = loops_mod.EdgeList(edge_opts[0], edge_opts[1], device=dev)
             self._checks = torch.zeros((self.capacity, loop["top_k"], loops_mod.OUT_COLS), dtype=torch.float64, device=dev)
+        self.deskew = deskew
+        self._deskewer = self._deskewed = None      # the stage is built by the first submit(), which fixes F
+        if deskew is not None:
+            self._dk_info = torch.zeros((self.capacity, 8), dtype=torch.float64, device=dev)
         self.pose_graph = pose_graph
         self._optimized = self._pg_info = None
         if pose_graph is not None and pose_graph.device != dev:
@@ -515,7 +547,7 @@ class OdometryRunner:
         self.stats = {"scans": 0, "encoder_runs": 0, "head_replays": 0, "head_eager": 0, "captures": 0,
                       "weight_refreshes": 0}
 
-    def submit(self, cloud):
+    def submit(self, cloud, times=None):
         raw = torch.is_tensor(cloud) and cloud.dim() == 2 and cloud.shape[1] in (3, 4)
         if self.normals == "input" and raw:
             raise capi.RsloHipError("OdometryRunner.submit: a [P, %d] scan has no normals; this runner takes [P, 7] clouds -- "
@@ -528,23 +560,45 @@ class OdometryRunner:
                 raise capi.RsloHipError("OdometryRunner.submit: the scan exceeds point_capacity = %d"
                                         % self.encoder.point_capacity)
         keep = (self.voxel_map is not None or self.places is not None or self.keyframes is not None
-                or self.surfels is not None)
+                or self.surfels is not None or self.deskew is not None)
         if keep and not (torch.is_tensor(cloud) and cloud.is_cuda and cloud.dtype == torch.float32 and cloud.dim() == 2):
             raise capi.RsloHipError("OdometryRunner.submit: a runner with a voxel map%s takes one fp32 CUDA [P, F] tensor"
                                     % ("" if self.places is None else " or a place database"))
+        if times is not None and (self.deskew is None or self.deskew["times"] != "input"):
+            raise capi.RsloHipError("OdometryRunner.submit: a times tensor needs deskew=dict(times=\"input\")")
+        if self.deskew is not None:
+            P, F = cloud.shape
+            if self.deskew["times"] == "input" and not (torch.is_tensor(times) and times.is_cuda and times.shape == (P,)
+                                                        and times.dtype == torch.float32 and times.is_contiguous()):
+                raise capi.RsloHipError("OdometryRunner.submit: deskew times=\"input\" takes a contiguous fp32 CUDA [P] "
+                                        "tensor of sweep fractions with every scan")
+            if P > self.encoder.point_capacity:
+                raise capi.RsloHipError("OdometryRunner.submit: the scan exceeds point_capacity = %d"
+                                        % self.encoder.point_capacity)
+            if self._deskewer is None:
+                from rslo_amd import deskew as deskew_mod
+                self._deskewer = deskew_mod.Deskewer(self.encoder.point_capacity, F, self.device, **self.deskew)
+            elif self._deskewer.n_cols != F:
+                raise capi.RsloHipError("OdometryRunner.submit: the de-skewing buffer holds [P, %d] scans, got [P, %d]"
+                                        % (self._deskewer.n_cols, F))
         h = self.encoder.submit(cloud)
         h.source = cloud if keep else None
+        h.times = times
         return h
 
-    def feed(self, scans):
+    def feed(self, scans, times=None):
         """Drive the runner over the sequence `scans` in order: scan i + 1 is submitted before scan i is run, so the
-        helper thread plans the next scan while the device works on this one.  Nothing is read back and nothing is
+        helper thread plans the next scan while the device works on this one.  times: one sweep-fraction tensor per scan
+        (deskew=dict(times="input")), else None.  Nothing is read back and nothing is
         returned (trajectory(), relative() ... hold the results); never more than two handles are outstanding."""
         if len(scans) == 0:
             return
-        h = self.submit(scans[0])
-        for cloud in scans[1:]:
-            ahead = self.submit(cloud)
+        if times is not None and len(times) != len(scans):
+            raise capi.RsloHipError("OdometryRunner.feed: %d scans and %d times tensors" % (len(scans), len(times)))
+        submit = (lambda i: self.submit(scans[i])) if times is None else (lambda i: self.submit(scans[i], times[i]))
+        h = submit(0)
+        for i in range(1, len(scans)):
+            ahead = submit(i)
             self.run(h)
             h = ahead
         self.run(h)
@@ -562,6 +616,7 @@ class OdometryRunner:
         """A new sequence: the next scan is paired with itself and seeds a new trajectory."""
         self._count.zero_()
         self._n = 0
+        self._deskewed = None
         if self.voxel_map is not None:
             self.voxel_map.reset()
         if self.surfels is not None:
@@ -680,6 +735,21 @@ class OdometryRunner:
             raise capi.RsloHipError("OdometryRunner.surfel_refine_info: the runner was built without surfel_refine")
         return self._info3[:min(self._n, self.capacity)]
 
+    def deskew_info(self):
+        """[n, 8] fp64 device rows (deskew=...): the motion block {axis, angle, t', status} every scan was de-skewed with."""
+        if self.deskew is None:
+            raise capi.RsloHipError("OdometryRunner.deskew_info: the runner was built without deskew")
+        return self._dk_info[:min(self._n, self.capacity)]
+
+    def deskewed(self):
+        """The [P, F] fp32 view of the runner's buffer that holds the last scan de-skewed (deskew=...); the next run()
+        overwrites it."""
+        if self.deskew is None:
+            raise capi.RsloHipError("OdometryRunner.deskewed: the runner was built without deskew")
+        if self._deskewed is None:
+            raise capi.RsloHipError("OdometryRunner.deskewed: no scan has been run since reset()")
+        return self._deskewed
+
     def refine_info(self):
         """[n, iters, 8] fp64 device rows: VoxelMap.register's info of every scan."""
         if self.refine is None:
@@ -744,19 +814,26 @@ class OdometryRunner:
             self._head_and_chain()
             self.stats["head_eager"] += 1
         n = self._n
+        source = handle.source              # what the back end reads: the submitted tensor, or its de-skewed copy
+        if self.deskew is not None:         # behind the head (rel[n] is written), before the second chain: one launch
+            if self.deskew["motion"] == "network":
+                motion = dict(rel7=self._rel[n]) if n >= 1 else {}
+            else:                           # constant velocity on the corrected chain, whose rows below n are final
+                motion = dict(pose_a=self._traj2[n - 2], pose_b=self._traj2[n - 1]) if n >= 2 else {}
+            source = self._deskewed = self._deskewer(handle.source, handle.times, motion_out=self._dk_info[n], **motion)
         chain = self._traj2 if self._refined else self._traj      # the chain whose row n places this scan in the maps
         if self._refined:                   # the second chain: predict from the refined pose, register, compose onto the result
             rel = self._rel[n]
             capi.pose_chain(rel[:3], rel[3:], self._state2, self._count2, self._rel2, self._traj2)
             if self.refine is not None:
-                self.voxel_map.register(handle.source, self._traj2[n], info=self._info2[n], **self.refine)
+                self.voxel_map.register(source, self._traj2[n], info=self._info2[n], **self.refine)
             if self.surfel_refine is not None:      # behind refine's own stage, on the same row
-                self.surfels.register(handle.source, self._traj2[n], info=self._info3[n], **self.surfel_refine)
+                self.surfels.register(source, self._traj2[n], info=self._info3[n], **self.surfel_refine)
             self._state2.copy_(self._traj2[n])
         if self.voxel_map is not None:      # behind the pose chain (and the registration) that wrote row n, on this stream
-            self.voxel_map.insert(handle.source, chain[n])
+            self.voxel_map.insert(source, chain[n])
         if self.surfels is not None:
-            self.surfels.insert(handle.source, chain[n])
+            self.surfels.insert(source, chain[n])
         if self.local_map is not None and (n + 1) % self.local_map["every"] == 0:
             lm = self.local_map
             if self.voxel_map is not None:
@@ -764,17 +841,17 @@ class OdometryRunner:
             if "surfels" in lm:                 # the same row and the same radius
                 self.surfels.prune(chain[n], lm["radius"], lm["surfels"]["inner_radius"], lm["surfels"]["min_count"])
         if self.places is not None:         # describe -> query -> add: the scan is searched for before it is stored
-            self.places.describe(handle.source)
+            self.places.describe(source)
             self.places.query(out=self._loop[n], **self.loop)
             if self.keyframes is not None:  # prepare -> verify -> emit -> add: an edge's j is the store's count before add
-                self.keyframes.prepare(handle.source)
+                self.keyframes.prepare(source)
                 if self._verifier is not None:
                     self._verifier.verify(self._loop[n], out=self._checks[n])
                     self._edges.emit(self._checks[n], self.keyframes)
                 self.keyframes.add()
             self.places.add()
         elif self.keyframes is not None:
-            self.keyframes.prepare(handle.source)
+            self.keyframes.prepare(source)
             self.keyframes.add()
         self._n += 1
         self.stats["scans"] += 1

@@ -15,6 +15,7 @@
     python scripts/odometry_stream.py --rebuild-map --scans 200 --warmup 20 [--out profiles/odometry_stream_rebuild.json]
     python scripts/odometry_stream.py --surfels --scans 200 --warmup 20 [--surfel-voxel 0.4] [--surfel-iters 4] [--out profiles/odometry_stream_surfels.json]
     python scripts/odometry_stream.py --surfels --local-map-radius 50 --surfel-min-count 2 --surfel-inner-radius 25 --scans 180 --warmup 20
+    python scripts/odometry_stream.py --deskew --scans 100 --warmup 10 [--out profiles/odometry_stream_deskew.json]
 
 A synthetic drive (rslo_amd.synthetic.sequence_scan: C2-shaped 64-beam scans, consecutive scans overlapping) is fed
 scan by scan to
@@ -73,6 +74,15 @@ size: frames, points, cells, dropped_full, the times, and whether the two maps a
 filled under the drive's own poses unpruned and pruned (SurfelMap.prune about the scan's pose every K scans;
 rslo_surfel_prune in csrc/surfel.hip): n_cells, n_planar, dropped_full and the prune counters side by side, and the
 device-event time of the prune call at capacity 2^20 beside VoxelMap.prune's (surfel_local_map_report).
+--deskew: scan de-skewing (rslo_amd.deskew, csrc/deskew.hip).  The drive's scans are rigid snapshots; their SKEWED twin
+is what a sensor that moves during the sweep records: deskew.skew_ref under the drive's true motion
+between(sequence_pose(i-1), sequence_pose(i)), the time of a return being the sweep fraction of the azimuth at which it
+is recorded, stamp 0.5.  The twin is de-skewed on the device (Deskewer, the motion given as that pose pair), and the
+registration-alone pass against a surfel map runs on three lists -- the original scans, the skewed ones, the de-skewed
+ones: pose error before / after for each (the network of this script is untrained, so accuracy is measured as the other
+reports measure it), with the distance of the skewed and of the de-skewed points from the original ones.  The kernel
+alone under device events, and the runner with and without deskew= in this one process, plain and with the surfel stage
+(--seed must be the drive's).
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -214,6 +224,8 @@ def main():
     ap.add_argument("--surfel-inner-radius", type=float, default=None,
                     help="with --surfels --local-map-radius: cells nearer than this are exempt from --surfel-min-count "
                          "(default: the radius)")
+    ap.add_argument("--deskew", action="store_true",
+                    help="also de-skew a skewed twin of the drive and run the runner with deskew=")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -314,6 +326,8 @@ def main():
         res.update(surfel_report(args, net, scans, res))
         if args.local_map_radius is not None:
             res.update(surfel_local_map_report(args, scans))
+    if args.deskew:
+        res.update(deskew_report(args, net, scans, res))
     line = json.dumps(res)
     print(line)
     if args.out:
@@ -974,6 +988,65 @@ def surfel_report(args, net, scans, res):
     out.update(register_alone(args, scans, _Targets(pyr, smap),
                               lambda s, p: torch.cat([pyr.register(s, p, sch)[1], smap.register(s, p, iters=K, **kw)[1]]),
                               "pyramid_then_surfel", pairs_row=-1))
+    return out
+
+
+def deskew_report(args, net, scans, res):
+    """--deskew: the skewed twin of the drive de-skewed on the device; the registration-alone pass on the original, the
+    skewed and the de-skewed scans against a surfel map; the kernel alone; the runner with and without deskew=."""
+    import numpy as np
+    import torch
+    from rslo_amd import deskew, inference, se3, surfels, synthetic
+    dev = scans[0].device
+    W, N, K = args.warmup, args.scans, args.surfel_iters
+    opts = dict(deskew.DESKEW_DEFAULTS)
+    out = {"deskew": opts, "deskew_surfel_voxel": args.surfel_voxel}
+    true = [synthetic.sequence_pose(i, args.seed) for i in range(W + N)]
+    pairs = [(true[max(i - 1, 0)], true[max(i, 1)]) for i in range(W + N)]      # scan 0: the motion of the sweep after it
+    stage = deskew.Deskewer(max(s.shape[0] for s in scans), scans[0].shape[1], dev)
+    skewed, flat, d_skew, d_flat, angles, steps = [], [], [], [], [], []
+    for s, (A, B) in zip(scans, pairs):
+        block = deskew.motion_ref(pose_a=A, pose_b=B, stamp=opts["stamp"])
+        host = s.cpu().numpy()
+        twin = torch.from_numpy(deskew.skew_ref(host, None, block, stamp=opts["stamp"], normal_col=4).astype(np.float32)).to(dev)
+        skewed.append(twin)
+        flat.append(stage(twin, pose_a=torch.from_numpy(A).to(dev), pose_b=torch.from_numpy(B).to(dev)).clone())
+        d_skew.append((twin[:, :3] - s[:, :3]).norm(dim=1))
+        d_flat.append((flat[-1][:, :3] - s[:, :3]).norm(dim=1))
+        angles.append(block[3])
+        steps.append(float(np.linalg.norm(se3.between(A, B)[:3])))
+    out["deskew_motion_mean_m"] = round(float(np.mean(steps)), 4)
+    out["deskew_motion_mean_deg"] = round(float(np.rad2deg(np.mean(angles))), 4)
+    for name, d in (("skewed", torch.cat(d_skew)), ("deskewed", torch.cat(d_flat))):
+        p99 = (d if d.numel() < (1 << 24) else d[::8]).quantile(0.99)       # (quantile takes 2^24 elements at the most)
+        out["deskew_%s_point_offset_m" % name] = {"mean": float(d.mean()), "p99": float(p99), "max": float(d.max())}
+    # the registration-alone pass: the same seeded disturbance and the same map parameters for the three lists
+    smap = surfels.SurfelMap(args.surfel_voxel, 1 << 20, dev)
+    smap.reserve(max(s.shape[0] for s in scans))
+    kw = {k: v for k, v in surfels.SURFEL_REFINE_DEFAULTS.items() if k != "iters"}
+    for name, rows in (("original", scans), ("skewed", skewed), ("deskewed", flat)):
+        out.update(register_alone(args, rows, smap, lambda s, p: smap.register(s, p, iters=K, **kw)[1], "deskew_%s_alone" % name))
+    # the kernel alone: one launch per scan, the pose pair already on the device
+    dpairs = [(torch.from_numpy(A).to(dev), torch.from_numpy(B).to(dev)) for A, B in pairs]
+    stage(skewed[0], pose_a=dpairs[0][0], pose_b=dpairs[0][1])
+    out["deskew_kernel_ms_per_call"] = round(device_ms(lambda i: stage(skewed[W + i], pose_a=dpairs[W + i][0],
+                                                                       pose_b=dpairs[W + i][1]), N), 5)
+    out["deskew_kernel_bytes_per_call"] = int(2 * 4 * sum(s.numel() for s in skewed[W:W + N]) / N)
+    # the runner with and without the stage, alternated in this one process
+    for name, kwargs in (("plain", {}), ("surfels", dict(surfel_refine=dict(surfels.SURFEL_REFINE_DEFAULTS, iters=K)))):
+        for rep in range(2):
+            for which, extra in (("without", {}), ("with", dict(deskew={}))):
+                if "surfel_refine" in kwargs:
+                    smap.reset()
+                    kwargs["surfels"] = smap
+                runner = inference.OdometryRunner(net, **kwargs, **extra)
+                ms, host_ms = timed_feed(runner, skewed, W, N)
+                key = "deskew_runner_%s_%s_ms_per_scan" % (name, which)
+                out[key] = min(out.get(key, float("inf")), round(ms, 3))
+                if extra:
+                    info = runner.deskew_info().cpu().numpy()
+                    out["deskew_runner_%s_status_counts" % name] = [int((info[:, 7] == k).sum()) for k in range(4)]
+                runner.close()
     return out
 
 
