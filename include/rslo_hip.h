@@ -918,7 +918,8 @@ RSLO_API int rslo_voxel_downsample(const float *points, int stride_floats, const
  * 1024 .. 2^31:  header (256 bytes) | keys u64 [capacity] | tags u64 [capacity] | rows f32 [capacity, 4] | hits i32
  * [capacity].  The header as int64 words: [0] magic, [1] capacity, [2..4] voxel_size, min_range, max_range (doubles),
  * [RSLO_MAP_HDR_COUNTERS + 0..5] = n_scans, n_cells, n_points (accepted), dropped_invalid, dropped_range, dropped_full,
- * [RSLO_MAP_HDR_PRUNE + 0..2] = n_prunes, n_evicted, n_lost ("Rolling local map" below)
+ * [RSLO_MAP_HDR_PRUNE + 0..2] = n_prunes, n_evicted, n_lost ("Rolling local map" below),
+ * [RSLO_MAP_HDR_CARVE + 0..1] = n_carves, n_carved ("Free-space carving" below)
  * -- integer atomics only, so they are deterministic.  Open addressing, linear probing from a 64-bit mix of the key.
  * Probing is BOUNDED: at most RSLO_MAP_MAX_PROBE slots are examined; a point that finds neither its key nor an empty
  * slot among them is dropped (dropped_full).  No loop depends on the table having room: a full map costs a counter,
@@ -1013,6 +1014,55 @@ RSLO_API int rslo_map_insert_frames(void *map, size_t map_bytes, const void *sto
 RSLO_API size_t rslo_map_prune_ws_bytes(int64_t capacity);
 RSLO_API int rslo_map_prune(void *map, size_t map_bytes, const double *center3 /*device, or NULL*/, double radius,
                             int min_hits, int grace, void *ws, size_t ws_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Free-space carving (csrc/carve.hip): evict the cells of a world voxel map that the current scan sees THROUGH -- the
+ * trail a moving object leaves in a map that otherwise only fills.  A visibility check in the style of Removert: a range
+ * image of the scan, and one test per stored cell.  The float64 restatement is rslo_amd/carve.py (range_image_ref) and
+ * rslo_amd/mapping.py (VoxelMapRef.carve); the tests compare bit for bit.  All arithmetic is IEEE double without
+ * contraction, in the order written.
+ * The pixel of a sensor-frame position (x, y, z) with rho2 = x*x + y*y != 0, in an image of H rows (1 .. 256) and W
+ * columns (8 .. 4096) that spans the elevation tangents [tan_lo, tan_hi) (finite, tan_lo < tan_hi):
+ *   col = min(W-1, int(floor(f * W))), f = the azimuth turn fraction of (x, y) from -0.5, counter-clockwise -- the
+ *         function of "Scan de-skewing" (csrc/azimuth.h; rslo_amd/deskew.py sweep_fraction_ref); f can round to 1.
+ *   e = z / sqrt(rho2);  u = ((e - tan_lo) / (tan_hi - tan_lo)) * H;  no pixel unless u >= 0 && u < H;
+ *   row = int(floor(u)).  Rows are binned in the TANGENT of the elevation: no second arctangent.
+ * rslo_range_image: for point i, (x, y, z) = double(xyz_i); a point with a non-finite coordinate, with rho2 == 0 or
+ *   without a pixel is skipped; r = sqrt(rho2 + z*z).  img[row*W + col] = the minimum, as uint32, of the bit patterns of
+ *   float(r) over the pixel's points (positive floats order as their bits); an empty pixel holds 0xFFFFFFFF.  A minimum
+ *   does not depend on arrival order: the image is reproducible to the bit.  Two launches whatever the data (fill; one
+ *   thread per point with an atomic minimum); N == 0 leaves an empty image.  RSLO_EINVAL, writing nothing: H, W or the
+ *   tangents outside the above, stride_floats < 3, N < 0, a null img, null points with N > 0.
+ * rslo_map_carve: S = n_scans at the time of the call, pose7 = (t, q wxyz) 7 DEVICE doubles, the pose of the scan the
+ *   image was made of.  A stored cell with row (x, y, z, .) and tag is EVICTED iff every one of the following holds; a
+ *   comparison that is false keeps the cell, so a NaN pose carves nothing:
+ *   1. old enough:  S - 1 - (tag >> 32) >= grace;
+ *   2. in view:  d = double(row.xyz) - t per axis;  p = rotate(conj(q), d), conj(q) = (w, -x, -y, -z), the rotation of
+ *      the insert (q NOT renormalised);  rho2 = p.x*p.x + p.y*p.y > 0;  r_m = sqrt(rho2 + p.z*p.z) < max_range
+ *      (max_range may be +inf);  p has a pixel (row, col);
+ *   3. observed:  img[row*W + col] is not empty;
+ *   4. seen through:  m = the minimum of the non-empty pixels of the window rows row-win_rows .. row+win_rows clipped
+ *      to the image, columns col-win_cols .. col+win_cols wrapped modulo W;
+ *      double(float_of(m)) - r_m > margin_abs + margin_rel * r_m.
+ *   The window is what keeps the ground: at grazing incidence the range of the ground changes by metres across one
+ *   pixel of elevation, and the nearer return in the row below protects the cell.
+ *   Evicted cells are gone exactly as after rslo_map_prune, kept cells keep tag, row and hits to the bit, and the table
+ *   is rebuilt in place by prune's own launches through the same workspace; a call that evicts nothing leaves every slot
+ *   as it is, to the byte.  Header words [RSLO_MAP_HDR_CARVE + 0..1] = n_carves (calls), n_carved (cells, cumulative);
+ *   rslo_map_reset zeroes them.  n_cells is recounted, n_lost is added to as in the prune, n_prunes and n_evicted do
+ *   not move.  Five launches whatever the data, no host read, nothing allocated: capturable.
+ *   RSLO_EINVAL, writing nothing: the H, W and tangent errors above, win_rows outside 0 .. 4, win_cols outside 0 .. 8,
+ *   a negative or NaN margin, !(max_range > 0), grace < 0, a null map, img, pose7 or workspace, a workspace that is not
+ *   16-byte aligned; RSLO_EWS: ws_bytes below rslo_map_carve_ws_bytes (= rslo_map_prune_ws_bytes) of the capacity
+ *   map_bytes can hold.
+ * ------------------------------------------------------------------------------------ */
+#define RSLO_MAP_HDR_CARVE 14
+RSLO_API int rslo_range_image(const float *points, int stride_floats, int N, int H, int W, double tan_lo, double tan_hi,
+                              uint32_t *img /*[H*W]*/, void *stream);
+RSLO_API size_t rslo_map_carve_ws_bytes(int64_t capacity);
+RSLO_API int rslo_map_carve(void *map, size_t map_bytes, const uint32_t *img /*[H*W]*/, int H, int W, double tan_lo,
+                            double tan_hi, const double *pose7 /*device*/, int win_rows, int win_cols, double margin_abs,
+                            double margin_rel, double max_range, int grace, void *ws, size_t ws_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Scan-to-map registration (csrc/mapreg.hip): the world voxel map as a registration target.  Read-only on the map;

@@ -199,6 +199,10 @@ SIGNATURES = {
     "rslo_map_insert_frames": (C.c_int, [_vp, _sz, _vp, _sz, _i64, _i, _vp, _i, _vp]),
     "rslo_map_prune_ws_bytes": (_sz, [_i64]),
     "rslo_map_prune": (C.c_int, [_vp, _sz, _vp, C.c_double, _i, _i, _vp, _sz, _vp]),
+    "rslo_range_image": (C.c_int, [_vp, _i, _i, _i, _i, C.c_double, C.c_double, _vp, _vp]),
+    "rslo_map_carve_ws_bytes": (_sz, [_i64]),
+    "rslo_map_carve": (C.c_int, [_vp, _sz, _vp, _i, _i, C.c_double, C.c_double, _vp, _i, _i, C.c_double, C.c_double,
+                                 C.c_double, _i, _vp, _sz, _vp]),
     "rslo_map_params": (C.c_int, [_vp, _sz, _vp, _vp]),
     "rslo_map_nearest": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "rslo_map_register_ws_bytes": (_sz, [_i]),
@@ -1258,6 +1262,46 @@ def map_prune(buf, ws, center=None, radius=0.0, min_hits=1, grace=0):
         raise RsloHipError("map_prune: ws must be a contiguous CUDA tensor (map_prune_ws)")
     _chk(lib().rslo_map_prune(ptr, nbytes, None if center is None else center.data_ptr(), float(radius), int(min_hits),
                               int(grace), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_map_prune")
+
+
+# free-space carving (csrc/carve.hip; rules: include/rslo_hip.h "Free-space carving")
+MAP_HDR_CARVE = 14        # first int64 word of n_carves, n_carved in a map's header
+MAP_CARVE_COUNTERS = ("n_carves", "n_carved")
+
+
+def _range_img(img, H, W, name):
+    if not (torch.is_tensor(img) and img.is_cuda and img.dtype == torch.int32 and img.shape == (int(H), int(W))
+            and img.is_contiguous()):
+        raise RsloHipError("%s: the image must be a contiguous int32 CUDA [%d, %d] tensor (the uint32 range words)"
+                           % (name, H, W))
+    return img.data_ptr()
+
+
+def range_image(points, img, tan_lo, tan_hi):
+    """rslo_range_image on the current stream: the rows of points (fp32 CUDA [P, F >= 3], read in place, any row stride)
+    binned into img (int32 CUDA [H, W], holding the uint32 bit patterns of the nearest range per pixel, all-ones = empty)
+    over the elevation tangents [tan_lo, tan_hi).  Two launches, no host read."""
+    src, stride = _rows3(points, "range_image: points")
+    H, W = img.shape if torch.is_tensor(img) and img.dim() == 2 else (0, 0)
+    N = int(points.shape[0])
+    _chk(lib().rslo_range_image(src if N else None, stride, N, int(H), int(W), float(tan_lo), float(tan_hi),
+                                _range_img(img, H, W, "range_image"), _stream()), "rslo_range_image")
+    return img
+
+
+def map_carve(buf, ws, img, tan_lo, tan_hi, pose, win_rows=1, win_cols=1, margin_abs=0.3, margin_rel=0.0,
+              max_range=60.0, grace=1):
+    """rslo_map_carve on the current stream: evict the cells of the map that the scan behind img (range_image) sees
+    through from pose (float64 CUDA [7], read in place), by rebuilding the table through ws (map_prune_ws).  No host
+    read."""
+    ptr, nbytes = _map_buf(buf)
+    H, W = img.shape if torch.is_tensor(img) and img.dim() == 2 else (0, 0)
+    if not (torch.is_tensor(ws) and ws.is_cuda and ws.is_contiguous()):
+        raise RsloHipError("map_carve: ws must be a contiguous CUDA tensor (map_prune_ws)")
+    _chk(lib().rslo_map_carve(ptr, nbytes, _range_img(img, H, W, "map_carve"), int(H), int(W), float(tan_lo), float(tan_hi),
+                              _pose7(pose, "map_carve"), int(win_rows), int(win_cols), float(margin_abs), float(margin_rel),
+                              float(max_range), int(grace), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
+         "rslo_map_carve")
 
 
 # scan-to-map registration (csrc/mapreg.hip; rules: include/rslo_hip.h "Scan-to-map registration")

@@ -15,11 +15,10 @@
 #pragma clang fp contract(off)
 
 #include "se3.h"      /* the pose algebra, after the pragma: uncontracted here */
+#include "azimuth.h"  /* the sweep fraction of an azimuth, likewise */
 
 #define DSK_THREADS 256
-#define DSK_HALF_PI 1.5707963267948966
-#define DSK_PI 3.141592653589793
-#define DSK_TWO_PI 6.283185307179586
+#define DSK_HALF_PI AZ_HALF_PI
 
 // Taylor polynomials in Horner form in z = x*x, coefficients the doubles nearest +-1/k!, for |x| <= pi/4
 __device__ __forceinline__ double dsk_sin(double x) {
@@ -49,35 +48,7 @@ __device__ __forceinline__ double dsk_cos(double x) {
   return p;
 }
 
-// Abramowitz & Stegun 4.4.49 on [0, 1]
-__device__ __forceinline__ double dsk_atan(double r) {
-  const double z = r * r;
-  double p = 0.0028662257;
-  p = -0.0161657367 + z * p;
-  p = 0.0429096138 + z * p;
-  p = -0.0752896400 + z * p;
-  p = 0.1065626393 + z * p;
-  p = -0.1420889944 + z * p;
-  p = 0.1999355085 + z * p;
-  p = -0.3333314528 + z * p;
-  p = 1.0 + z * p;
-  return r * p;
-}
-
 __device__ __forceinline__ bool dsk_finite(double v) { return fabs(v) < (double)__builtin_inff(); }
-
-// the sweep fraction of a return at (x, y), neither both zero: the azimuth in turns from az_start_turn, in [0, 1]
-__device__ __forceinline__ double dsk_fraction(double x, double y, double az_start_turn, int az_clockwise) {
-  const double ax = fabs(x), ay = fabs(y);
-  const double lo = ax < ay ? ax : ay, hi = ax < ay ? ay : ax;
-  double phi = dsk_atan(lo / hi);
-  if (ay > ax) phi = DSK_HALF_PI - phi;
-  if (x < 0.0) phi = DSK_PI - phi;
-  if (y < 0.0) phi = -phi;
-  double f = phi / DSK_TWO_PI - az_start_turn;
-  if (az_clockwise) f = -f;
-  return f - floor(f);
-}
 
 // the motion block {a.x, a.y, a.z, theta, t'.x, t'.y, t'.z, status} of one call, by one lane
 __device__ void dsk_motion(const float *rel7, const double *pose_a, const double *pose_b, double stamp, double max_angle,
@@ -152,7 +123,7 @@ __global__ __launch_bounds__(DSK_THREADS) void k_deskew(const float *points, siz
     else if (p[0] == 0.0 && p[1] == 0.0)
       move = false;
     else
-      s = dsk_fraction(p[0], p[1], az_start_turn, az_clockwise);
+      s = az_fraction(p[0], p[1], az_start_turn, az_clockwise);
     move = move && dsk_finite(s);
   }
   if (!move) {

@@ -26,20 +26,12 @@
 #include <cstddef>
 
 #include "map_table.h"
+#include "map_rebuild.h"         /* the staging area and the rebuild launches rslo_map_carve shares (csrc/carve.hip) */
 #include "kf_store.h"            /* rslo_map_insert_frames reads a keyframe store */
 
 #pragma clang fp contract(off)   /* the cell of a point must not depend on FMA formation */
 
-#define MAP_SLOT_BYTES 36                /* key 8 + tag 8 + row 16 + hits 4 */
 #define MAP_FRAMES_BLOCKS 2048u          /* workgroups of rslo_map_insert_frames' points pass: eight per CU */
-
-static inline long long map_cap_of_bytes(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
-  if (bytes < (size_t)MAP_HDR_BYTES + (size_t)MAP_SLOT_BYTES * MAP_MIN_CAP) return 0;
-  const size_t slots = (bytes - MAP_HDR_BYTES) / MAP_SLOT_BYTES;
-  long long cap = MAP_MIN_CAP;
-  while ((size_t)cap * 2 <= slots && cap < ((long long)1 << 40)) cap *= 2;
-  return cap;
-}
 
 // filled in one launch: the header by thread 0, the sections by everybody
 __global__ __launch_bounds__(256) void k_map_reset(void *map, long long cap, double voxel, double min_range,
@@ -56,6 +48,7 @@ __global__ __launch_bounds__(256) void k_map_reset(void *map, long long cap, dou
     h->min_range = min_range;
     h->max_range = max_range;
     h->n_prunes = h->n_evicted = h->n_lost = 0;
+    h->n_carves = h->n_carved = 0;
     h->n_scans = h->n_cells = h->n_points = h->dropped_invalid = h->dropped_range = h->dropped_full = 0;
   }
   for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
@@ -298,31 +291,8 @@ __global__ __launch_bounds__(256) void k_map_export(void *map, long long cap_max
 // ---------------------------------------------------------------------------------------------------------------------
 // rslo_map_prune: evict far and sparse cells by rebuilding the table (rules: include/rslo_hip.h "Rolling local map").
 // Workspace: control block (256 bytes, zeroed by the first, one-thread launch) | staged keys u64 [cap] |
-// tags u64 [cap] | rows f32 [cap, 4] | hits i32 [cap] -- the map's own section layout.
+// tags u64 [cap] | rows f32 [cap, 4] | hits i32 [cap] -- the map's own section layout (map_rebuild.h).
 // ---------------------------------------------------------------------------------------------------------------------
-#define PRUNE_CTL_BYTES 256
-struct PruneCtl {
-  map_u64 kept, evicted, lost;
-};
-
-struct PruneStage {
-  PruneCtl *ctl;
-  map_u64 *keys, *tags;
-  float4 *rows;
-  int32_t *hits;
-};
-
-__device__ __forceinline__ PruneStage prune_stage(void *ws, long long cap) {
-  unsigned char *p = (unsigned char *)ws + PRUNE_CTL_BYTES;
-  PruneStage st;
-  st.ctl = (PruneCtl *)ws;
-  st.keys = (map_u64 *)p;
-  st.tags = (map_u64 *)(p + (size_t)cap * 8);
-  st.rows = (float4 *)(p + (size_t)cap * 16);
-  st.hits = (int32_t *)(p + (size_t)cap * 32);
-  return st;
-}
-
 // the control block starts every call at zero
 __global__ void k_map_prune_begin(void *ws) {
   if (threadIdx.x == 0) {
@@ -528,6 +498,15 @@ extern "C" int rslo_map_export(const void *map, size_t map_bytes, int min_hits, 
   return RSLO_OK;
 }
 
+// the launches of a rebuild that do not depend on who removes the cells (map_rebuild.h)
+void map_rebuild_begin(void *ws, hipStream_t s) { hipLaunchKernelGGL(k_map_prune_begin, dim3(1), dim3(64), 0, s, ws); }
+
+void map_rebuild_table(void *map, long long cap_max, void *ws, hipStream_t s) {
+  const unsigned nb = map_rebuild_blocks(cap_max);
+  hipLaunchKernelGGL(k_map_prune_clear, dim3(nb), dim3(256), 0, s, map, cap_max, (const void *)ws);
+  hipLaunchKernelGGL(k_map_prune_reinsert, dim3(nb), dim3(256), 0, s, map, cap_max, ws);
+}
+
 extern "C" size_t rslo_map_prune_ws_bytes(int64_t capacity) {
   if (rslo_map_bytes(capacity) == 0) return 0;
   return (size_t)PRUNE_CTL_BYTES + (size_t)MAP_SLOT_BYTES * (size_t)capacity;
@@ -545,11 +524,10 @@ extern "C" int rslo_map_prune(void *map, size_t map_bytes, const double *center3
     rslo_set_error("map_prune: workspace too small");
     return RSLO_EWS;
   }
-  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
-  hipLaunchKernelGGL(k_map_prune_begin, dim3(1), dim3(64), 0, s, ws);
+  const unsigned nb = map_rebuild_blocks(cap_max);
+  map_rebuild_begin(ws, s);
   hipLaunchKernelGGL(k_map_prune_scan, dim3(nb), dim3(256), 0, s, map, cap_max, center3, radius, min_hits, grace, ws);
-  hipLaunchKernelGGL(k_map_prune_clear, dim3(nb), dim3(256), 0, s, map, cap_max, (const void *)ws);
-  hipLaunchKernelGGL(k_map_prune_reinsert, dim3(nb), dim3(256), 0, s, map, cap_max, ws);
+  map_rebuild_table(map, cap_max, ws, s);
   hipLaunchKernelGGL(k_map_prune_done, dim3(1), dim3(64), 0, s, map, cap_max, (const void *)ws);
   RSLO_CHECK_LAUNCH("map_prune");
   return RSLO_OK;

@@ -15,12 +15,13 @@ typedef unsigned long long map_u64;
 #define MAP_MAXC 1048576.0               /* 2^20: |cell| of a stored point is below it */
 #define MAP_MIN_CAP 1024
 
-struct MapHdr {                          // int64 words: 0 magic, 1 capacity, 2-4 parameters, 5-7 prune counters, 8-13 counters
-  map_u64 magic;
+struct MapHdr {                          // int64 words: 0 magic, 1 capacity, 2-4 parameters, 5-7 prune counters, 8-13 counters,
+  map_u64 magic;                         // 14-15 carve counters
   long long capacity;
   double voxel, min_range, max_range;
-  map_u64 n_prunes, n_evicted, n_lost;   // written by rslo_map_prune's last launch only
+  map_u64 n_prunes, n_evicted, n_lost;   // written by rslo_map_prune's last launch only (n_lost: by rslo_map_carve's too)
   map_u64 n_scans, n_cells, n_points, dropped_invalid, dropped_range, dropped_full;
+  map_u64 n_carves, n_carved;            // written by rslo_map_carve's last launch only
 };
 static_assert(sizeof(MapHdr) <= MAP_HDR_BYTES, "map header");
 

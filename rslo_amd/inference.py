@@ -350,13 +350,30 @@ class OdometryRunner:
       last scan.  The ENCODER's input is deliberately not de-skewed: its job is planned one scan ahead on the helper
       thread, before any motion for that scan exists.  trajectory() and relative() stay bit for bit.  Unknown keys
       are errors at construction.  None (the default): every launch and every bit of before.
+    * Free-space carving: carve=dict(every=1, rows=64, cols=1024, tan_lo=tan(-25 deg), tan_hi=tan(3 deg), win_rows=1,
+      win_cols=1, margin_abs=0.3, margin_rel=0.0, max_range=60.0, grace=1) (these defaults; rslo_amd/carve.py,
+      csrc/carve.hip; needs voxel_map) removes what moves: when (n + 1) % every == 0, behind the registration of scan n
+      and in FRONT of its insert, run() builds the range image of the scan the back end reads (the de-skewed buffer
+      with deskew=) and calls voxel_map.carve(image, row n of the chain that feeds the insert) -- a VoxelMap, or every
+      level of a MapPyramid (VoxelMap.carve; include/rslo_hip.h "Free-space carving").  Two launches for the image and
+      five per map level, no synchronisation, nothing allocated (the image and the rebuild's workspace are made here).  The surfel map
+      is not carved.  trajectory() and relative() are untouched.  Unknown keys are errors at construction.  None (the
+      default): every launch and every bit of before.
     `rel` and `pose` are rows of the runner's device buffers [capacity, 7]; they stay valid until reset()."""
 
     def __init__(self, net, max_voxels=None, device="cuda", capacity=8192, arenas=4, point_capacity=160000,
                  normals="input", normal_radius=0.6, normal_max_nn=30, voxel_map=None, refine=None, local_map=None,
                  places=None, loop=None, pose_graph=None, keyframes=None, verify=None, surfels=None, surfel_refine=None,
-                 deskew=None):
+                 deskew=None, carve=None):
         from rslo_amd import synthetic
+        if carve is not None:
+            from rslo_amd import carve as carve_mod
+            if voxel_map is None:
+                raise capi.RsloHipError("OdometryRunner: carve needs a voxel_map to carve")
+            try:
+                carve = carve_mod.check_carve(carve)
+            except ValueError as e:
+                raise capi.RsloHipError("OdometryRunner: %s" % e)
         if normals not in ("input", "estimate"):
             raise capi.RsloHipError("OdometryRunner: normals must be \"input\" or \"estimate\", got %r" % (normals,))
         if refine is not None and voxel_map is not None:      # (before anything is built: a refused option leaves nothing behind)
@@ -519,6 +536,13 @@ class OdometryRunner:
             self.local_map = local_map
             if voxel_map is not None:
                 voxel_map.reserve_prune()               # run() must not allocate
+        self.carve = carve
+        self._range_image = None
+        if carve is not None:
+            from rslo_amd import carve as carve_mod
+            self._range_image = carve_mod.RangeImage(carve["rows"], carve["cols"], carve["tan_lo"], carve["tan_hi"], dev)
+            self._carve_kw = {k: carve[k] for k in ("win_rows", "win_cols", "margin_abs", "margin_rel", "max_range", "grace")}
+            voxel_map.reserve_prune()                   # the rebuild shares prune's workspace: run() must not allocate
         self.places, self.loop = places, loop
         if places is not None:
             if places.device != dev:
@@ -830,6 +854,8 @@ class OdometryRunner:
             if self.surfel_refine is not None:      # behind refine's own stage, on the same row
                 self.surfels.register(source, self._traj2[n], info=self._info3[n], **self.surfel_refine)
             self._state2.copy_(self._traj2[n])
+        if self.carve is not None and (n + 1) % self.carve["every"] == 0:      # behind the registration, in front of the insert
+            self.voxel_map.carve(self._range_image(source), chain[n], **self._carve_kw)
         if self.voxel_map is not None:      # behind the pose chain (and the registration) that wrote row n, on this stream
             self.voxel_map.insert(source, chain[n])
         if self.surfels is not None:

@@ -54,6 +54,29 @@ Rolling local map (rules: include/rslo_hip.h "Rolling local map"), on both class
     that found no slot within 128 probes when the table was rebuilt (dropped whole; impossible while the survivors'
     longest run of occupied slots is below 128; VoxelMapRef has no capacity: always 0).  reset() zeroes them.
 
+Free-space carving (csrc/carve.hip; rules: include/rslo_hip.h "Free-space carving"; the image: rslo_amd/carve.py), on
+both classes and on the pyramids, which apply the one image to every level:
+
+    ri = carve.RangeImage(rows=64, cols=1024)                  # the range image of a scan, on the device
+    vmap.carve(ri(scan), pose)                                 # forget the cells the scan at `pose` sees through
+    ref.carve(carve.range_image_ref(scan), pose)               # VoxelMapRef takes the uint32 [H, W] array
+
+  * carve(image, pose, tan_lo=None, tan_hi=None, win_rows=1, win_cols=1, margin_abs=0.3, margin_rel=0.0, max_range=60.0,
+    grace=1); tan_lo / tan_hi None: those of a RangeImage, else carve.CARVE_DEFAULTS.  S = n_scans at the time of the
+    call.  A stored cell with row (x, y, z, .) and tag is EVICTED iff all of these hold -- a comparison that is false
+    keeps the cell, so a NaN pose carves nothing.  Old enough: S - 1 - (tag >> 32) >= grace.  In view:
+    d = float64(row.xyz) - t; p = rotate(conj(q), d) with conj(q) = (w, -x, -y, -z), q not renormalised;
+    rho2 = p.x*p.x + p.y*p.y > 0; r_m = sqrt(rho2 + p.z*p.z) < max_range (+inf allowed); p has a pixel (row, col) by
+    carve.pixel_ref.  Observed: that pixel is not empty.  Seen through: with m the minimum of the non-empty pixels in
+    the window rows row +- win_rows (clipped) x columns col +- win_cols (wrapped modulo W),
+    float64(float32_of(m)) - r_m > margin_abs + margin_rel * r_m.  The window is what keeps the ground: at grazing
+    incidence its range changes by metres across one pixel of elevation, and the nearer return in the row below
+    protects the cell;
+  * evicted cells are gone exactly as after a prune, kept cells keep tag, row and hits to the bit, n_cells is recounted;
+    carve_stats() -> {n_carves, n_carved}; n_lost (prune_stats) is added to as in the prune, n_prunes and n_evicted do
+    not move.  A call that evicts nothing leaves the device table as it is, to the byte.  An argument outside its
+    range (carve.check_image, carve.check_rule) is a ValueError and writes nothing.
+
 Scan-to-map registration (csrc/mapreg.hip; rules: include/rslo_hip.h "Scan-to-map registration") reads the map back, on
 both classes:
 
@@ -102,6 +125,7 @@ from .gauss_newton import gauss_newton_step, point_jacobian, terms_of
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full")
 PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
+CARVE_COUNTERS = ("n_carves", "n_carved")
 _MAXC = 1 << 20
 
 
@@ -164,6 +188,20 @@ def check_prune(center, radius, min_hits, grace, has_center=None):
     if int(min_hits) != min_hits or int(grace) != grace or min_hits < 1 or grace < 0:
         raise ValueError("prune: min_hits >= 1 and grace >= 0 must be integers, got %r and %r" % (min_hits, grace))
     return r
+
+
+def check_carve_call(image, tan_lo, tan_hi, win_rows, win_cols, margin_abs, margin_rel, max_range, grace):
+    """The argument errors of carve (ValueError), raised before anything is written.  image: anything with a 2-D .shape,
+    or a carve.RangeImage, whose tangents stand in for tan_lo / tan_hi = None (else carve.CARVE_DEFAULTS).
+    -> (H, W, tan_lo, tan_hi, win_rows, win_cols, margin_abs, margin_rel, max_range, grace)"""
+    from . import carve as carve_mod
+    shape = tuple(getattr(getattr(image, "img", image), "shape", ()))
+    if len(shape) != 2:
+        raise ValueError("carve: the image must be [rows, cols], got shape %r" % (shape,))
+    tan_lo = getattr(image, "tan_lo", carve_mod.CARVE_DEFAULTS["tan_lo"]) if tan_lo is None else tan_lo
+    tan_hi = getattr(image, "tan_hi", carve_mod.CARVE_DEFAULTS["tan_hi"]) if tan_hi is None else tan_hi
+    return carve_mod.check_image(int(shape[0]), int(shape[1]), tan_lo, tan_hi) + carve_mod.check_rule(
+        win_rows, win_cols, margin_abs, margin_rel, max_range, grace)
 
 
 def _check_register(iters, tol_t, tol_r):
@@ -264,6 +302,7 @@ class VoxelMapRef:
         self.rows = np.zeros((0, 4), np.float32)
         self.counters = dict.fromkeys(COUNTERS, 0)
         self.prune_counters = dict.fromkeys(PRUNE_COUNTERS, 0)
+        self.carve_counters = dict.fromkeys(CARVE_COUNTERS, 0)
 
     def _cells(self, points, pose):
         """-> (status [P]: 0 accepted, 1 skipped, 2 out of range; key [P] int64; world [P, 3] float64)"""
@@ -377,6 +416,43 @@ class VoxelMapRef:
 
     def prune_stats(self):
         return dict(self.prune_counters)
+
+    def carve_mask(self, image, pose, tan_lo=None, tan_hi=None, win_rows=1, win_cols=1, margin_abs=0.3, margin_rel=0.0,
+                   max_range=60.0, grace=1):
+        """bool, one per stored cell in the order of the cell arrays: the cells carve() would evict (module docstring);
+        image: uint32 [H, W] (carve.range_image_ref)."""
+        from . import carve as carve_mod
+        H, W, tan_lo, tan_hi, win_rows, win_cols, margin_abs, margin_rel, max_range, grace = check_carve_call(
+            image, tan_lo, tan_hi, win_rows, win_cols, margin_abs, margin_rel, max_range, grace)
+        img = np.ascontiguousarray(np.asarray(image)).view(np.uint32).reshape(H, W)
+        pose = np.asarray(pose, dtype=np.float64).reshape(7)
+        with np.errstate(all="ignore"):
+            old = (self.counters["n_scans"] - 1 - (self.tags >> 32)) >= grace
+            d = self.rows[:, :3].astype(np.float64) - pose[None, :3]
+            qc = np.array([pose[3], -pose[4], -pose[5], -pose[6]])
+            p = se3.rotate(qc, d)
+            rho2 = p[:, 0] * p[:, 0] + p[:, 1] * p[:, 1]
+            r_m = np.sqrt(rho2 + p[:, 2] * p[:, 2])
+            in_view = (rho2 > 0.0) & (r_m < max_range)
+            has, row, col = carve_mod.pixel_ref(p, H, W, tan_lo, tan_hi)
+            in_view &= has
+            observed = img[row, col] != carve_mod.EMPTY
+            m = carve_mod.window_min_ref(img, row, col, win_rows, win_cols)
+            through = (m.view(np.float32).astype(np.float64) - r_m) > (margin_abs + margin_rel * r_m)
+        return old & in_view & observed & through
+
+    def carve(self, image, pose, **kw):
+        """Evict the cells the scan behind `image` sees through from `pose` (module docstring), then rebuild like prune:
+        the sorted arrays are filtered."""
+        evict = self.carve_mask(image, pose, **kw)
+        keep = ~evict
+        self.carve_counters["n_carves"] += 1
+        self.carve_counters["n_carved"] += int(evict.sum())
+        self.keys, self.tags, self.hits, self.rows = self.keys[keep], self.tags[keep], self.hits[keep], self.rows[keep]
+        self.counters["n_cells"] = len(self.keys)
+
+    def carve_stats(self):
+        return dict(self.carve_counters)
 
     def _match(self, points, pose, max_dist, min_hits):
         """-> (world [P, 3] float64, index [P] into the cell arrays (-1: no match), d2 [P] (-1.0: no match))"""
@@ -654,6 +730,26 @@ class VoxelMap:
         vals = self._buf[capi.MAP_HDR_PRUNE:capi.MAP_HDR_PRUNE + len(PRUNE_COUNTERS)].tolist()
         return dict(zip(PRUNE_COUNTERS, (int(v) for v in vals)))
 
+    def carve(self, image, pose, tan_lo=None, tan_hi=None, win_rows=1, win_cols=1, margin_abs=0.3, margin_rel=0.0,
+              max_range=60.0, grace=1):
+        """Evict the cells that the scan behind `image` sees through from `pose` (module docstring).  image: a
+        carve.RangeImage, or its int32 CUDA [H, W] tensor with tan_lo= / tan_hi=; pose: a float64 CUDA [7] tensor is read
+        in place (a trajectory row), anything else is copied.  Enqueued on the current stream, five launches; no host
+        read, and nothing allocated after reserve_prune() (the rebuild shares prune's workspace) when the pose is a
+        device tensor: capturable."""
+        from rslo_amd import capi
+        _, _, tan_lo, tan_hi, win_rows, win_cols, margin_abs, margin_rel, max_range, grace = check_carve_call(
+            image, tan_lo, tan_hi, win_rows, win_cols, margin_abs, margin_rel, max_range, grace)
+        self.reserve_prune()
+        capi.map_carve(self._buf, self._prune_ws, getattr(image, "img", image), tan_lo, tan_hi, self._pose(pose), win_rows,
+                       win_cols, margin_abs, margin_rel, max_range, grace)
+
+    def carve_stats(self):
+        """{n_carves, n_carved} of the map's header (one host read)."""
+        from rslo_amd import capi
+        vals = self._buf[capi.MAP_HDR_CARVE:capi.MAP_HDR_CARVE + len(CARVE_COUNTERS)].tolist()
+        return dict(zip(CARVE_COUNTERS, (int(v) for v in vals)))
+
     def points(self, min_hits=1, center=None, radius=None, sort=True):
         """(rows [M, 4] fp32, tags [M] int64, hits [M] int32) of the cells with hits >= min_hits, and within radius of
         center when one is given (a sequence, or a float64 CUDA [3] tensor).  One host read (M).  sort=True orders by tag:
@@ -693,6 +789,10 @@ class VoxelMap:
 DEFAULT_ROBUST_FACTOR = 0.5
 
 
+_CARVE_KW = (("tan_lo", None), ("tan_hi", None), ("win_rows", 1), ("win_cols", 1), ("margin_abs", 0.3), ("margin_rel", 0.0),
+             ("max_range", 60.0), ("grace", 1))      # carve's keywords and defaults, in check_carve_call's order
+
+
 class _PyramidBase:
     """What MapPyramidRef and MapPyramid share: a list of maps, coarse to fine, that receive the same calls."""
 
@@ -718,6 +818,17 @@ class _PyramidBase:
 
     def prune_stats(self):
         return self._each("prune_stats")
+
+    def carve(self, image, pose, **kw):
+        """the one image carves every level (MapPyramid: the pose is copied to the device once, if need be)"""
+        check_carve_call(image, *[kw.get(k, d) for k, d in _CARVE_KW])      # before any level is written
+        self._each("carve", image, self._carve_pose(pose), **kw)
+
+    def _carve_pose(self, pose):
+        return pose
+
+    def carve_stats(self):
+        return self._each("carve_stats")
 
     def points(self, *args, **kw):
         return self.levels[-1].points(*args, **kw)
@@ -801,6 +912,9 @@ class MapPyramid(_PyramidBase):
         if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
             center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(-1)[:3].copy()).to(self.device)
         self._each("prune", center, radius, min_hits, grace)
+
+    def _carve_pose(self, pose):
+        return self.levels[-1]._pose(pose)
 
     def register(self, points, pose, schedule=None, metric=None, min_hits=1, damping=0.0, min_pairs=50, tol_t=0.0,
                  tol_r=0.0, info=None):

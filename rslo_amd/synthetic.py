@@ -36,8 +36,10 @@ def _rays(n_az, n_el, yaw):
 
 
 def scan(n_az=2083, n_el=64, pose_xy=(0.0, 0.0), yaw=0.0, scan_seed=0, world_seed=123, h=SENSOR_H,
-         with_features=True):
-    """One scan in the sensor frame.  Returns [P,7] float32 (or [P,3] if not with_features)."""
+         with_features=True, extra_boxes=None):
+    """One scan in the sensor frame.  Returns [P,7] float32 (or [P,3] if not with_features).  extra_boxes: axis-aligned
+    boxes (cx, cy, sx, sy, sz) standing on the ground, in world coordinates, ray-cast after the world's own (a vehicle
+    that is there in one scan and gone in the next); None: the world alone."""
     d_s, d = _rays(n_az, n_el, yaw)
     n = len(d)
     o = np.array([pose_xy[0], pose_xy[1], 0.0])
@@ -60,9 +62,11 @@ def scan(n_az=2083, n_el=64, pose_xy=(0.0, 0.0), yaw=0.0, scan_seed=0, world_see
             ok = (tw > 0) & (px >= x0) & (px < x0 + 10) & (pz > -h) & (pz < top) & (tw < t)
             t = np.where(ok, tw, t)
             nrm[ok] = (0.0, -float(ysign), 0.0)
+    boxes = []
     for _ in range(40):
         cx, cy = w.uniform(-60, 60), w.uniform(-7, 7)
-        sx, sy, sz = w.uniform(1.5, 4.5), w.uniform(1.5, 2), w.uniform(1.3, 2)
+        boxes.append((cx, cy, w.uniform(1.5, 4.5), w.uniform(1.5, 2), w.uniform(1.3, 2)))
+    for cx, cy, sx, sy, sz in boxes + [tuple(float(v) for v in b) for b in (extra_boxes or ())]:
         lo = np.array([cx - sx / 2, cy - sy / 2, -h]) - o
         hi = np.array([cx + sx / 2, cy + sy / 2, -h + sz]) - o
         inv = 1 / np.where(np.abs(d) > 1e-9, d, 1e-9)

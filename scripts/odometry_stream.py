@@ -83,6 +83,14 @@ ones: pose error before / after for each (the network of this script is untraine
 reports measure it), with the distance of the skewed and of the de-skewed points from the original ones.  The kernel
 alone under device events, and the runner with and without deskew= in this one process, plain and with the surfel stage
 (--seed must be the drive's).
+--carve [--carve-scans 40]: free-space carving (rslo_amd.carve, csrc/carve.hip), a report of its own that needs no network
+and returns before the loops above: a drive of --carve-scans scans of the synthetic world in which a vehicle-sized box
+(synthetic.scan(extra_boxes=...)) drives 12..20 m ahead of the sensor for the first half and is then gone.  The map is
+filled under the drive's true poses without and with VoxelMap.carve in front of every insert (the defaults of
+carve.CARVE_DEFAULTS): the cells inside the swept volume of the box at the end, with and without, and the share of all
+OTHER cells that carving removed.  Then, on the uncarved table at --map-capacity: the device-event time of RangeImage, of
+VoxelMap.carve and of VoxelMap.prune (60 m about the last pose), carve and prune alternated on a table restored from a
+snapshot before every call, median / min / max of 11; and the same two as calls that evict nothing.
 --launches: launches per scan of the runner from the kernel statistics of two rocprofv3 runs of different lengths
 (their difference: warm-up, capture and set-up cancel), and the kernels per scan that are not hand-written ones."""
 import argparse
@@ -110,6 +118,137 @@ def make_scans(n, seed, workers):
     import multiprocessing as mp
     with mp.get_context("spawn").Pool(workers) as pool:
         return pool.map(_scan, [(i, seed) for i in range(n)])
+
+
+CARVE_BOX = (4.2, 1.8, 1.5)      # a vehicle: length, width, height in metres
+
+
+def _carve_box(i, n, seed):
+    """(cx, cy, sx, sy, sz) of the vehicle in front of scan i of the --carve drive, or None once it is gone: 12 m ahead of
+    the sensor at scan 0, 20 m at the last scan of the first half (axis-aligned: the drive's heading stays within degrees)"""
+    import math
+    from rslo_amd import synthetic
+    half = n // 2
+    if i >= half:
+        return None
+    p = synthetic.sequence_pose(i, seed)
+    yaw = 2.0 * math.atan2(p[6], p[3])
+    d = 12.0 + 8.0 * i / max(1, half - 1)
+    return (p[0] + d * math.cos(yaw), p[1] + d * math.sin(yaw)) + CARVE_BOX
+
+
+def _carve_scan(a):
+    import math
+    from rslo_amd import synthetic
+    i, n, seed = a
+    p = synthetic.sequence_pose(i, seed)
+    box = _carve_box(i, n, seed)
+    return synthetic.scan(pose_xy=(p[0], p[1]), yaw=2.0 * math.atan2(p[6], p[3]), scan_seed=7 * seed + 3 * i + 1,
+                          extra_boxes=None if box is None else [box])
+
+
+def carve_report(args):
+    """--carve (module docstring)"""
+    import numpy as np
+    import torch
+    import rslo_amd  # noqa: F401
+    from rslo_amd import carve, mapping, synthetic
+    n, seed = args.carve_scans, args.seed
+    t0 = time.time()
+    jobs = [(i, n, seed) for i in range(n)]
+    if args.workers <= 1:
+        clouds = [_carve_scan(j) for j in jobs]
+    else:
+        import multiprocessing as mp
+        with mp.get_context("spawn").Pool(args.workers) as pool:
+            clouds = pool.map(_carve_scan, jobs)
+    out = {"metric": "odometry_stream_carve", "scans": n, "seed": seed, "scan_generation_s": round(time.time() - t0, 1),
+           "points_per_scan": int(sum(len(c) for c in clouds) / n), "box": list(CARVE_BOX), "map_voxel": args.map_voxel,
+           "map_capacity": args.map_capacity,
+           "carve": {k: (round(v, 6) if isinstance(v, float) else v) for k, v in carve.CARVE_DEFAULTS.items()}}
+    dev = torch.device("cuda", 0)
+    scans = [torch.from_numpy(c).to(dev) for c in clouds]
+    true = [torch.from_numpy(synthetic.sequence_pose(i, seed)).to(dev) for i in range(n)]
+    boxes = [b for b in (_carve_box(i, n, seed) for i in range(n)) if b is not None]
+    opts = {k: carve.CARVE_DEFAULTS[k] for k in ("win_rows", "win_cols", "margin_abs", "margin_rel", "max_range", "grace")}
+    ri = carve.RangeImage(device=dev)
+
+    def fill(carving):
+        vmap = mapping.VoxelMap(args.map_voxel, args.map_capacity, dev, min_range=2.5, max_range=80.0)
+        vmap.reserve(max(s.shape[0] for s in scans))
+        vmap.reserve_prune()
+        for s, p in zip(scans, true):
+            if carving:
+                vmap.carve(ri(s), p, **opts)
+            vmap.insert(s, p)
+        return vmap
+
+    def in_swept_volume(rows):
+        """the cells a box ever covered, above the road surface (the ground under the box is static)"""
+        inside = np.zeros((len(rows),), bool)
+        for cx, cy, sx, sy, sz in boxes:
+            inside |= ((np.abs(rows[:, 0] - cx) <= sx / 2 + 0.1) & (np.abs(rows[:, 1] - cy) <= sy / 2 + 0.1)
+                       & (rows[:, 2] > -synthetic.SENSOR_H + 0.25) & (rows[:, 2] <= -synthetic.SENSOR_H + sz + 0.1))
+        return inside
+
+    plain, carved = fill(False), fill(True)
+    rows_p, rows_c = plain.points()[0].cpu().numpy(), carved.points()[0].cpu().numpy()
+    tp, tc = in_swept_volume(rows_p), in_swept_volume(rows_c)
+    out["cells_plain"], out["cells_carved"] = len(rows_p), len(rows_c)
+    out["swept_cells_plain"], out["swept_cells_carved"] = int(tp.sum()), int(tc.sum())
+    out["other_cells_plain"], out["other_cells_carved"] = int((~tp).sum()), int((~tc).sum())
+    out["other_cells_removed_share"] = round(1.0 - float((~tc).sum()) / float((~tp).sum()), 5)
+    out["carve_stats"], out["carved_map_stats"], out["plain_map_stats"] = carved.carve_stats(), carved.stats(), plain.stats()
+    out["carved_map_n_lost"] = carved.prune_stats()["n_lost"]
+
+    # the calls alone, on the uncarved table: restored from a snapshot in front of every timed call
+    snapshot = plain._buf.clone()
+    last, reps = n - 1, 11
+
+    def timed(fn, restore=True):
+        if restore:
+            plain._buf.copy_(snapshot)
+        return device_ms(lambda _: fn(), 1)
+
+    def spread(ms):
+        ms = sorted(ms)
+        return {"median": round(ms[len(ms) // 2], 4), "min": round(ms[0], 4), "max": round(ms[-1], 4)}
+
+    do_image = lambda: ri(scans[last])
+    do_carve = lambda: plain.carve(ri, true[last], **dict(opts, grace=0))      # grace 0: the whole table is eligible
+    do_prune = lambda: plain.prune(true[last], 60.0)
+    for fn in (do_image, do_carve, do_prune):      # first launches
+        timed(fn)
+    image_ms, carve_ms, prune_ms = [], [], []
+    for _ in range(reps):
+        image_ms.append(timed(do_image, restore=False))
+        carve_ms.append(timed(do_carve))
+        prune_ms.append(timed(do_prune))
+    plain._buf.copy_(snapshot)
+    before = plain.stats()["n_cells"]
+    do_carve()
+    out["timed_carve_evicts"] = before - plain.stats()["n_cells"]
+    plain._buf.copy_(snapshot)
+    do_prune()
+    out["timed_prune_evicts"] = before - plain.stats()["n_cells"]
+    out["timed_table_cells"], out["timed_table_load"] = before, round(before / float(args.map_capacity), 4)
+    out["range_image_ms"], out["carve_ms"], out["prune_ms"] = spread(image_ms), spread(carve_ms), spread(prune_ms)
+    out["carve_over_prune"] = round(out["carve_ms"]["median"] / out["prune_ms"]["median"], 3)
+    # calls that evict nothing, on the table the carve above left (a second carve from the same pose finds nothing new)
+    plain._buf.copy_(snapshot)
+    do_carve()
+    noop_carve, noop_prune = [], []
+    for _ in range(reps):
+        noop_carve.append(timed(do_carve, restore=False))
+        noop_prune.append(timed(lambda: plain.prune(true[last], float("inf")), restore=False))
+    out["carve_no_evict_ms"], out["prune_no_evict_ms"] = spread(noop_carve), spread(noop_prune)
+    # the contended image: every point in one pixel, beside a scan's spread of the same size
+    P = scans[last].shape[0]
+    one = torch.zeros((P, 3), dtype=torch.float32, device=dev)
+    one[:, 0] = torch.linspace(30.0, 5.0, P, device=dev)
+    ri(one)
+    out["range_image_one_pixel_ms"] = spread([device_ms(lambda _: ri(one), 1) for _ in range(reps)])
+    return out
 
 
 def _kernel_counts(path):
@@ -226,6 +365,9 @@ def main():
                          "(default: the radius)")
     ap.add_argument("--deskew", action="store_true",
                     help="also de-skew a skewed twin of the drive and run the runner with deskew=")
+    ap.add_argument("--carve", action="store_true",
+                    help="the free-space carving report alone: a box drives ahead of the sensor and is then gone")
+    ap.add_argument("--carve-scans", type=int, default=40, help="scans of the --carve drive")
     ap.add_argument("--out", default=None)
     ap.add_argument("--launches", nargs=2, default=None)
     ap.add_argument("--scans-a", type=int, default=20)
@@ -240,6 +382,13 @@ def main():
     if args.launches:
         res = launches(args.launches[0], args.launches[1], args.scans_a, args.scans_b)
         line = json.dumps(res)
+        print(line)
+        if args.out:
+            with open(args.out, "w") as f:
+                f.write(line + "\n")
+        return
+    if args.carve:
+        line = json.dumps(carve_report(args))
         print(line)
         if args.out:
             with open(args.out, "w") as f:

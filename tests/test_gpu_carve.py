@@ -1,0 +1,428 @@
+"""Free-space carving on the GPU (csrc/carve.hip: rslo_range_image, rslo_map_carve; carve.RangeImage, VoxelMap.carve)
+against the float64 restatement on the same inputs (carve.range_image_ref, VoxelMapRef.carve), and the map an
+OdometryRunner keeps with carve=.
+
+The bar is that of tests/test_gpu_local_map.py: BIT equality with no tolerance.  The image is a minimum over bit patterns
+of float32 ranges computed in IEEE double in a fixed order, so it equals the restatement as uint32; the carve rule is a
+chain of IEEE double comparisons on stored fp32 rows, and a kept cell is copied, not recomputed, so after sorting by tag
+the rows (viewed as int32), tags, hits and every header counter are equal.
+"""
+import math
+
+import numpy as np
+import pytest
+import torch
+from stream_support import dev, network_and_scans, stream
+
+pytestmark = pytest.mark.gpu
+
+IDENT = np.array([0, 0, 0, 1, 0, 0, 0], np.float64)
+POSE_YAW = np.array([1.0, -0.5, 0.1, np.cos(0.15), 0.0, 0.0, np.sin(0.15)], np.float64)
+POSE_BACK = np.array([-1.5, 1.0, 0.05, np.cos(0.1), 0.0, 0.0, -np.sin(0.1)], np.float64)
+_q = np.array([0.98, 0.02, -0.03, 0.1])
+SENSOR = np.concatenate([[0.5, -0.3, 1.5], _q / np.linalg.norm(_q)])       # 1.5 m above the clouds' surface, slightly tilted
+SENSOR2 = np.array([-2.0, 1.0, 1.2, np.cos(0.4), 0.0, 0.0, np.sin(0.4)], np.float64)
+SPAN = dict(tan_lo=-1.0, tan_hi=0.1)                                        # the surface seen from there
+EMPTY = 0xFFFFFFFF
+_CLOUD = {}
+
+
+def _cloud(seed, n=4000):
+    from rslo_amd import synthetic
+    if (seed, n) not in _CLOUD:
+        _CLOUD[(seed, n)] = synthetic.small_cloud(n, seed=seed)
+    return _CLOUD[(seed, n)]
+
+
+def _seen_from(pose, seed, drop=0.8, n=4000):
+    """a scan in the frame of the sensor at `pose`: the surface of small_cloud(seed), lowered by `drop` metres where
+    x > 0 -- there the sensor looks through the cells of a map of the surface, elsewhere it sees them"""
+    from rslo_amd import se3
+    w = _cloud(seed, n)[:, :3].astype(np.float64)
+    w[:, 2] -= np.where(w[:, 0] > 0.0, drop, 0.0)
+    out = np.zeros((n, 4), np.float32)
+    out[:, :3] = se3.rotate(se3.qconj(pose[3:]), w - pose[None, :3]).astype(np.float32)
+    return out
+
+
+def _image_pair(scan, rows, cols, tan_lo, tan_hi):
+    """(device RangeImage, host uint32 image) of one scan, asserted equal"""
+    from rslo_amd import carve
+    ri = carve.RangeImage(rows, cols, tan_lo, tan_hi)
+    ri(dev(scan))
+    want = carve.range_image_ref(scan, rows, cols, tan_lo, tan_hi)
+    assert (ri.numpy() == want).all()
+    return ri, want
+
+
+def _got(vmap):
+    rows, tags, hits = vmap.points()
+    return rows.cpu().numpy(), tags.cpu().numpy(), hits.cpu().numpy()
+
+
+def _assert_same(vmap, ref, label=""):
+    rows, tags, hits = _got(vmap)
+    rrows, rtags, rhits = ref.points()
+    st, ps, cs = vmap.stats(), vmap.prune_stats(), vmap.carve_stats()
+    print("%s: cells kernel %d, reference %d; counters %s; prune %s; carve %s" % (label, len(tags), len(rtags), st, ps, cs))
+    assert st == ref.stats() and ps == ref.prune_stats() and cs == ref.carve_stats()
+    assert len(tags) == len(rtags) and (tags == rtags).all()       # the evicted set is equal
+    assert (hits == rhits).all()
+    assert rows.dtype == np.float32 and (rows.view(np.int32) == rrows.view(np.int32)).all()
+
+
+def _pair(voxel, capacity, scans):
+    from rslo_amd.mapping import VoxelMap, VoxelMapRef
+    vmap, ref = VoxelMap(voxel, capacity), VoxelMapRef(voxel)
+    for cloud, pose in scans:
+        vmap.insert(dev(cloud), pose)
+        ref.insert(cloud, pose)
+    return vmap, ref
+
+
+TWO_SCANS = lambda: ((_cloud(0), IDENT), (_cloud(5), POSE_YAW))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the range image
+# ---------------------------------------------------------------------------------------------------------------------
+def _scan_like(n, seed=11):
+    r = np.random.default_rng(seed)
+    p = np.zeros((n, 4), np.float32)
+    p[:, 0], p[:, 1] = r.uniform(-30, 30, n), r.uniform(-30, 30, n)
+    p[:, 2] = r.uniform(-0.6, 0.1, n) * np.sqrt(p[:, 0].astype(np.float64) ** 2 + p[:, 1].astype(np.float64) ** 2)
+    p[:, 3] = r.random(n)
+    return p
+
+
+@pytest.mark.parametrize("N", [0, 1, 255, 256, 257, 5000])
+@pytest.mark.parametrize("H, W", [(1, 8), (8, 24), (64, 1024)])
+def test_image_bit_for_bit(H, W, N):
+    from rslo_amd import carve
+    pts = _scan_like(5000)[:N]
+    ri, want = _image_pair(pts, H, W, carve.CARVE_DEFAULTS["tan_lo"], carve.CARVE_DEFAULTS["tan_hi"])
+    filled = int((want != EMPTY).sum())
+    print("H %d W %d N %d: %d pixels filled" % (H, W, N, filled))
+    assert filled <= N and (filled == 0) == (N == 0)
+    if N == 5000:
+        assert filled > 0.9 * H * W if H * W <= 8 * 24 else filled > 1500
+    first = ri.numpy().copy()
+    ri(dev(pts))                                               # a second call: the same bits
+    assert (ri.numpy() == first).all()
+
+
+def test_image_of_strided_inputs():
+    cloud = _seen_from(SENSOR, 7)
+    wide = np.zeros((len(cloud), 7), np.float32)
+    wide[:, :4] = cloud
+    wide[:, 4:] = 1.0e6                                        # columns the kernel must not read as coordinates
+    ri, want = _image_pair(wide, 32, 256, **SPAN)
+    assert (want != EMPTY).sum() > 1000
+    from rslo_amd import carve
+    big = np.full((len(cloud), 9), 7.0e5, np.float32)
+    big[:, 2:5] = cloud[:, :3]
+    view = dev(big)[:, 2:6]                                    # a column view: row stride 9, first column 2
+    assert view.stride(0) == 9 and not view.is_contiguous()
+    ri2 = carve.RangeImage(32, 256, **SPAN)
+    ri2(view)
+    assert (ri2.numpy() == want).all()
+
+
+def test_every_point_in_one_pixel():
+    """the contended case: 5000 atomic minima on one word"""
+    r = np.random.default_rng(3)
+    pts = np.zeros((5000, 3), np.float32)
+    pts[:, 0] = r.uniform(2.0, 30.0, 5000)
+    pts[:, 1] = pts[:, 0] * r.uniform(0.0, 1.0e-4, 5000)       # far inside the pixel's 0.35 degrees
+    ri, want = _image_pair(pts, 64, 1024, -0.5, 0.5)
+    assert (want != EMPTY).sum() == 1
+    rng = np.sqrt(pts[:, 0].astype(np.float64) ** 2 + pts[:, 1].astype(np.float64) ** 2).astype(np.float32)
+    assert int(want[32, 512]) == int(rng.min().view(np.uint32))
+
+
+def test_image_skips_non_finite_and_vertical_points():
+    pts = _scan_like(600)
+    pts[0::7, 0] = np.nan
+    pts[1::7, 1] = np.inf
+    pts[2::7, 2] = -np.inf
+    pts[3::7, :2] = 0.0                                        # vertical: rho2 == 0
+    pts[4::7, 2] = 1.0e9                                       # above the image
+    ri, want = _image_pair(pts, 16, 64, -0.7, 0.2)
+    clean = np.delete(pts, np.concatenate([np.arange(k, 600, 7) for k in range(5)]), axis=0)
+    from rslo_amd import carve
+    assert (want == carve.range_image_ref(clean, 16, 64, -0.7, 0.2)).all() and (want != EMPTY).sum() > 100
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the carve
+# ---------------------------------------------------------------------------------------------------------------------
+def _carve_both(vmap, ref, ri, want, pose, **kw):
+    vmap.carve(ri, dev(pose), **kw)
+    ref.carve(want, pose, tan_lo=ri.tan_lo, tan_hi=ri.tan_hi, **kw)
+
+
+@pytest.mark.parametrize("win", [(0, 0), (1, 1), (4, 8)])
+def test_two_scan_map(win):
+    vmap, ref = _pair(0.4, 1 << 16, TWO_SCANS())
+    ri, want = _image_pair(_seen_from(SENSOR, 7), 32, 256, **SPAN)
+    n0 = ref.stats()["n_cells"]
+    _carve_both(vmap, ref, ri, want, SENSOR, win_rows=win[0], win_cols=win[1], grace=0, max_range=40.0)
+    n_carved = ref.carve_stats()["n_carved"]
+    print("window %s: %d of %d cells carved" % (win, n_carved, n0))
+    assert n_carved > 100 and ref.stats()["n_cells"] > 1000 and vmap.prune_stats()["n_lost"] == 0
+    _assert_same(vmap, ref, "window %s" % (win,))
+    # the map lives on: a later insert creates carved cells afresh, a second carve from elsewhere counts on
+    third = _cloud(9)
+    vmap.insert(dev(third), POSE_BACK)
+    ref.insert(third, POSE_BACK)
+    ri2, want2 = _image_pair(_seen_from(SENSOR2, 3, drop=0.5), 32, 256, **SPAN)
+    _carve_both(vmap, ref, ri2, want2, SENSOR2, win_rows=win[0], win_cols=win[1], grace=1, max_range=25.0)
+    assert ref.carve_stats()["n_carves"] == 2 and ref.carve_stats()["n_carved"] > n_carved
+    _assert_same(vmap, ref, "window %s, second carve" % (win,))
+
+
+@pytest.mark.parametrize("capacity, voxel, n", [(1024, 1.0, 1000), (1 << 16, 0.4, 4000), (1 << 20, 0.4, 4000)])
+def test_capacities(capacity, voxel, n):
+    """the smallest table (probe runs wrap around its end), the issue's 2^16, and 2^20 slots: two rounds of the scan
+    pass's grid-stride loop (2048 workgroups of 256 threads take 2^19 slots per round)"""
+    vmap, ref = _pair(voxel, capacity, ((_cloud(5, n), IDENT),))
+    assert vmap.stats()["dropped_full"] == 0
+    ri, want = _image_pair(_seen_from(SENSOR, 5, n=n), 32, 256, **SPAN)      # the surface itself, lowered where x > 0
+    n0 = ref.stats()["n_cells"]
+    _carve_both(vmap, ref, ri, want, SENSOR, grace=0)
+    print("capacity %d: %d of %d cells carved" % (capacity, ref.carve_stats()["n_carved"], n0))
+    assert 50 < ref.carve_stats()["n_carved"] < n0 - 50 and vmap.prune_stats()["n_lost"] == 0
+    _assert_same(vmap, ref, "capacity %d" % capacity)
+    hits = vmap.lookup(dev(_cloud(5, n)), IDENT).cpu().numpy()
+    assert (hits == ref.lookup(_cloud(5, n), IDENT)).all() and (hits == 0).sum() > 50      # a carved cell reads 0
+
+
+def test_window_that_wraps_the_whole_image():
+    """W = 8 with win_cols = 8: every window covers every column, several times over"""
+    vmap, ref = _pair(0.4, 1 << 14, TWO_SCANS())
+    ri, want = _image_pair(_seen_from(SENSOR, 7), 4, 8, **SPAN)
+    for cols in (1, 8):
+        _carve_both(vmap, ref, ri, want, SENSOR, win_rows=1, win_cols=cols, grace=0, margin_abs=0.05)
+        _assert_same(vmap, ref, "W 8, win_cols %d" % cols)
+    assert ref.carve_stats()["n_carves"] == 2
+
+
+def test_max_range_cuts_the_map_in_two():
+    vmap, ref = _pair(0.4, 1 << 16, TWO_SCANS())
+    ri, want = _image_pair(_seen_from(SENSOR, 7), 32, 256, **SPAN)
+    far = ref.carve_mask(want, SENSOR, grace=0, max_range=float("inf"), **SPAN)
+    near = ref.carve_mask(want, SENSOR, grace=0, max_range=8.0, **SPAN)
+    assert near.sum() > 50 and (far & ~near).sum() > 50 and not (near & ~far).any()
+    _carve_both(vmap, ref, ri, want, SENSOR, grace=0, max_range=8.0)
+    assert ref.carve_stats()["n_carved"] == int(near.sum())
+    _assert_same(vmap, ref, "max_range 8")
+    _carve_both(vmap, ref, ri, want, SENSOR, grace=0, max_range=float("inf"))
+    assert ref.carve_stats()["n_carved"] == int(far.sum())
+    _assert_same(vmap, ref, "max_range inf")
+
+
+@pytest.mark.parametrize("grace", [0, 2])
+def test_grace(grace):
+    vmap, ref = _pair(0.4, 1 << 16, TWO_SCANS() + ((_cloud(9), POSE_BACK),))
+    ri, want = _image_pair(_seen_from(SENSOR, 7), 32, 256, **SPAN)
+    mask0 = ref.carve_mask(want, SENSOR, grace=0, **SPAN)
+    by_scan = [int((mask0 & (ref.tags >> 32 == s)).sum()) for s in range(3)]
+    assert min(by_scan) > 30
+    _carve_both(vmap, ref, ri, want, SENSOR, grace=grace)
+    assert ref.carve_stats()["n_carved"] == (sum(by_scan) if grace == 0 else by_scan[0])      # S = 3: only scan 0 is two old
+    _assert_same(vmap, ref, "grace %d" % grace)
+
+
+def test_nothing_carved_leaves_the_table_alone():
+    from rslo_amd import carve
+    vmap, ref = _pair(0.4, 1 << 14, TWO_SCANS())
+    ri, want = _image_pair(_seen_from(SENSOR, 7), 32, 256, **SPAN)
+    empty = carve.RangeImage(32, 256, **SPAN)
+    empty(dev(np.zeros((0, 4), np.float32)))
+    nan_pose = SENSOR.copy()
+    nan_pose[4] = np.nan
+    hdr = 256 // 8
+    before = vmap._buf.clone()
+    for n, (image, himage, pose, kw) in enumerate(((ri, want, SENSOR, dict(grace=2)),      # two scans: no cell is two old
+                                                   (ri, want, nan_pose, dict(grace=0)),
+                                                   (empty, empty.numpy(), SENSOR, dict(grace=0)),
+                                                   (ri, want, SENSOR, dict(grace=0, margin_abs=1.0e3))), 1):
+        _carve_both(vmap, ref, image, himage, pose, **kw)
+        assert torch.equal(vmap._buf[hdr:], before[hdr:])            # every slot section, to the byte
+        changed = torch.nonzero(vmap._buf[:hdr] != before[:hdr]).flatten().tolist()
+        assert changed == [14]                                       # n_carves and nothing else in the header
+        assert vmap.carve_stats() == {"n_carves": n, "n_carved": 0}
+    _assert_same(vmap, ref, "nothing carved")
+
+
+def test_determinism():
+    """two identical sequences of calls on two identical maps: the same content and the same header.  (Which slot a cell
+    occupies is unspecified -- it follows the race for slots in the insert and in the rebuild -- so the content is
+    compared in tag order, as everywhere.)"""
+    first = None
+    for _ in range(2):
+        vmap, ref = _pair(0.4, 1 << 14, TWO_SCANS())
+        ri, _ = _image_pair(_seen_from(SENSOR, 7), 32, 256, **SPAN)
+        vmap.carve(ri, dev(SENSOR), grace=0)
+        vmap.insert(dev(_cloud(9)), POSE_BACK)
+        vmap.carve(ri, dev(SENSOR2), grace=1, win_rows=2, win_cols=3)
+        got = _got(vmap), vmap._buf[:16].cpu().numpy().tobytes()      # the header's 16 words (the rest of its 256 bytes is unused)
+        assert vmap.carve_stats()["n_carves"] == 2 and vmap.carve_stats()["n_carved"] > 100
+        if first is not None:
+            assert all(a.tobytes() == b.tobytes() for a, b in zip(first[0], got[0])) and first[1] == got[1]
+        first = got
+
+
+def test_argument_errors_write_nothing():
+    from rslo_amd import capi, carve
+    lib = capi.lib()
+    vmap, ref = _pair(0.4, 2048, ((_cloud(0)[:1000], IDENT),))
+    vmap.reserve_prune()
+    ri, want = _image_pair(_seen_from(SENSOR, 7), 32, 256, **SPAN)
+    before, img_before = vmap._buf.clone(), ri.img.clone()
+    buf, ws, img, pose = vmap._buf, vmap._prune_ws, ri.img, dev(SENSOR)
+    nb, wb = buf.numel() * 8, ws.numel() * 8
+    assert wb == lib.rslo_map_carve_ws_bytes(2048) == lib.rslo_map_prune_ws_bytes(2048)
+    nan, inf = float("nan"), float("inf")
+
+    def call(H=32, W=256, lo=-1.0, hi=0.1, wr=1, wc=1, ma=0.3, mr=0.0, rng=60.0, grace=1, i=img.data_ptr(),
+             p=pose.data_ptr(), w=ws.data_ptr(), w_bytes=wb, m_bytes=nb):
+        return lib.rslo_map_carve(buf.data_ptr(), m_bytes, i, H, W, lo, hi, p, wr, wc, ma, mr, rng, grace, w, w_bytes, None)
+
+    rcs = [call(H=0), call(H=257), call(W=7), call(W=4097), call(lo=0.1, hi=0.1), call(lo=nan), call(hi=inf), call(wr=-1),
+           call(wr=5), call(wc=9), call(ma=-0.1), call(mr=nan), call(rng=0.0), call(rng=nan), call(grace=-1), call(i=None),
+           call(p=None), call(w=None), call(w=ws.data_ptr() + 8, w_bytes=wb - 8), call(m_bytes=1000)]
+    ews = call(w_bytes=wb - 16)
+    print("return codes:", rcs, ews, lib.rslo_last_error().decode())
+    assert all(rc == rcs[0] != 0 for rc in rcs) and ews not in (0, rcs[0])
+    pts = dev(_cloud(0))
+
+    def image(H=32, W=256, lo=-1.0, hi=0.1, stride=7, N=100, p=pts.data_ptr(), i=img.data_ptr()):
+        return lib.rslo_range_image(p, stride, N, H, W, lo, hi, i, None)
+
+    rcs = [image(H=0), image(H=257), image(W=7), image(W=4097), image(lo=0.2, hi=0.1), image(lo=-inf), image(hi=nan),
+           image(stride=2), image(N=-1), image(p=None), image(i=None)]
+    print("return codes:", rcs, lib.rslo_last_error().decode())
+    assert all(rc == rcs[0] != 0 for rc in rcs)
+    for kw in (dict(win_rows=5), dict(win_cols=-1), dict(margin_abs=nan), dict(max_range=-1.0), dict(grace=-1),
+               dict(tan_lo=0.5, tan_hi=0.5)):
+        with pytest.raises(ValueError):
+            vmap.carve(ri, pose, **kw)
+    with pytest.raises(ValueError):
+        carve.RangeImage(300, 256)
+    with pytest.raises(capi.RsloHipError):
+        vmap.carve(ri.img.to(torch.int64), pose, **SPAN)             # not the image's type
+    with pytest.raises(capi.RsloHipError):
+        ri(torch.zeros((10, 2), dtype=torch.float32, device="cuda"))
+    torch.cuda.synchronize()
+    assert torch.equal(vmap._buf, before) and torch.equal(ri.img, img_before)
+    _assert_same(vmap, ref, "after refused calls")
+
+
+def test_capture_and_replay():
+    """image + carve captured once; replayed under two scans and two poses copied into the static tensors"""
+    from rslo_amd import carve
+    from rslo_amd.mapping import VoxelMap
+    views = [(_seen_from(SENSOR, 7), SENSOR), (_seen_from(SENSOR2, 3, drop=0.5), SENSOR2)]
+    warm = VoxelMap(0.4, 1 << 14)                   # the kernels' first launches, outside the capture
+    warm.insert(dev(_cloud(0)), IDENT)
+    warm.carve(carve.RangeImage(32, 256, **SPAN)(dev(views[0][0])), dev(SENSOR))
+    vmap, ref = _pair(0.4, 1 << 14, TWO_SCANS())
+    vmap.reserve_prune()
+    ri = carve.RangeImage(32, 256, **SPAN)
+    static_pts = torch.zeros((4000, 4), dtype=torch.float32, device="cuda")
+    static_pose = torch.zeros(7, dtype=torch.float64, device="cuda")
+    on_dev = [(dev(s), dev(p)) for s, p in views]
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        vmap.carve(ri(static_pts), static_pose, grace=0, max_range=30.0)
+    assert vmap.carve_stats()["n_carves"] == 0      # captured, not run
+    torch.cuda.synchronize()
+    mem = torch.cuda.memory_allocated()
+    for k, (s, p) in enumerate(on_dev):
+        static_pts.copy_(s)
+        static_pose.copy_(p)
+        g.replay()
+        torch.cuda.synchronize()
+        assert torch.cuda.memory_allocated() == mem
+        want = carve.range_image_ref(views[k][0], 32, 256, **SPAN)
+        assert (ri.numpy() == want).all()
+        carved = ref.carve_stats()["n_carved"]
+        ref.carve(want, views[k][1], grace=0, max_range=30.0, **SPAN)
+        assert ref.carve_stats()["n_carved"] > carved + 50
+        _assert_same(vmap, ref, "replay %d" % k)
+
+
+def test_pyramid_carves_every_level():
+    from rslo_amd.mapping import MapPyramid, MapPyramidRef
+    pyr, ref = MapPyramid((0.8, 0.4), 1 << 14), MapPyramidRef((0.8, 0.4))
+    for cloud, pose in TWO_SCANS():
+        pyr.insert(dev(cloud), pose)
+        ref.insert(cloud, pose)
+    ri, want = _image_pair(_seen_from(SENSOR, 7), 32, 256, **SPAN)
+    pyr.carve(ri, SENSOR, grace=0)                  # a host pose: copied to the device once
+    ref.carve(want, SENSOR, grace=0, **SPAN)
+    assert pyr.carve_stats() == ref.carve_stats() and all(s["n_carved"] > 50 for s in ref.carve_stats())
+    for k, (lvl, rlvl) in enumerate(zip(pyr.levels, ref.levels)):
+        _assert_same(lvl, rlvl, "level %d" % k)
+    with pytest.raises(ValueError):
+        pyr.carve(ri, SENSOR, win_cols=9)
+    assert pyr.carve_stats() == ref.carve_stats()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the runner
+# ---------------------------------------------------------------------------------------------------------------------
+N_SCANS = 4
+MAP_ARGS = dict(voxel_size=0.2, capacity=1 << 21, min_range=2.5, max_range=80.0)
+CARVE = dict(every=2, max_range=40.0)      # the defaults otherwise
+
+
+def test_runner_carves_in_front_of_the_insert():
+    from rslo_amd import capi, carve, inference
+    from rslo_amd.mapping import VoxelMap, VoxelMapRef
+    net, scans = network_and_scans(21, 3, N_SCANS)
+    plain = inference.OdometryRunner(net)
+    try:
+        rel0, traj0 = stream(plain, scans)
+    finally:
+        plain.close()
+    for bad in (dict(every=0), dict(evry=2), dict(rows=0), dict(win_cols=9), dict(max_range=float("nan"))):
+        with pytest.raises((capi.RsloHipError, ValueError)):
+            inference.OdometryRunner(net, voxel_map=VoxelMap(0.2, 1024), carve=bad)
+    with pytest.raises(capi.RsloHipError):
+        inference.OdometryRunner(net, carve=CARVE)               # needs a voxel_map
+    # The untrained network's poses do not place its own scans where they overlap (stream_support.seed_poses): among
+    # them alone the rule evicts nothing.  Ghosts give the carve something to find (as stream_support.seed_poses does for the registration): a copy of every
+    # scan shrunk to 0.7 of its range, put into the map where the chain will place that scan -- the scan then looks
+    # straight through its ghost.  The ghosts are scans 0 .. N-1 of the map, so they are old enough for any grace here.
+    ghosts = [s.clone() for s in scans]
+    for g in ghosts:
+        g[:, :3] *= 0.7
+    vmap = VoxelMap(**MAP_ARGS)
+    runner = inference.OdometryRunner(net, voxel_map=vmap, carve=CARVE)
+    try:
+        assert vmap._prune_ws is not None                        # reserved by the constructor
+        o = runner.carve
+        assert (o["rows"], o["cols"], o["grace"], o["every"], o["max_range"]) == (64, 1024, 1, 2, 40.0)
+        ref = VoxelMapRef(MAP_ARGS["voxel_size"], MAP_ARGS["min_range"], MAP_ARGS["max_range"])
+        for g, pose in zip(ghosts, traj0):
+            vmap.insert(g, pose)
+            ref.insert(g.cpu().numpy(), pose)
+        n_ghost = ref.stats()["n_cells"]
+        rel, traj = stream(runner, scans)
+        assert rel.tobytes() == rel0.tobytes() and traj.tobytes() == traj0.tobytes()      # carving disturbs no pose
+        for n, (s, pose) in enumerate(zip(scans, traj)):
+            host = s.cpu().numpy()
+            if (n + 1) % CARVE["every"] == 0:
+                ref.carve(carve.range_image_ref(host), pose, max_range=CARVE["max_range"])
+            ref.insert(host, pose)
+        print("runner: %d ghost cells, carve %s, cells %d" % (n_ghost, ref.carve_stats(), ref.stats()["n_cells"]))
+        assert ref.carve_stats()["n_carves"] == N_SCANS // 2 and 1000 < ref.carve_stats()["n_carved"] < n_ghost
+        assert ref.stats()["n_cells"] > 10000
+        _assert_same(vmap, ref, "runner, carve")
+        assert vmap.stats()["dropped_full"] == 0 and vmap.prune_stats()["n_lost"] == 0
+        assert (runner._range_image.numpy() == carve.range_image_ref(scans[-1].cpu().numpy())).all()
+    finally:
+        runner.close()
