@@ -1478,6 +1478,37 @@ RSLO_API int rslo_loop_emit(const double *out /*[top_k,16]*/, int top_k, const v
  * Register (rslo_surfel_register): the rules of rslo_map_register_w with the normal equations above: the step, damping,
  * min_pairs, tol_t / tol_r, statuses 0..3, info rows [iters, 8], 2 launches per iteration and 1 for N == 0.
  *
+ * Distribution cost (rslo_surfel_nearest_d, rslo_surfel_normal_eq_d, rslo_surfel_register_d): the point-to-distribution
+ * (NDT) form.  The matched cell's covariance -- already in the table as integers -- weighs the whole residual
+ * d = w - mean, so the fitted cells that fail the planar test (poles, trunks, kerbs, vegetation) take part.
+ *   Candidates: the cells c + {-1,0,1}^3 whose row flag is >= min_flag, min_flag in {1, 2}.  The winner is chosen as in
+ *   "Nearest" (smallest d2 to the row's mean, then smallest key) and accepted iff d2 < max_dist*max_dist.  With
+ *   min_flag = 2 keys and d2 are those of rslo_surfel_nearest.
+ *   Information matrix of the matched slot from its ten moments (N, S_a, S_ab): n = double(N); mu_a = double(S_a) / n;
+ *   c_ab = double(S_ab) / n - mu_a * mu_b in the order 00 01 02 11 12 22 (the expressions of "Derive");
+ *   u = voxel / 16384.0; C_ab = (c_ab * u) * u; lam = reg_rel * ((C00 + C11) + C22) + reg_abs * reg_abs;
+ *   S = C + lam I (S_aa = C_aa + lam, the off-diagonal entries are C's);
+ *     A00 = S11*S22 - S12*S12    A01 = S02*S12 - S01*S22    A02 = S01*S12 - S02*S11
+ *     A11 = S00*S22 - S02*S02    A12 = S01*S02 - S00*S12    A22 = S00*S11 - S01*S01
+ *   det = (S00*A00 + S01*A01) + S02*A02; M_ab = A_ab / det.  The grid is axis-aligned: M is in the world frame.
+ *   reg_rel and reg_abs are >= 0, finite and not both zero.
+ *   Unusable pair: a pair whose det fails det > 0 && det < inf adds nothing and is not counted.
+ *   Term of a used pair, with J = [I | -[w]x] (the rows of the point term of "Scan-to-map registration") and d = w - mean:
+ *     m_a = M_a0*d0 + M_a1*d1 + M_a2*d2;  e = d0*m0 + d1*m1 + d2*m2;
+ *     B[a][k] = M_a0*J[0][k] + M_a1*J[1][k] + M_a2*J[2][k];
+ *     H(k, l) += J[0][k]*B[0][l] + J[1][k]*B[1][l] + J[2][k]*B[2][l] for k <= l;
+ *     g_k += J[0][k]*m0 + J[1][k]*m1 + J[2][k]*m2;  cost += e.
+ *   The residual is dimensionless (sigmas), and so is robust_scale: rho = u*u, u = s2 / (s2 + e), s2 = scale*scale, on the
+ *   28 addends, as "Robust weight"; 0 means no weights.
+ *   rslo_surfel_nearest_d: keys_out, d2_out, rows_out as rslo_surfel_nearest; info_out double [N, 8] or NULL: the row
+ *   {M00, M01, M02, M11, M12, M22, det, lam} of the matched cell, zeros without a match; for an unusable pair the six
+ *   M entries are zeros (det and lam are written as computed).  The table is read-only.
+ *   rslo_surfel_normal_eq_d / rslo_surfel_register_d: out29, the two-stage reduction, the step, statuses 0..3, the
+ *   converged flag, info rows {status, pairs, cost, |dt|, theta, 0, 0, 0}, the workspace
+ *   (rslo_surfel_register_ws_bytes(N)) and the launch counts (2 per iteration, 1 for N == 0) are those of
+ *   rslo_surfel_normal_eq / rslo_surfel_register.  Errors are those of the plane calls, plus RSLO_EINVAL for min_flag
+ *   outside {1, 2} and for reg_rel / reg_abs that break the rule above (NaN included).
+ *
  * Rolling local surfel map (rslo_surfel_prune): the one call that removes surfel cells.  A cell carries no creation
  * scan and the slot layout does not change (156 bytes per slot), so the rule uses only the key, the count
  * N = moments[0], the header's voxel and the arguments.  For a stored cell, cell_a is unpacked from the key (3 x 21
@@ -1548,6 +1579,19 @@ RSLO_API int rslo_surfel_register(const void *map, size_t map_bytes, double voxe
                                   int stride_floats, int N, double *pose7, int iters, double max_dist, double damping,
                                   int min_pairs, double tol_t, double tol_r, double robust_scale, double *info /*[iters,8]*/,
                                   void *ws, size_t ws_bytes, void *stream);
+RSLO_API int rslo_surfel_nearest_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                   int stride_floats, int N, const double *pose7, double max_dist, int min_flag,
+                                   double reg_rel, double reg_abs, int64_t *keys_out, double *d2_out,
+                                   double *rows_out /*[N,8] or NULL*/, double *info_out /*[N,8] or NULL*/, void *stream);
+RSLO_API int rslo_surfel_normal_eq_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                     int stride_floats, int N, const double *pose7, double max_dist, int min_flag,
+                                     double reg_rel, double reg_abs, double robust_scale, double *out29, void *ws,
+                                     size_t ws_bytes, void *stream);
+RSLO_API int rslo_surfel_register_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                    int stride_floats, int N, double *pose7, int iters, double max_dist, double damping,
+                                    int min_pairs, double tol_t, double tol_r, double robust_scale, int min_flag,
+                                    double reg_rel, double reg_abs, double *info /*[iters,8]*/, void *ws, size_t ws_bytes,
+                                    void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Scan de-skewing (csrc/deskew.hip; float64 restatement: rslo_amd/deskew.py)

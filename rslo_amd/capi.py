@@ -252,6 +252,12 @@ SIGNATURES = {
     "rslo_surfel_normal_eq": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
     "rslo_surfel_register": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, _i, C.c_double, C.c_double, _i, C.c_double,
                                        C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_surfel_nearest_d": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, _i, C.c_double, C.c_double, _vp,
+                                        _vp, _vp, _vp, _vp]),
+    "rslo_surfel_normal_eq_d": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, C.c_double, _i, C.c_double, C.c_double,
+                                          C.c_double, _vp, _vp, _sz, _vp]),
+    "rslo_surfel_register_d": (C.c_int, [_vp, _sz, C.c_double, _vp, _i, _i, _vp, _i, C.c_double, C.c_double, _i, C.c_double,
+                                         C.c_double, C.c_double, _i, C.c_double, C.c_double, _vp, _vp, _sz, _vp]),
     "rslo_deskew": (C.c_int, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_double, C.c_double, _i, C.c_double, _vp, _i, _vp,
                               _vp]),
 }
@@ -1626,6 +1632,73 @@ def surfel_register(buf, points, pose, voxel_size, iters=4, max_dist=None, dampi
                                     float(voxel_size if max_dist is None else max_dist), float(damping), int(min_pairs),
                                     float(tol_t), float(tol_r), float(robust_scale), _ptr(info, torch.float64, "info"),
                                     ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_surfel_register")
+    return info
+
+
+def surfel_nearest_d(buf, points, pose, voxel_size, max_dist=None, min_flag=1, reg_rel=0.01, reg_abs=0.02, rows=None,
+                     info=None, keys=None, d2=None):
+    """rslo_surfel_nearest_d: surfel_nearest among the cells with flag >= min_flag (1 or 2).  Returns (keys, d2[, rows]
+    [, info]): with info=True or a float64 [P, 8] tensor, the rows {M00, M01, M02, M11, M12, M22, det, lam} of the matched
+    cells' information matrices (include/rslo_hip.h "Distribution cost"), zeros without a match.  Read-only, no host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if keys is None:
+        keys = torch.empty((P,), dtype=torch.int64, device=points.device)
+    if d2 is None:
+        d2 = torch.empty((P,), dtype=torch.float64, device=points.device)
+    if rows is True:
+        rows = torch.empty((P, 8), dtype=torch.float64, device=points.device)
+    if info is True:
+        info = torch.empty((P, 8), dtype=torch.float64, device=points.device)
+    if keys.shape != (P,) or d2.shape != (P,) or any(t is not None and t.shape != (P, 8) for t in (rows, info)):
+        raise RsloHipError("surfel_nearest_d: keys and d2 must be [P], rows and info [P, 8]")
+    _chk(lib().rslo_surfel_nearest_d(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_nearest_d"),
+                                     float(voxel_size if max_dist is None else max_dist), int(min_flag), float(reg_rel),
+                                     float(reg_abs), _ptr(keys, torch.int64, "keys"), _ptr(d2, torch.float64, "d2"),
+                                     _ptr(rows, torch.float64, "rows"), _ptr(info, torch.float64, "info"), _stream()),
+         "rslo_surfel_nearest_d")
+    return (keys, d2) + tuple(t for t in (rows, info) if t is not None)
+
+
+def surfel_normal_eq_d(buf, points, pose, voxel_size, max_dist=None, min_flag=1, reg_rel=0.01, reg_abs=0.02,
+                       robust_scale=0.0, out=None, ws=None):
+    """rslo_surfel_normal_eq_d: out float64 CUDA [29] = the upper triangle of H (21), g (6), cost, pairs of the
+    distribution terms of the matches of surfel_nearest_d at pose; robust_scale > 0 (in sigmas): Geman-McClure weights.
+    No host read."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if out is None:
+        out = torch.empty((29,), dtype=torch.float64, device=points.device)
+    if out.shape != (29,):
+        raise RsloHipError("surfel_normal_eq_d: out must be [29]")
+    ws = _surfel_ws(ws, P, points.device)
+    _chk(lib().rslo_surfel_normal_eq_d(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_normal_eq_d"),
+                                       float(voxel_size if max_dist is None else max_dist), int(min_flag), float(reg_rel),
+                                       float(reg_abs), float(robust_scale), _ptr(out, torch.float64, "out"), ws.data_ptr(),
+                                       ws.numel() * ws.element_size(), _stream()), "rslo_surfel_normal_eq_d")
+    return out
+
+
+def surfel_register_d(buf, points, pose, voxel_size, iters=4, max_dist=None, damping=0.0, min_pairs=50, tol_t=0.0,
+                      tol_r=0.0, robust_scale=0.0, min_flag=1, reg_rel=0.01, reg_abs=0.02, info=None, ws=None):
+    """rslo_surfel_register_d: surfel_register with the distribution cost: pose (float64 CUDA [7]) is updated IN PLACE.
+    Returns info float64 CUDA [iters, 8] as surfel_register.  No host read, a fixed number of launches: capturable."""
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    iters = int(iters)
+    if info is None:
+        info = torch.empty((max(iters, 0), 8), dtype=torch.float64, device=points.device)
+    if info.shape != (iters, 8):
+        raise RsloHipError("surfel_register_d: info must be [iters, 8]")
+    ws = _surfel_ws(ws, P, points.device)
+    _chk(lib().rslo_surfel_register_d(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_register_d"),
+                                      iters, float(voxel_size if max_dist is None else max_dist), float(damping),
+                                      int(min_pairs), float(tol_t), float(tol_r), float(robust_scale), int(min_flag),
+                                      float(reg_rel), float(reg_abs), _ptr(info, torch.float64, "info"), ws.data_ptr(),
+                                      ws.numel() * ws.element_size(), _stream()), "rslo_surfel_register_d")
     return info
 
 

@@ -55,6 +55,37 @@ __device__ __forceinline__ void gn_plane_terms(const double *n, const double *wn
   t28[o] = r0 * r0;
 }
 
+// The 28 addends of a point-to-distribution term: the rows J = [I | -[w]x] of gn_point_terms, residual d = w - mean and
+// the symmetric information matrix M of the matched cell (M6: 00 01 02 11 12 22, world frame).  m = M d, B = M J;
+// addend of H(k, l) = J0[k]*B0[l] + J1[k]*B1[l] + J2[k]*B2[l], of g(k) = J0[k]*m0 + J1[k]*m1 + J2[k]*m2, of the cost
+// e = d0*m0 + d1*m1 + d2*m2, every sum left to right.  Assigns t28 (host twin: gauss_newton.py info_terms).
+__device__ __forceinline__ void gn_info_terms(const double *w, const double *d, const double *M6, double *t28) {
+  const double M[3][3] = {{M6[0], M6[1], M6[2]}, {M6[1], M6[3], M6[4]}, {M6[2], M6[4], M6[5]}};
+  double J[3][6], B[3][6], m[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int b = 0; b < 3; ++b) J[a][b] = a == b ? 1.0 : 0.0;
+  J[0][3] = 0.0, J[0][4] = w[2], J[0][5] = -w[1];
+  J[1][3] = -w[2], J[1][4] = 0.0, J[1][5] = w[0];
+  J[2][3] = w[1], J[2][4] = -w[0], J[2][5] = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    m[a] = M[a][0] * d[0] + M[a][1] * d[1] + M[a][2] * d[2];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) B[a][k] = M[a][0] * J[0][k] + M[a][1] * J[1][k] + M[a][2] * J[2][k];
+  }
+  int o = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+#pragma unroll
+    for (int l = k; l < 6; ++l) t28[o++] = J[0][k] * B[0][l] + J[1][k] * B[1][l] + J[2][k] * B[2][l];
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k) t28[o++] = J[0][k] * m[0] + J[1][k] * m[1] + J[2][k] * m[2];
+  t28[o] = d[0] * m[0] + d[1] * m[1] + d[2] * m[2];
+}
+
 // The workgroup's sums of the GN_NSUM values of every thread, in a fixed order: lane l takes l + 32, then + 16, ...
 // inside its wave, lane 0 leaves the wave's sums in part (LDS, [n_waves, GN_NSUM] doubles), and after a barrier thread
 // k < GN_NSUM adds the waves in wave order and writes sum k to dst[k].  Called by every thread of the workgroup; acc is

@@ -604,9 +604,11 @@ __global__ void k_surfel_prune_done(void *map, long long cap_max, const void *ws
 // ---------------------------------------------------------------------------------------------------------------------
 // The planar cell whose mean is nearest to w among the cells key + {-1,0,1}^3: slot, key and d2 of the winner (smallest
 // d2, then smallest key), d = w - mean.  The first-slot keys of all 27 chains are loaded before any is examined
-// (mapreg.hip's mr_nearest); rows are read for matching cells only.
-__device__ __forceinline__ bool sf_nearest(const SurfView &m, map_u64 key, const double *w, uint32_t &bslot, map_u64 &bkey,
-                                           double &bd2, double *d) {
+// (mapreg.hip's mr_nearest); rows are read for matching cells only.  PLANAR (the plane calls): the candidates are the
+// rows with flag 2.0 and min_flag is not read; otherwise (the distribution calls) the rows with flag >= min_flag.
+template <bool PLANAR>
+__device__ __forceinline__ bool sf_nearest(const SurfView &m, map_u64 key, const double *w, double min_flag,
+                                           uint32_t &bslot, map_u64 &bkey, double &bd2, double *d) {
   const uint32_t mask = (uint32_t)((map_u64)m.hdr->capacity - 1);      // capacity <= 2^31
   const int c[3] = {(int)(key >> 42) & 0x1fffff, (int)(key >> 21) & 0x1fffff, (int)key & 0x1fffff};
   map_u64 k0[27];
@@ -632,7 +634,7 @@ __device__ __forceinline__ bool sf_nearest(const SurfView &m, map_u64 key, const
     }
     if (k != nk) continue;
     const double *row = m.rows + (size_t)s * 8;
-    if (row[7] != 2.0) continue;
+    if (PLANAR ? row[7] != 2.0 : !(row[7] >= min_flag)) continue;
     const double dx = w[0] - row[0], dy = w[1] - row[1], dz = w[2] - row[2];
     const double d2 = dx * dx + dy * dy + dz * dz;
     if (!found || d2 < bd2 || (d2 == bd2 && nk < bkey)) {
@@ -664,7 +666,7 @@ __global__ __launch_bounds__(SF_BLOCK) void k_surfel_nearest(const void *map, lo
   const double *row = nullptr;
   if (sf_view_of(map, cap_max, voxel, m) &&
       !map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
-      sf_nearest(m, key, w, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
+      sf_nearest<true>(m, key, w, 2.0, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
     kout = (long long)bkey;
     d2 = bd2;
     row = m.rows + (size_t)s * 8;
@@ -695,7 +697,7 @@ __global__ __launch_bounds__(SF_BLOCK) void k_surfel_accum(const void *map, long
   uint32_t s;
   if (i < N && sf_view_of(map, cap_max, voxel, m)) {
     if (!map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
-        sf_nearest(m, key, w, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
+        sf_nearest<true>(m, key, w, 2.0, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
       const double *row = m.rows + (size_t)s * 8;
       const double n[3] = {row[3], row[4], row[5]};      // already in the world frame
       double wn[3];
@@ -707,6 +709,115 @@ __global__ __launch_bounds__(SF_BLOCK) void k_surfel_accum(const void *map, long
         const double rho = u * u;
 #pragma unroll
         for (int k = 0; k < GN_NSUM - 1; ++k) acc[k] = rho * acc[k];
+      }
+    }
+  }
+  gn_block_reduce(acc, part, SF_BLOCK / 64, partials + (size_t)blockIdx.x * GN_NSUM);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Distribution cost (rules: "Distribution cost"): the matched cell's covariance, regularised and inverted, weighs the
+// whole residual d = w - mean.  The candidates are the rows with flag >= min_flag.
+// ---------------------------------------------------------------------------------------------------------------------
+struct SfDist {
+  double min_flag, reg_rel, reg_abs;
+};
+
+// The information matrix M6 (00 01 02 11 12 22) of a slot from its ten moments mo: the derive pass's covariance in
+// metres plus lam on the diagonal, inverted by the adjugate.  -> whether the pair is usable (det > 0 && det < inf).
+__device__ __forceinline__ bool sf_information(const long long *__restrict__ mo, double voxel, const SfDist &dd, double *M6,
+                                               double &det, double &lam) {
+  long long q[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) q[k] = mo[k];      // the 80 contiguous bytes of the slot
+  const double n = (double)q[0];
+  const double mu0 = (double)q[1] / n, mu1 = (double)q[2] / n, mu2 = (double)q[3] / n;
+  const double c00 = (double)q[4] / n - mu0 * mu0, c01 = (double)q[5] / n - mu0 * mu1, c02 = (double)q[6] / n - mu0 * mu2;
+  const double c11 = (double)q[7] / n - mu1 * mu1, c12 = (double)q[8] / n - mu1 * mu2, c22 = (double)q[9] / n - mu2 * mu2;
+  const double u = voxel / SF_Q;
+  const double C00 = (c00 * u) * u, C01 = (c01 * u) * u, C02 = (c02 * u) * u;
+  const double C11 = (c11 * u) * u, C12 = (c12 * u) * u, C22 = (c22 * u) * u;
+  lam = dd.reg_rel * ((C00 + C11) + C22) + dd.reg_abs * dd.reg_abs;
+  const double S00 = C00 + lam, S01 = C01, S02 = C02, S11 = C11 + lam, S12 = C12, S22 = C22 + lam;
+  const double A00 = S11 * S22 - S12 * S12, A01 = S02 * S12 - S01 * S22, A02 = S01 * S12 - S02 * S11;
+  const double A11 = S00 * S22 - S02 * S02, A12 = S01 * S02 - S00 * S12, A22 = S00 * S11 - S01 * S01;
+  det = (S00 * A00 + S01 * A01) + S02 * A02;
+  M6[0] = A00 / det; M6[1] = A01 / det; M6[2] = A02 / det;
+  M6[3] = A11 / det; M6[4] = A12 / det; M6[5] = A22 / det;
+  return det > 0.0 && det < (double)__builtin_inff();
+}
+
+// info_out row = {M00, M01, M02, M11, M12, M22, det, lam} of the matched cell (M as zeros for an unusable pair)
+__global__ __launch_bounds__(SF_BLOCK) void k_surfel_nearest_d(const void *map, long long cap_max, double voxel,
+                                                               const float *__restrict__ points, int stride, int N,
+                                                               const double *__restrict__ pose, double max_dist, SfDist dd,
+                                                               long long *__restrict__ keys_out, double *__restrict__ d2_out,
+                                                               double *__restrict__ rows_out, double *__restrict__ info_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  SurfView m;
+  long long kout = -1;
+  double d2 = -1.0;
+  map_u64 key, bkey;
+  double w[3], d[3], bd2;
+  uint32_t s = 0;
+  bool got = false;
+  if (sf_view_of(map, cap_max, voxel, m) &&
+      !map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
+      sf_nearest<false>(m, key, w, dd.min_flag, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
+    kout = (long long)bkey;
+    d2 = bd2;
+    got = true;
+  }
+  keys_out[i] = kout;
+  d2_out[i] = d2;
+  if (rows_out) {
+    const double *row = got ? m.rows + (size_t)s * 8 : nullptr;
+    for (int k = 0; k < 8; ++k) rows_out[(size_t)i * 8 + k] = row ? row[k] : 0.0;
+  }
+  if (info_out) {
+    double v[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (got) {
+      const bool usable = sf_information(m.mom + (size_t)s * 10, m.hdr->voxel, dd, v, v[6], v[7]);
+      if (!usable)
+        for (int k = 0; k < 6; ++k) v[k] = 0.0;
+    }
+    for (int k = 0; k < 8; ++k) info_out[(size_t)i * 8 + k] = v[k];
+  }
+}
+
+// k_surfel_accum with the distribution term.  The match comes first and leaves slot and d; only then are the winner's
+// moments read, so the 27-key arrays of sf_nearest are dead while M and the 3 x 6 product M J are live.  An unusable pair
+// adds nothing and is not counted.  WEIGHTED: rho = u*u, u = s2 / (s2 + e) on the 28 addends, e = d^T M d.
+template <bool WEIGHTED>
+__global__ __launch_bounds__(SF_BLOCK) void k_surfel_accum_d(const void *map, long long cap_max, double voxel,
+                                                             const float *__restrict__ points, int stride, int N,
+                                                             const double *__restrict__ pose, double max_dist, SfDist dd,
+                                                             int iter, const int32_t *__restrict__ flag,
+                                                             double *__restrict__ partials, double s2) {
+  if (iter > 0 && *flag) return;      // converged in an earlier iteration: the second stage does not read the partials
+  __shared__ double part[SF_BLOCK / 64 * GN_NSUM];
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  double acc[GN_NSUM];
+#pragma unroll
+  for (int k = 0; k < GN_NSUM; ++k) acc[k] = 0.0;
+  SurfView m;
+  map_u64 key, bkey;
+  double w[3], d[3], bd2;
+  uint32_t s;
+  if (i < N && sf_view_of(map, cap_max, voxel, m)) {
+    if (!map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
+        sf_nearest<false>(m, key, w, dd.min_flag, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
+      double M6[6], det, lam;
+      if (sf_information(m.mom + (size_t)s * 10, m.hdr->voxel, dd, M6, det, lam)) {
+        gn_info_terms(w, d, M6, acc);
+        acc[GN_NSUM - 1] = 1.0;
+        if (WEIGHTED) {
+          const double u = s2 / (s2 + acc[GN_NSUM - 2]);
+          const double rho = u * u;
+#pragma unroll
+          for (int k = 0; k < GN_NSUM - 1; ++k) acc[k] = rho * acc[k];
+        }
       }
     }
   }
@@ -978,6 +1089,98 @@ extern "C" int rslo_surfel_register(const void *map, size_t map_bytes, double vo
   for (int it = 0; it < iters; ++it)
     sf_launch(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, nullptr, pose7, it, sp,
               info, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Distribution cost: the three calls above with candidates of flag >= min_flag and the cell's information matrix
+// ---------------------------------------------------------------------------------------------------------------------
+static int sf_check_dist(const char *name, int min_flag, double reg_rel, double reg_abs) {
+  const double inf = (double)__builtin_inff();
+  RSLO_CHECK_ARG(min_flag == 1 || min_flag == 2, "%s: min_flag must be 1 or 2", name);
+  RSLO_CHECK_ARG(reg_rel >= 0.0 && reg_rel < inf && reg_abs >= 0.0 && reg_abs < inf && (reg_rel > 0.0 || reg_abs > 0.0),
+                 "%s: reg_rel and reg_abs must be >= 0, finite and not both zero (NaN is refused)", name);
+  return RSLO_OK;
+}
+
+static void sf_launch_d(const void *map, long long cap_max, double voxel, const float *points, int stride, int N,
+                        const double *pose, double max_dist, double scale, const SfDist &dd, double *out29, double *pose_rw,
+                        int iter, const SfSolve &sp, double *info, void *ws, hipStream_t s) {
+  int32_t *flag = (int32_t *)ws;
+  double *partials = (double *)((unsigned char *)ws + SF_WS_HDR);
+  const int nb = (int)rslo_cdiv(N, SF_BLOCK);
+  if (nb > 0 && scale == 0.0)
+    hipLaunchKernelGGL(k_surfel_accum_d<false>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points,
+                       stride, N, pose, max_dist, dd, iter, (const int32_t *)flag, partials, 0.0);
+  else if (nb > 0)
+    hipLaunchKernelGGL(k_surfel_accum_d<true>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points,
+                       stride, N, pose, max_dist, dd, iter, (const int32_t *)flag, partials, scale * scale);
+  hipLaunchKernelGGL(k_surfel_finish, dim3(1), dim3(64), 0, s, (const double *)partials, nb, out29, pose_rw, iter, sp, flag,
+                     info);
+}
+
+extern "C" int rslo_surfel_nearest_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                     int stride_floats, int N, const double *pose7, double max_dist, int min_flag,
+                                     double reg_rel, double reg_abs, int64_t *keys_out, double *d2_out, double *rows_out,
+                                     double *info_out, void *stream) {
+  const char *name = "surfel_nearest_d";
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  rc = sf_check_dist(name, min_flag, reg_rel, reg_abs);
+  if (rc) return rc;
+  if (N == 0) return RSLO_OK;
+  RSLO_CHECK_ARG(points && keys_out && d2_out, "%s: null pointer", name);
+  const SfDist dd = {(double)min_flag, reg_rel, reg_abs};
+  hipLaunchKernelGGL(k_surfel_nearest_d, dim3((unsigned)rslo_cdiv(N, SF_BLOCK)), dim3(SF_BLOCK), 0, (hipStream_t)stream,
+                     map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, dd, (long long *)keys_out, d2_out,
+                     rows_out, info_out);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
+extern "C" int rslo_surfel_normal_eq_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                       int stride_floats, int N, const double *pose7, double max_dist, int min_flag,
+                                       double reg_rel, double reg_abs, double robust_scale, double *out29, void *ws,
+                                       size_t ws_bytes, void *stream) {
+  const char *name = "surfel_normal_eq_d";
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  rc = sf_check_dist(name, min_flag, reg_rel, reg_abs);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(out29, "%s: out29 is null", name);
+  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
+  if (rc) return rc;
+  const SfSolve sp = {0, 0.0, 0.0, 0.0};
+  const SfDist dd = {(double)min_flag, reg_rel, reg_abs};
+  sf_launch_d(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, dd, out29, nullptr, 0, sp,
+              nullptr, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
+extern "C" int rslo_surfel_register_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                      int stride_floats, int N, double *pose7, int iters, double max_dist, double damping,
+                                      int min_pairs, double tol_t, double tol_r, double robust_scale, int min_flag,
+                                      double reg_rel, double reg_abs, double *info, void *ws, size_t ws_bytes, void *stream) {
+  const char *name = "surfel_register_d";
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  rc = sf_check_dist(name, min_flag, reg_rel, reg_abs);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(iters >= 1 && iters <= SF_MAX_ITERS, "%s: iters must be in 1 .. 32", name);
+  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "%s: tol_t and tol_r must be >= 0 (NaN is refused)", name);
+  RSLO_CHECK_ARG(info, "%s: info is null", name);
+  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
+  if (rc) return rc;
+  const SfSolve sp = {min_pairs, damping, tol_t, tol_r};
+  const SfDist dd = {(double)min_flag, reg_rel, reg_abs};
+  for (int it = 0; it < iters; ++it)
+    sf_launch_d(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, dd, nullptr, pose7, it,
+                sp, info, ws, (hipStream_t)stream);
   RSLO_CHECK_LAUNCH(name);
   return RSLO_OK;
 }

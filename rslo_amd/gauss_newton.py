@@ -1,7 +1,8 @@
 """The Gauss-Newton core of scan-to-map registration and loop verification on the host, numpy float64 (device twin:
 csrc/gauss_newton.h).  The 28 sums of a set of matched points are the upper triangle of H = sum J^T J (21, row-major),
 g = sum J^T r (6) and the cost sum r.r, for the world-frame twist (dt, dtheta).  terms_of gives their addends row by row
-in the operand order of gn_point_terms / gn_plane_terms; gauss_newton_step is gn_step, scalar float64 in the order of
+in the operand order of gn_point_terms / gn_plane_terms, info_terms those of gn_info_terms (H = sum J^T M J with a
+cell's information matrix M); gauss_newton_step is gn_step, scalar float64 in the order of
 the device's one thread."""
 import math
 
@@ -36,6 +37,29 @@ def terms_of(J, r):
 def point_terms(w, d):
     """[n, 28]: the addends of the 28 sums of matched points at world positions w with residuals d (J = [I | -[w]x])"""
     return terms_of(point_jacobian(w), d)
+
+
+def info_terms(w, d, M6):
+    """[n, 28]: the addends of point-to-distribution terms (gn_info_terms): rows J = [I | -[w]x] of the points at world
+    positions w [n, 3], residuals d [n, 3], information matrices M6 [n, 6] in the order 00 01 02 11 12 22.  m = M d,
+    B = M J; H(k, l) = J0[k] B0[l] + J1[k] B1[l] + J2[k] B2[l], g(k) = J0[k] m0 + J1[k] m1 + J2[k] m2, cost = d . m,
+    every sum left to right."""
+    w, d, M6 = (np.asarray(x, np.float64) for x in (w, d, M6))
+    J = point_jacobian(w)
+    M = [[M6[:, 0], M6[:, 1], M6[:, 2]], [M6[:, 1], M6[:, 3], M6[:, 4]], [M6[:, 2], M6[:, 4], M6[:, 5]]]
+    terms = np.zeros((len(w), 28), np.float64)
+    with np.errstate(all="ignore"):
+        m = [M[a][0] * d[:, 0] + M[a][1] * d[:, 1] + M[a][2] * d[:, 2] for a in range(3)]
+        B = [[M[a][0] * J[:, 0, k] + M[a][1] * J[:, 1, k] + M[a][2] * J[:, 2, k] for k in range(6)] for a in range(3)]
+        o = 0
+        for k in range(6):
+            for l in range(k, 6):
+                terms[:, o] = J[:, 0, k] * B[0][l] + J[:, 1, k] * B[1][l] + J[:, 2, k] * B[2][l]
+                o += 1
+        for k in range(6):
+            terms[:, 21 + k] = J[:, 0, k] * m[0] + J[:, 1, k] * m[1] + J[:, 2, k] * m[2]
+        terms[:, 27] = d[:, 0] * m[0] + d[:, 1] * m[1] + d[:, 2] * m[2]
+    return terms
 
 
 def _cross3(a, b):

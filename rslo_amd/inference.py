@@ -328,7 +328,10 @@ class OdometryRunner:
       against the surfel map's planes (SurfelMap.register: no scan normal is read, so raw scans get a plane metric): it
       creates the refined chain when refine= is absent, and corrects row n of it in place behind refine's own stage
       (if any); then the chain state is set and both maps are filled.  Scan 0 meets an empty table (status 1) and
-      stays the identity.  surfel_refine_info() is the [n, iters, 8] info.  reset() empties the surfel map;
+      stays the identity.  With cost="distribution" among the options (then also min_flag=1, reg_rel=0.01, reg_abs=0.02,
+      and robust_scale defaults to 3.0 sigmas) the stage is the point-to-distribution cost over every fitted cell
+      (SurfelMap.register(cost="distribution")), which also refines where the map holds no planes; nothing else in the
+      runner changes.  surfel_refine_info() is the [n, iters, 8] info.  reset() empties the surfel map;
       rebuild_map() on the runner's own maps and adopt_loop_closure() also reset it and refill it from the keyframe
       store under the same poses (SurfelMap.insert_frames).  The table only fills unless local_map= carries the
       surfels key (above): then it is pruned about the sensor every K scans and a long drive runs in a fixed table.

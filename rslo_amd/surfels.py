@@ -3,6 +3,7 @@
     smap = SurfelMap(voxel_size=0.4, capacity=1 << 20)
     smap.insert(scan, pose)                                     # fp32 CUDA [P, >= 3]: only x, y, z are read
     pose, info = smap.register(scan, pose, iters=4, robust_scale=0.2)
+    pose, info = smap.register(scan, pose, iters=4, robust_scale=3.0, cost="distribution")      # every fitted cell
     keys, moments, rows = smap.cells(min_flag=2)                # the planar cells, sorted by key
     runner = inference.OdometryRunner(net, surfels=smap, surfel_refine=dict(iters=4))
 
@@ -24,6 +25,11 @@ bit.  The rules in one place:
   * normal equations: every matched point adds ONE plane row a = (n, w x n), r = n . (w - mean) with the CELL's normal:
     no scan normal is read and there is no point-term fallback; robust weights and the Gauss-Newton step are those of
     mapping.py (gauss_newton.py);
+  * cost="distribution" on nearest / normal_equations / register (include/rslo_hip.h "Distribution cost"): the
+    candidates are the cells with flag >= min_flag (default 1: every fitted cell, poles and vegetation included), and a
+    matched point adds d^T M d with d = w - mean and M = (C + lam I)^-1, C the covariance of the cell's moments in
+    metres, lam = reg_rel * trace(C) + reg_abs^2 (SurfelMapRef.information, gauss_newton.info_terms).  The residual is
+    in sigmas, and so is robust_scale.  cost="plane", the default, is the rule above and takes none of these options;
   * the device table probes at most 128 slots and drops what finds no slot (dropped_full); SurfelMapRef has no capacity.
     Between two prunes the table only fills: reset() empties it;
   * prune(center=None, radius=None, inner_radius=None, min_count=1) is the one call that removes cells (include/
@@ -36,7 +42,7 @@ bit.  The rules in one place:
 """
 import numpy as np
 
-from .gauss_newton import gauss_newton_step, terms_of
+from .gauss_newton import gauss_newton_step, info_terms, terms_of
 from .mapping import VoxelMapRef, _check_params, _check_register, _max_dist_of, check_scale
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full", "n_planar")
@@ -55,19 +61,57 @@ def _check_plane_params(min_points, planar_ratio, line_ratio):
 
 
 SURFEL_REFINE_DEFAULTS = dict(iters=4, max_dist=None, robust_scale=0.2, damping=1e-6, min_pairs=50, tol_t=0.0, tol_r=0.0)
+COSTS = ("plane", "distribution")
+DIST_DEFAULTS = dict(min_flag=1, reg_rel=0.01, reg_abs=0.02)
+DIST_ROBUST_SCALE = 3.0      # the runner's default for cost="distribution": the residual is in sigmas, a three-sigma soft gate
+
+
+def check_cost(cost="plane", min_flag=None, reg_rel=None, reg_abs=None):
+    """The cost options of nearest / normal_equations / register (ValueError).  -> None for cost="plane", which takes
+    none of the others (min_flag=2 says what it does and is accepted); (min_flag, reg_rel, reg_abs) for
+    cost="distribution", defaults DIST_DEFAULTS: min_flag 1 or 2, reg_rel and reg_abs >= 0, finite, not both zero."""
+    if cost not in COSTS:
+        raise ValueError("cost must be one of %s, got %r" % (COSTS, cost))
+    if cost == "plane":
+        if min_flag not in (None, 2) or reg_rel is not None or reg_abs is not None:
+            raise ValueError("cost=\"plane\" matches the planar cells only and takes no min_flag, reg_rel or reg_abs")
+        return None
+    mf = DIST_DEFAULTS["min_flag"] if min_flag is None else min_flag
+    if mf not in (1, 2):
+        raise ValueError("min_flag must be 1 or 2, got %r" % (min_flag,))
+    rr = float(DIST_DEFAULTS["reg_rel"] if reg_rel is None else reg_rel)
+    ra = float(DIST_DEFAULTS["reg_abs"] if reg_abs is None else reg_abs)
+    if not (0.0 <= rr < float("inf") and 0.0 <= ra < float("inf") and (rr > 0.0 or ra > 0.0)):
+        raise ValueError("reg_rel and reg_abs must be >= 0, finite and not both zero (NaN is refused), got %r and %r"
+                         % (reg_rel, reg_abs))
+    return int(mf), rr, ra
+
+
+def _dist_kw(dist):
+    return dict(zip(("min_flag", "reg_rel", "reg_abs"), dist))
 
 
 def check_surfel_refine(options, surfel_map):
     """The surfel_refine= options of an OdometryRunner against the map it was given (ValueError): -> the keyword
-    arguments of surfel_map.register, defaults filled in."""
-    unknown = set(options) - set(SURFEL_REFINE_DEFAULTS)
+    arguments of surfel_map.register, defaults filled in.  cost="plane" (the default): SURFEL_REFINE_DEFAULTS and
+    nothing else.  cost="distribution" also takes min_flag, reg_rel and reg_abs (DIST_DEFAULTS), and its default
+    robust_scale is DIST_ROBUST_SCALE."""
+    known = set(SURFEL_REFINE_DEFAULTS) | {"cost"} | set(DIST_DEFAULTS)
+    unknown = set(options) - known
     if unknown:
-        raise ValueError("surfel_refine takes %s; got %s" % (", ".join(sorted(SURFEL_REFINE_DEFAULTS)), sorted(unknown)))
-    opts = dict(SURFEL_REFINE_DEFAULTS, **options)
+        raise ValueError("surfel_refine takes %s; got %s" % (", ".join(sorted(known)), sorted(unknown)))
+    options = dict(options)
+    dist = check_cost(options.pop("cost", "plane"), *(options.pop(k, None) for k in ("min_flag", "reg_rel", "reg_abs")))
+    opts = dict(SURFEL_REFINE_DEFAULTS)
+    if dist is not None:
+        opts["robust_scale"] = DIST_ROBUST_SCALE
+    opts.update(options)
     opts["iters"] = int(opts["iters"])
     _check_register(opts["iters"], opts["tol_t"], opts["tol_r"])
     _max_dist_of(opts["max_dist"], surfel_map.voxel_size)
     check_scale(opts["robust_scale"])
+    if dist is not None:
+        opts.update(cost="distribution", **_dist_kw(dist))
     return opts
 
 
@@ -283,8 +327,9 @@ class SurfelMapRef:
         sel = self.rows[:, 7] >= float(min_flag)
         return self.keys[sel], self.moments[sel], self.rows[sel]
 
-    def _match(self, points, pose, max_dist):
-        """-> (world [P, 3], index [P] into the cell arrays (-1: no match), d2 [P] (-1.0: no match))"""
+    def _match(self, points, pose, max_dist, min_flag=2):
+        """-> (world [P, 3], index [P] into the cell arrays (-1: no match), d2 [P] (-1.0: no match)); the candidates are
+        the cells with flag >= min_flag (2: the planar ones)"""
         md = _max_dist_of(max_dist, self.voxel_size)
         status, key, w = self._cells(points, pose)
         P = len(status)
@@ -295,7 +340,7 @@ class SurfelMapRef:
             ok = status == 0
             c = [(key >> 42) & 0x1fffff, (key >> 21) & 0x1fffff, key & 0x1fffff]
             last = len(self.keys) - 1
-            planar = self.rows[:, 7] == 2.0
+            planar = self.rows[:, 7] >= float(min_flag)
             with np.errstate(all="ignore"):
                 for dx in (-1, 0, 1):
                     for dy in (-1, 0, 1):
@@ -313,23 +358,72 @@ class SurfelMapRef:
             acc = (best >= 0) & (bd2 < md * md)
         return w, np.where(acc, best, -1), np.where(acc, bd2, -1.0)
 
-    def nearest(self, points, pose=None, max_dist=None, return_rows=False):
-        """(keys int64 [P], d2 float64 [P][, rows float64 [P, 8]]) of the nearest planar cell within max_dist (None:
-        voxel_size) of every point; -1 / -1.0 / zeros without a match or for a skipped point."""
-        _, idx, d2 = self._match(points, pose, max_dist)
+    def nearest(self, points, pose=None, max_dist=None, return_rows=False, cost="plane", min_flag=None, reg_rel=None,
+                reg_abs=None, return_info=False):
+        """(keys int64 [P], d2 float64 [P][, rows float64 [P, 8]][, info float64 [P, 8]]) of the nearest planar cell
+        within max_dist (None: voxel_size) of every point; -1 / -1.0 / zeros without a match or for a skipped point.
+        cost="distribution": the nearest cell with flag >= min_flag (default 1); return_info adds the rows of
+        information() of the matched cells, zeros without a match."""
+        dist = check_cost(cost, min_flag, reg_rel, reg_abs)
+        if dist is None and return_info:
+            raise ValueError("return_info needs cost=\"distribution\"")
+        _, idx, d2 = self._match(points, pose, max_dist, 2 if dist is None else dist[0])
         got = idx >= 0
         keys = np.full((len(idx),), -1, np.int64)
         keys[got] = self.keys[idx[got]]
-        if not return_rows:
-            return keys, d2
-        rows = np.zeros((len(idx), 8), np.float64)
-        rows[got] = self.rows[idx[got]]
-        return keys, d2, rows
+        out = [keys, d2]
+        if return_rows:
+            rows = np.zeros((len(idx), 8), np.float64)
+            rows[got] = self.rows[idx[got]]
+            out.append(rows)
+        if return_info:
+            info = np.zeros((len(idx), 8), np.float64)
+            info[got] = self.information(idx[got], dist[1], dist[2])
+            out.append(info)
+        return tuple(out)
 
-    def _pair_terms(self, points, pose, max_dist=None):
+    def information(self, idx_or_keys, reg_rel=DIST_DEFAULTS["reg_rel"], reg_abs=DIST_DEFAULTS["reg_abs"]):
+        """[n, 8] float64 rows {M00, M01, M02, M11, M12, M22, det, lam} of the given cells -- indices into the cell
+        arrays, or packed keys (a key is >= 2^42) -- by the rules of "Distribution cost": the covariance of the cell's
+        moments in metres, lam = reg_rel * trace + reg_abs^2 on the diagonal, inverted by the adjugate, operation by
+        operation the device's sf_information.  A row whose det fails det > 0 && det < inf is unusable: its six M
+        entries are zeros."""
+        _, rr, ra = check_cost("distribution", None, reg_rel, reg_abs)
+        at = np.asarray(idx_or_keys, np.int64).reshape(-1)
+        is_key = at >= (1 << 42)
+        if is_key.any():
+            pos = np.minimum(np.searchsorted(self.keys, at), max(len(self.keys) - 1, 0))
+            if len(self.keys) == 0 or (self.keys[pos] != at)[is_key].any():
+                raise ValueError("information: a key that is not in the map")
+            at = np.where(is_key, pos, at)
+        _, c, _ = covariances(self.moments[at])
+        out = np.zeros((len(at), 8), np.float64)
+        with np.errstate(all="ignore"):
+            u = self.voxel_size / Q
+            C = [(c[:, k] * u) * u for k in range(6)]
+            lam = rr * ((C[0] + C[3]) + C[5]) + ra * ra
+            S00, S01, S02, S11, S12, S22 = C[0] + lam, C[1], C[2], C[3] + lam, C[4], C[5] + lam
+            A = [S11 * S22 - S12 * S12, S02 * S12 - S01 * S22, S01 * S12 - S02 * S11,
+                 S00 * S22 - S02 * S02, S01 * S02 - S00 * S12, S00 * S11 - S01 * S01]
+            det = (S00 * A[0] + S01 * A[1]) + S02 * A[2]
+            usable = (det > 0.0) & (det < np.inf)
+            for k in range(6):
+                out[:, k] = np.where(usable, A[k] / np.where(usable, det, 1.0), 0.0)
+        out[:, 6], out[:, 7] = det, lam
+        return out
+
+    def _pair_terms(self, points, pose, max_dist=None, dist=None):
         """The addends of normal_equations, one row per matched point in input order: [K, 28] = H upper triangle (21),
-        g (6), cost of the plane term with the cell's normal."""
+        g (6), cost of the plane term with the cell's normal.  dist = (min_flag, reg_rel, reg_abs): of the distribution
+        term with the cell's information matrix instead, one row per USABLE pair (gauss_newton.info_terms)."""
         posev = np.asarray([0, 0, 0, 1, 0, 0, 0] if pose is None else pose, dtype=np.float64).reshape(7)
+        if dist is not None:
+            w, idx, _ = self._match(points, posev, max_dist, dist[0])
+            sel = np.nonzero(idx >= 0)[0]
+            info = self.information(idx[sel], dist[1], dist[2])
+            use = (info[:, 6] > 0.0) & (info[:, 6] < np.inf)
+            sel, info = sel[use], info[use]
+            return info_terms(w[sel], w[sel] - self.rows[idx[sel], :3], info[:, :6])
         w, idx, _ = self._match(points, posev, max_dist)
         sel = np.nonzero(idx >= 0)[0]
         w = w[sel]
@@ -341,9 +435,9 @@ class SurfelMapRef:
         r[:, 0] = n[:, 0] * d[:, 0] + n[:, 1] * d[:, 1] + n[:, 2] * d[:, 2]
         return terms_of(J, r)
 
-    def _weighted_terms(self, points, pose, max_dist=None, robust_scale=0.0):
+    def _weighted_terms(self, points, pose, max_dist=None, robust_scale=0.0, dist=None):
         scale = check_scale(robust_scale)
-        terms = self._pair_terms(points, pose, max_dist)
+        terms = self._pair_terms(points, pose, max_dist, dist)
         if scale == 0.0:
             return terms
         s2 = scale * scale
@@ -352,14 +446,20 @@ class SurfelMapRef:
             rho = u * u
             return terms * rho[:, None]
 
-    def normal_equations(self, points, pose, max_dist=None, robust_scale=0.0):
-        """[29] float64: the column sums of _pair_terms (weighted when robust_scale > 0), then the number of pairs."""
-        terms = self._weighted_terms(points, pose, max_dist, robust_scale)
+    def normal_equations(self, points, pose, max_dist=None, robust_scale=0.0, cost="plane", min_flag=None, reg_rel=None,
+                         reg_abs=None):
+        """[29] float64: the column sums of _pair_terms (weighted when robust_scale > 0), then the number of pairs.
+        cost="distribution": of the distribution terms (robust_scale is then in sigmas)."""
+        dist = check_cost(cost, min_flag, reg_rel, reg_abs)
+        terms = self._weighted_terms(points, pose, max_dist, robust_scale, dist)
         return np.concatenate([terms.sum(axis=0), [float(len(terms))]])
 
     def register(self, points, pose, iters=4, max_dist=None, damping=0.0, min_pairs=50, tol_t=0.0, tol_r=0.0,
-                 robust_scale=0.0):
-        """-> (pose [7] float64, info [iters, 8]): the loop of mapping.VoxelMapRef.register on the plane terms above."""
+                 robust_scale=0.0, cost="plane", min_flag=None, reg_rel=None, reg_abs=None):
+        """-> (pose [7] float64, info [iters, 8]): the loop of mapping.VoxelMapRef.register on the plane terms above, or
+        with cost="distribution" on the distribution terms."""
+        dist = check_cost(cost, min_flag, reg_rel, reg_abs)
+        cost_kw = {} if dist is None else dict(cost="distribution", **_dist_kw(dist))
         _check_register(iters, tol_t, tol_r)
         check_scale(robust_scale)
         _max_dist_of(max_dist, self.voxel_size)
@@ -370,7 +470,7 @@ class SurfelMapRef:
             if done:
                 info[it, 0] = 3.0
                 continue
-            sums = self.normal_equations(points, pose, max_dist, robust_scale)
+            sums = self.normal_equations(points, pose, max_dist, robust_scale, **cost_kw)
             info[it, 1], info[it, 2] = sums[28], sums[27]
             if sums[28] < min_pairs:
                 info[it, 0] = 1.0
@@ -462,35 +562,57 @@ class SurfelMap:
             poses = torch.as_tensor(np.ascontiguousarray(host)).to(self.device)
         capi.surfel_insert_frames(self._buf, store._buf, store.capacity, store.K, poses.contiguous())
 
-    def nearest(self, points, pose=None, max_dist=None, return_rows=False):
-        """(keys int64 [P], d2 float64 [P][, rows float64 [P, 8]]) on the device; -1 / -1.0 / zeros without a match."""
+    def nearest(self, points, pose=None, max_dist=None, return_rows=False, cost="plane", min_flag=None, reg_rel=None,
+                reg_abs=None, return_info=False):
+        """(keys int64 [P], d2 float64 [P][, rows float64 [P, 8]][, info float64 [P, 8]]) on the device; -1 / -1.0 /
+        zeros without a match.  cost="distribution": among the cells with flag >= min_flag (default 1); return_info adds
+        the information-matrix rows {M00, M01, M02, M11, M12, M22, det, lam} of the matched cells."""
         from rslo_amd import capi
+        dist = check_cost(cost, min_flag, reg_rel, reg_abs)
         md = _max_dist_of(max_dist, self.voxel_size)
-        return capi.surfel_nearest(self._buf, points, self._pose(pose), self.voxel_size, md,
-                                   rows=True if return_rows else None)
+        if dist is None:
+            if return_info:
+                raise ValueError("return_info needs cost=\"distribution\"")
+            return capi.surfel_nearest(self._buf, points, self._pose(pose), self.voxel_size, md,
+                                       rows=True if return_rows else None)
+        return capi.surfel_nearest_d(self._buf, points, self._pose(pose), self.voxel_size, md, *dist,
+                                     rows=True if return_rows else None, info=True if return_info else None)
 
-    def normal_equations(self, points, pose, max_dist=None, robust_scale=0.0):
-        """float64 CUDA [29]: the upper triangle of H (21), g (6), cost, pairs of the matched points at pose."""
+    def normal_equations(self, points, pose, max_dist=None, robust_scale=0.0, cost="plane", min_flag=None, reg_rel=None,
+                         reg_abs=None):
+        """float64 CUDA [29]: the upper triangle of H (21), g (6), cost, pairs of the matched points at pose.
+        cost="distribution": of the distribution terms (robust_scale is then in sigmas)."""
         from rslo_amd import capi
+        dist = check_cost(cost, min_flag, reg_rel, reg_abs)
         md = _max_dist_of(max_dist, self.voxel_size)
         scale = check_scale(robust_scale)
         self.reserve(points.shape[0])
-        return capi.surfel_normal_eq(self._buf, points, self._pose(pose), self.voxel_size, md, scale, ws=self._reg_ws)
+        if dist is None:
+            return capi.surfel_normal_eq(self._buf, points, self._pose(pose), self.voxel_size, md, scale, ws=self._reg_ws)
+        return capi.surfel_normal_eq_d(self._buf, points, self._pose(pose), self.voxel_size, md, *dist, robust_scale=scale,
+                                       ws=self._reg_ws)
 
     def register(self, points, pose, iters=4, max_dist=None, damping=0.0, min_pairs=50, tol_t=0.0, tol_r=0.0,
-                 robust_scale=0.0, info=None):
+                 robust_scale=0.0, info=None, cost="plane", min_flag=None, reg_rel=None, reg_abs=None):
         """`iters` Gauss-Newton iterations of points (fp32 CUDA [P, F >= 3], read in place) against the planar cells, on
-        the device.  pose: a float64 CUDA [7] tensor (a trajectory row) is updated IN PLACE and returned; anything else
-        is copied to the device first.  -> (pose [7], info [iters, 8]) device tensors; info may be preallocated.  No
-        host read, nothing allocated after a reserve() when info is given."""
+        the device; cost="distribution": against every cell with flag >= min_flag (default 1) under the
+        point-to-distribution cost (include/rslo_hip.h "Distribution cost"; robust_scale is then in sigmas).  pose: a
+        float64 CUDA [7] tensor (a trajectory row) is updated IN PLACE and returned; anything else is copied to the
+        device first.  -> (pose [7], info [iters, 8]) device tensors; info may be preallocated.  No host read, nothing
+        allocated after a reserve() when info is given."""
         from rslo_amd import capi
+        dist = check_cost(cost, min_flag, reg_rel, reg_abs)
         _check_register(iters, tol_t, tol_r)
         md = _max_dist_of(max_dist, self.voxel_size)
         scale = check_scale(robust_scale)
         self.reserve(points.shape[0])
         pose = self._identity.clone() if pose is None else self._pose(pose)
-        info = capi.surfel_register(self._buf, points, pose, self.voxel_size, iters, md, damping, min_pairs, tol_t, tol_r,
-                                    scale, info=info, ws=self._reg_ws)
+        if dist is None:
+            info = capi.surfel_register(self._buf, points, pose, self.voxel_size, iters, md, damping, min_pairs, tol_t,
+                                        tol_r, scale, info=info, ws=self._reg_ws)
+        else:
+            info = capi.surfel_register_d(self._buf, points, pose, self.voxel_size, iters, md, damping, min_pairs, tol_t,
+                                          tol_r, scale, *dist, info=info, ws=self._reg_ws)
         return pose, info
 
     def reserve_prune(self):

@@ -14,6 +14,7 @@
     python scripts/odometry_stream.py --verify --scans 200 --warmup 20 [--out profiles/odometry_stream_verify.json]
     python scripts/odometry_stream.py --rebuild-map --scans 200 --warmup 20 [--out profiles/odometry_stream_rebuild.json]
     python scripts/odometry_stream.py --surfels --scans 200 --warmup 20 [--surfel-voxel 0.4] [--surfel-iters 4] [--out profiles/odometry_stream_surfels.json]
+    python scripts/odometry_stream.py --surfels --surfel-cost distribution --scans 200 --warmup 20 [--surfel-reg-abs 0.02]
     python scripts/odometry_stream.py --surfels --local-map-radius 50 --surfel-min-count 2 --surfel-inner-radius 25 --scans 180 --warmup 20
     python scripts/odometry_stream.py --deskew --scans 100 --warmup 10 [--out profiles/odometry_stream_deskew.json]
 
@@ -358,6 +359,11 @@ def main():
                     help="also run the runner with a surfel map and its registration stage, and the registration-alone rows")
     ap.add_argument("--surfel-voxel", type=float, default=0.4)
     ap.add_argument("--surfel-iters", type=int, default=4, help="Gauss-Newton iterations of the surfel stage")
+    ap.add_argument("--surfel-cost", choices=("plane", "distribution"), default="plane",
+                    help="with --surfels: distribution runs the registration-alone rows of BOTH costs in one process and "
+                         "nothing else, and writes profiles/odometry_stream_surfels_dist.json unless --out is given")
+    ap.add_argument("--surfel-reg-abs", type=float, default=0.02,
+                    help="with --surfel-cost distribution: the absolute regularisation of a cell's covariance in metres")
     ap.add_argument("--surfel-min-count", type=int, default=1,
                     help="with --surfels --local-map-radius: evict surfel cells with fewer points beyond the inner radius")
     ap.add_argument("--surfel-inner-radius", type=float, default=None,
@@ -410,6 +416,16 @@ def main():
     t_scans = time.time() - t0
     import torch
     import rslo_amd  # noqa: F401
+    if args.surfels and args.surfel_cost == "distribution":
+        scans = [torch.from_numpy(c).to(torch.device("cuda", 0)) for c in clouds]
+        res = {"metric": "surfel_alone_ms_per_iteration", "scans": args.scans, "warmup": args.warmup, "seed": args.seed,
+               "points_per_scan": int(sum(c.shape[0] for c in clouds) / len(clouds)), "scan_generation_s": round(t_scans, 1)}
+        res.update(surfel_dist_report(args, scans))
+        line = json.dumps(res)
+        print(line)
+        with open(args.out or os.path.join(ROOT, "profiles", "odometry_stream_surfels_dist.json"), "w") as f:
+            f.write(line + "\n")
+        return
     from rslo_amd import inference, workload
     torch.manual_seed(args.seed)
     net, _ = workload.build_network()
@@ -1137,6 +1153,31 @@ def surfel_report(args, net, scans, res):
     out.update(register_alone(args, scans, _Targets(pyr, smap),
                               lambda s, p: torch.cat([pyr.register(s, p, sch)[1], smap.register(s, p, iters=K, **kw)[1]]),
                               "pyramid_then_surfel", pairs_row=-1))
+    return out
+
+
+def surfel_dist_report(args, scans):
+    """--surfels --surfel-cost distribution: the registration-alone pass (register_alone: the same seeded disturbance
+    for every row) against a surfel map, once with the plane cost and the runner's defaults and once with the
+    point-to-distribution cost over every fitted cell and its defaults, in this one process: ms per call and per
+    iteration, pairs, and the error against the synthetic truth behind the last iteration."""
+    from rslo_amd import surfels
+    K = args.surfel_iters
+    out = {"surfel_voxel": args.surfel_voxel}
+    smap = surfels.SurfelMap(args.surfel_voxel, 1 << 20, scans[0].device)
+    smap.reserve(max(s.shape[0] for s in scans))
+    rows = (("surfel_alone", {}), ("surfel_dist_alone", dict(cost="distribution", reg_abs=args.surfel_reg_abs)))
+    for name, options in rows:
+        kw = surfels.check_surfel_refine(dict(options, iters=K), smap)
+        out[name + "_options"] = kw
+        out.update(register_alone(args, scans, smap, lambda s, p: smap.register(s, p, **kw)[1], name))
+        out[name + "_ms_per_iteration"] = round(out[name + "_ms_per_call"] / K, 4)
+        print("%-18s %.4f ms per call, %.4f ms per iteration, %.1f pairs, error %.5f -> %.5f m, %.5f -> %.5f deg" % (
+            name, out[name + "_ms_per_call"], out[name + "_ms_per_iteration"], out[name + "_pairs_per_scan"],
+            out[name + "_before_trans_m_mean"], out[name + "_after_trans_m_mean"], out[name + "_before_rot_deg_mean"],
+            out[name + "_after_rot_deg_mean"]), flush=True)
+    out["surfel_dist_over_plane_ms_per_iteration"] = round(
+        out["surfel_dist_alone_ms_per_iteration"] / out["surfel_alone_ms_per_iteration"], 3)
     return out
 
 
