@@ -1358,12 +1358,37 @@ def map_register_ws(n_points, device):
     return torch.empty((int(lib().rslo_map_register_ws_bytes(int(n_points))) // 8,), dtype=torch.int64, device=device)
 
 
-def _map_ws(ws, P, device):
+def _register_ws(family, ws, P, device):
+    """the workspace of a normal_eq / register call of the "map" or the "surfel" family: the caller's, or a new one"""
     if ws is None:
-        return map_register_ws(P, device)
+        return (map_register_ws if family == "map" else surfel_register_ws)(P, device)
     if not (ws.is_cuda and ws.is_contiguous()):
-        raise RsloHipError("map: the workspace must be a contiguous CUDA tensor")
+        raise RsloHipError("%s: the workspace must be a contiguous CUDA tensor" % family)
     return ws
+
+
+def _gn_args(name, buf, points, voxel_size, max_dist, result, ws, iters=None):
+    """What the normal_eq and register wrappers of both map families do before their call: -> (head, P, max_dist,
+    result, ws) with head = (map pointer, map bytes, voxel size, points pointer, stride in floats) and result the [29] sums
+    (iters None) or the [iters, 8] info rows, the caller's or a new tensor.  voxel_size None is read from a voxel map."""
+    family = name.split("_")[0]
+    ptr, nbytes = _map_buf(buf)
+    src, stride = _rows3(points, "points")
+    P = points.shape[0]
+    if voxel_size is None and family == "map":
+        voxel_size = map_params(buf)[0]
+    shape, what = ((29,), "out must be [29]") if iters is None else ((iters, 8), "info must be [iters, 8]")
+    if result is None:
+        result = torch.empty(tuple(max(n, 0) for n in shape), dtype=torch.float64, device=points.device)
+    if result.shape != shape:
+        raise RsloHipError("%s: %s" % (name, what))
+    ws = _register_ws(family, ws, P, points.device)
+    return ((ptr, nbytes, float(voxel_size), src, stride), P, float(voxel_size if max_dist is None else max_dist), result, ws)
+
+
+def _gn_tail(result, what, ws):
+    """the last four arguments of those calls: the result, the workspace and its bytes, the stream"""
+    return _ptr(result, torch.float64, what), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()
 
 
 def map_normal_eq(buf, points, pose, voxel_size=None, metric="plane", max_dist=None, min_hits=1, out=None, ws=None,
@@ -1372,28 +1397,12 @@ def map_normal_eq(buf, points, pose, voxel_size=None, metric="plane", max_dist=N
     matches of map_nearest.  metric "plane" reads the normals at columns 4..6 of points.  No host read.
     robust_scale (not None): rslo_map_normal_eq_w, every matched point's addends times its Geman-McClure weight
     (0.0: no weights, the bits of rslo_map_normal_eq)."""
-    ptr, nbytes = _map_buf(buf)
-    src, stride = _rows3(points, "points")
-    P = points.shape[0]
-    if voxel_size is None:
-        voxel_size = map_params(buf)[0]
-    if out is None:
-        out = torch.empty((29,), dtype=torch.float64, device=points.device)
-    if out.shape != (29,):
-        raise RsloHipError("map_normal_eq: out must be [29]")
-    ws = _map_ws(ws, P, points.device)
+    head, P, max_dist, out, ws = _gn_args("map_normal_eq", buf, points, voxel_size, max_dist, out, ws)
+    sym = "map_normal_eq" if robust_scale is None else "map_normal_eq_w"
+    args = [*head, int(points.shape[1]), P, _pose7(pose, sym), _map_metric(metric), max_dist, int(min_hits)]
     if robust_scale is not None:
-        _chk(lib().rslo_map_normal_eq_w(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
-                                        _pose7(pose, "map_normal_eq_w"), _map_metric(metric),
-                                        float(voxel_size if max_dist is None else max_dist), int(min_hits),
-                                        float(robust_scale), _ptr(out, torch.float64, "out"), ws.data_ptr(),
-                                        ws.numel() * ws.element_size(), _stream()), "rslo_map_normal_eq_w")
-        return out
-    _chk(lib().rslo_map_normal_eq(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
-                                  _pose7(pose, "map_normal_eq"), _map_metric(metric),
-                                  float(voxel_size if max_dist is None else max_dist), int(min_hits),
-                                  _ptr(out, torch.float64, "out"), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()),
-         "rslo_map_normal_eq")
+        args.append(float(robust_scale))
+    _chk(getattr(lib(), "rslo_" + sym)(*args, *_gn_tail(out, "out", ws)), "rslo_" + sym)
     return out
 
 
@@ -1403,30 +1412,14 @@ def map_register(buf, points, pose, voxel_size=None, iters=5, metric="plane", ma
     IN PLACE.  Returns info float64 CUDA [iters, 8]: rows {status, pairs, cost, |dt|, theta, 0, 0, 0}, status 0 step taken, 1
     too few pairs, 2 not positive definite, 3 skipped after convergence.  No host read, a fixed number of launches: capturable.
     robust_scale (not None): rslo_map_register_w, Geman-McClure weights of that scale (0.0: no weights, the same bits)."""
-    ptr, nbytes = _map_buf(buf)
-    src, stride = _rows3(points, "points")
-    P = points.shape[0]
     iters = int(iters)
-    if voxel_size is None:
-        voxel_size = map_params(buf)[0]
-    if info is None:
-        info = torch.empty((max(iters, 0), 8), dtype=torch.float64, device=points.device)
-    if info.shape != (iters, 8):
-        raise RsloHipError("map_register: info must be [iters, 8]")
-    ws = _map_ws(ws, P, points.device)
+    head, P, max_dist, info, ws = _gn_args("map_register", buf, points, voxel_size, max_dist, info, ws, iters)
+    sym = "map_register" if robust_scale is None else "map_register_w"
+    args = [*head, int(points.shape[1]), P, _pose7(pose, sym), iters, _map_metric(metric), max_dist, int(min_hits),
+            float(damping), int(min_pairs), float(tol_t), float(tol_r)]
     if robust_scale is not None:
-        _chk(lib().rslo_map_register_w(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
-                                       _pose7(pose, "map_register_w"), iters, _map_metric(metric),
-                                       float(voxel_size if max_dist is None else max_dist), int(min_hits), float(damping),
-                                       int(min_pairs), float(tol_t), float(tol_r), float(robust_scale),
-                                       _ptr(info, torch.float64, "info"), ws.data_ptr(), ws.numel() * ws.element_size(),
-                                       _stream()), "rslo_map_register_w")
-        return info
-    _chk(lib().rslo_map_register(ptr, nbytes, float(voxel_size), src, stride, int(points.shape[1]), P,
-                                 _pose7(pose, "map_register"), iters, _map_metric(metric),
-                                 float(voxel_size if max_dist is None else max_dist), int(min_hits), float(damping),
-                                 int(min_pairs), float(tol_t), float(tol_r), _ptr(info, torch.float64, "info"),
-                                 ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_map_register")
+        args.append(float(robust_scale))
+    _chk(getattr(lib(), "rslo_" + sym)(*args, *_gn_tail(info, "info", ws)), "rslo_" + sym)
     return info
 
 
@@ -1454,7 +1447,7 @@ def map_register_sched(bufs, voxel_sizes, stages, points, pose, metric="plane", 
         info = torch.empty((max(total, 0), 8), dtype=torch.float64, device=points.device)
     if info.shape != (total, 8):
         raise RsloHipError("map_register_sched: info must be [sum of iters, 8] = [%d, 8]" % total)
-    ws = _map_ws(ws, P, points.device)
+    ws = _register_ws("map", ws, P, points.device)
     _chk(lib().rslo_map_register_sched(maps, nbytes, voxels, L, flat, len(rows), src, stride, int(points.shape[1]), P,
                                        _pose7(pose, "map_register_sched"), _map_metric(metric), int(min_hits),
                                        float(damping), int(min_pairs), float(tol_t), float(tol_r),
@@ -1588,29 +1581,12 @@ def surfel_nearest(buf, points, pose, voxel_size, max_dist=None, rows=None, keys
     return (keys, d2) if rows is None else (keys, d2, rows)
 
 
-def _surfel_ws(ws, P, device):
-    if ws is None:
-        return surfel_register_ws(P, device)
-    if not (ws.is_cuda and ws.is_contiguous()):
-        raise RsloHipError("surfel: the workspace must be a contiguous CUDA tensor")
-    return ws
-
-
 def surfel_normal_eq(buf, points, pose, voxel_size, max_dist=None, robust_scale=0.0, out=None, ws=None):
     """rslo_surfel_normal_eq: out float64 CUDA [29] = the upper triangle of H (21), g (6), cost, pairs of the plane terms
     of the matches of surfel_nearest at pose; robust_scale > 0: Geman-McClure weights.  No host read."""
-    ptr, nbytes = _map_buf(buf)
-    src, stride = _rows3(points, "points")
-    P = points.shape[0]
-    if out is None:
-        out = torch.empty((29,), dtype=torch.float64, device=points.device)
-    if out.shape != (29,):
-        raise RsloHipError("surfel_normal_eq: out must be [29]")
-    ws = _surfel_ws(ws, P, points.device)
-    _chk(lib().rslo_surfel_normal_eq(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_normal_eq"),
-                                     float(voxel_size if max_dist is None else max_dist), float(robust_scale),
-                                     _ptr(out, torch.float64, "out"), ws.data_ptr(), ws.numel() * ws.element_size(),
-                                     _stream()), "rslo_surfel_normal_eq")
+    head, P, max_dist, out, ws = _gn_args("surfel_normal_eq", buf, points, voxel_size, max_dist, out, ws)
+    _chk(lib().rslo_surfel_normal_eq(*head, P, _pose7(pose, "surfel_normal_eq"), max_dist, float(robust_scale),
+                                     *_gn_tail(out, "out", ws)), "rslo_surfel_normal_eq")
     return out
 
 
@@ -1619,19 +1595,11 @@ def surfel_register(buf, points, pose, voxel_size, iters=4, max_dist=None, dampi
     """rslo_surfel_register: `iters` Gauss-Newton iterations of points against the surfel map; pose (float64 CUDA [7]) is
     updated IN PLACE.  Returns info float64 CUDA [iters, 8]: rows {status, pairs, cost, |dt|, theta, 0, 0, 0}, statuses
     as map_register.  No host read, a fixed number of launches: capturable."""
-    ptr, nbytes = _map_buf(buf)
-    src, stride = _rows3(points, "points")
-    P = points.shape[0]
     iters = int(iters)
-    if info is None:
-        info = torch.empty((max(iters, 0), 8), dtype=torch.float64, device=points.device)
-    if info.shape != (iters, 8):
-        raise RsloHipError("surfel_register: info must be [iters, 8]")
-    ws = _surfel_ws(ws, P, points.device)
-    _chk(lib().rslo_surfel_register(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_register"), iters,
-                                    float(voxel_size if max_dist is None else max_dist), float(damping), int(min_pairs),
-                                    float(tol_t), float(tol_r), float(robust_scale), _ptr(info, torch.float64, "info"),
-                                    ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_surfel_register")
+    head, P, max_dist, info, ws = _gn_args("surfel_register", buf, points, voxel_size, max_dist, info, ws, iters)
+    _chk(lib().rslo_surfel_register(*head, P, _pose7(pose, "surfel_register"), iters, max_dist, float(damping),
+                                    int(min_pairs), float(tol_t), float(tol_r), float(robust_scale),
+                                    *_gn_tail(info, "info", ws)), "rslo_surfel_register")
     return info
 
 
@@ -1666,18 +1634,10 @@ def surfel_normal_eq_d(buf, points, pose, voxel_size, max_dist=None, min_flag=1,
     """rslo_surfel_normal_eq_d: out float64 CUDA [29] = the upper triangle of H (21), g (6), cost, pairs of the
     distribution terms of the matches of surfel_nearest_d at pose; robust_scale > 0 (in sigmas): Geman-McClure weights.
     No host read."""
-    ptr, nbytes = _map_buf(buf)
-    src, stride = _rows3(points, "points")
-    P = points.shape[0]
-    if out is None:
-        out = torch.empty((29,), dtype=torch.float64, device=points.device)
-    if out.shape != (29,):
-        raise RsloHipError("surfel_normal_eq_d: out must be [29]")
-    ws = _surfel_ws(ws, P, points.device)
-    _chk(lib().rslo_surfel_normal_eq_d(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_normal_eq_d"),
-                                       float(voxel_size if max_dist is None else max_dist), int(min_flag), float(reg_rel),
-                                       float(reg_abs), float(robust_scale), _ptr(out, torch.float64, "out"), ws.data_ptr(),
-                                       ws.numel() * ws.element_size(), _stream()), "rslo_surfel_normal_eq_d")
+    head, P, max_dist, out, ws = _gn_args("surfel_normal_eq_d", buf, points, voxel_size, max_dist, out, ws)
+    _chk(lib().rslo_surfel_normal_eq_d(*head, P, _pose7(pose, "surfel_normal_eq_d"), max_dist, int(min_flag), float(reg_rel),
+                                       float(reg_abs), float(robust_scale), *_gn_tail(out, "out", ws)),
+         "rslo_surfel_normal_eq_d")
     return out
 
 
@@ -1685,20 +1645,11 @@ def surfel_register_d(buf, points, pose, voxel_size, iters=4, max_dist=None, dam
                       tol_r=0.0, robust_scale=0.0, min_flag=1, reg_rel=0.01, reg_abs=0.02, info=None, ws=None):
     """rslo_surfel_register_d: surfel_register with the distribution cost: pose (float64 CUDA [7]) is updated IN PLACE.
     Returns info float64 CUDA [iters, 8] as surfel_register.  No host read, a fixed number of launches: capturable."""
-    ptr, nbytes = _map_buf(buf)
-    src, stride = _rows3(points, "points")
-    P = points.shape[0]
     iters = int(iters)
-    if info is None:
-        info = torch.empty((max(iters, 0), 8), dtype=torch.float64, device=points.device)
-    if info.shape != (iters, 8):
-        raise RsloHipError("surfel_register_d: info must be [iters, 8]")
-    ws = _surfel_ws(ws, P, points.device)
-    _chk(lib().rslo_surfel_register_d(ptr, nbytes, float(voxel_size), src, stride, P, _pose7(pose, "surfel_register_d"),
-                                      iters, float(voxel_size if max_dist is None else max_dist), float(damping),
+    head, P, max_dist, info, ws = _gn_args("surfel_register_d", buf, points, voxel_size, max_dist, info, ws, iters)
+    _chk(lib().rslo_surfel_register_d(*head, P, _pose7(pose, "surfel_register_d"), iters, max_dist, float(damping),
                                       int(min_pairs), float(tol_t), float(tol_r), float(robust_scale), int(min_flag),
-                                      float(reg_rel), float(reg_abs), _ptr(info, torch.float64, "info"), ws.data_ptr(),
-                                      ws.numel() * ws.element_size(), _stream()), "rslo_surfel_register_d")
+                                      float(reg_rel), float(reg_abs), *_gn_tail(info, "info", ws)), "rslo_surfel_register_d")
     return info
 
 

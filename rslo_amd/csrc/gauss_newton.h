@@ -2,6 +2,8 @@
 // twin: rslo_amd/gauss_newton.py): the 28 addends of a matched point, the fixed-order reduction of the 29 sums over a
 // workgroup, and the damped Cholesky step on a pose.  posegraph.hip takes the scalar block sum from here.
 //
+// gn_register.h builds the registration calls' kernels, launches and argument rules on top of this file.
+//
 // Like se3.h this header carries no `#pragma clang fp contract`: its functions take the contraction state of the file
 // that includes them, so every includer places the include AFTER its own pragma and after se3.h.  All three includers
 // switch contraction off, and there every operation below rounds on its own, in the order written.
@@ -11,7 +13,7 @@
 
 // The 28 addends of a matched point at world position w with residual d, for the world-frame twist (dt, dtheta): the
 // three rows of J = [I | -[w]x]; addend of H(a, b) = J0[a]*J0[b] + J1[a]*J1[b] + J2[a]*J2[b], left to right.
-// add (a constant at every call): false ASSIGNS t28[k] = addend k, as k_mapreg_accum needs it (0.0 + (-0.0) would
+// add (a constant at every call): false ASSIGNS t28[k] = addend k, as k_gn_accum needs it (0.0 + (-0.0) would
 // lose the sign); true adds, t28[k] = t28[k] + addend k, one addend at a time.  Adding a finished array of addends
 // afterwards is the same arithmetic but holds 28 more doubles live: in k_loop_verify, which sits at the 128 registers
 // of a 1024-thread workgroup, that is 60 bytes more scratch per thread.

@@ -1,5 +1,6 @@
-// The table of the world voxel map as its kernels see it (csrc/map.hip, csrc/mapreg.hip): header and section layout,
-// the hash, and the one function that turns a point into its world position and cell.  Rules: include/rslo_hip.h
+// The table of the world voxel map as its kernels see it (csrc/map.hip, csrc/mapreg.hip; csrc/surfel.hip shares the hash,
+// the point function and the search): header and section layout, the hash, the one function that turns a point into its
+// world position and cell, and the 27-cell neighbour search.  Rules: include/rslo_hip.h
 // "World voxel map".
 #pragma once
 #include "rslo_common.h"
@@ -53,6 +54,38 @@ __device__ __forceinline__ map_u64 map_mix(map_u64 x) {      // splitmix64 final
   x *= 0x94d049bb133111ebull;
   x ^= x >> 31;
   return x;
+}
+
+// The stored cells among key + {-1,0,1}^3 in a table of `capacity` (<= 2^31) slots: visit(slot, neighbour key) for each,
+// in the order j = 9 (dx + 1) + 3 (dy + 1) + (dz + 1).  The 27 probe chains are independent 8-byte gathers into a table
+// far larger than L2, so the first-slot keys of all 27 are loaded before any of them is examined (27 loads in flight
+// per lane); a chain goes on alone, up to the bounded probe, only when its first slot held another cell's key.
+template <class Visit>
+__device__ __forceinline__ void map_neighbours(const map_u64 *keys, long long capacity, map_u64 key, Visit visit) {
+  const uint32_t mask = (uint32_t)((map_u64)capacity - 1);
+  const int c[3] = {(int)(key >> 42) & 0x1fffff, (int)(key >> 21) & 0x1fffff, (int)key & 0x1fffff};
+  map_u64 k0[27];
+  uint32_t s0[27];
+#pragma unroll
+  for (int j = 0; j < 27; ++j) {
+    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
+    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
+    s0[j] = (uint32_t)map_mix(nk) & mask;      // (a neighbour outside the key space is not examined below; its slot is in range)
+    k0[j] = keys[s0[j]];
+  }
+#pragma unroll
+  for (int j = 0; j < 27; ++j) {
+    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
+    if (x < 1 || x > 0x1fffff || y < 1 || y > 0x1fffff || z < 1 || z > 0x1fffff) continue;      // |cell| >= 2^20
+    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
+    map_u64 k = k0[j];
+    uint32_t s = s0[j];
+    for (int probe = 1; k != nk && k != MAP_KEY_NONE && probe < RSLO_MAP_MAX_PROBE; ++probe) {
+      s = (s + 1) & mask;
+      k = keys[s];
+    }
+    if (k == nk) visit(s, nk);
+  }
 }
 
 // 0: key and world position valid; 1: skipped (not finite, or outside the range gate); 2: cell outside +-2^20

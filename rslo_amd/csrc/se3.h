@@ -9,7 +9,7 @@
 // k_pose_chain is compiled with fused multiply-adds and always was.
 //
 // The rotation is summed in two ways in this project, and the two differ in the last bit:
-//   form A  v + (2 b w + 2 c)      se3_rotate: map_point, the normals of k_mapreg_accum, the pose graph;
+//   form A  v + (2 b w + 2 c)      se3_rotate: map_point, the normals of mapreg.hip's cost, the pose graph;
 //                                  host: se3.rotate, VoxelMapRef
 //   form B  (v + 2 b w) + 2 c      the translation updates of k_pose_chain (pose.hip) and gn_step (gauss_newton.h), each
 //                                  written out where it is; host: inference.pose_chain_host,

@@ -28,14 +28,12 @@
 #pragma clang fp contract(off)   /* every rule is stated operation by operation */
 
 #include "gauss_newton.h"        /* after the pragma and after map_table.h's se3.h */
+#include "gn_register.h"         /* the registration scaffold: workspace, accumulate and finish kernels, shared rules */
 
 #define SF_MAGIC 0x52534c4f53524631ull   /* "RSLOSRF1" */
 #define SF_HDR_BYTES 256
 #define SF_SLOT_BYTES 156                /* key 8 + moments 80 + row 64 + dirty 4 */
 #define SF_Q 16384.0                     /* fixed-point steps per cell edge */
-#define SF_BLOCK 256
-#define SF_WS_HDR 256                    /* register workspace: int32 word 0 is the "converged" flag */
-#define SF_MAX_ITERS 32
 #define SF_FRAMES_BLOCKS 2048u
 
 struct SurfHdr {      // int64 words: 0 magic, 1 capacity, 2-4 map parameters, 5-7 plane parameters, 8-14 counters, 15-17 prune
@@ -71,21 +69,12 @@ __device__ __forceinline__ bool sf_view(void *map, long long cap_max, SurfView &
   return true;
 }
 
-// reset, and with the cell edge the caller was checked against
-__device__ __forceinline__ bool sf_view_of(const void *map, long long cap_max, double voxel, SurfView &v) {
-  return sf_view((void *)map, cap_max, v) && v.hdr->voxel == voxel;
-}
-
 extern "C" size_t rslo_surfel_bytes(int64_t capacity) {
   if (capacity < MAP_MIN_CAP || capacity > ((int64_t)1 << 31) || (capacity & (capacity - 1))) return 0;
   return (size_t)SF_HDR_BYTES + (size_t)SF_SLOT_BYTES * (size_t)capacity;
 }
 
-static long long sf_cap_of_bytes(size_t bytes) {      // the largest capacity the allocation can hold (0: none)
-  long long cap = 0;
-  for (long long c = MAP_MIN_CAP; c <= ((long long)1 << 31) && rslo_surfel_bytes(c) <= bytes; c *= 2) cap = c;
-  return cap;
-}
+static long long sf_cap_of_bytes(size_t bytes) { return gn_cap_of_bytes(bytes, rslo_surfel_bytes); }
 
 __global__ __launch_bounds__(256) void k_surfel_reset(void *map, long long cap, double voxel, double min_range,
                                                       double max_range, int min_points, double planar_ratio,
@@ -602,39 +591,16 @@ __global__ void k_surfel_prune_done(void *map, long long cap_max, const void *ws
 // ---------------------------------------------------------------------------------------------------------------------
 // Search and registration (rules: "Nearest", "Normal equations", "Register").  Read-only on the table.
 // ---------------------------------------------------------------------------------------------------------------------
-// The planar cell whose mean is nearest to w among the cells key + {-1,0,1}^3: slot, key and d2 of the winner (smallest
-// d2, then smallest key), d = w - mean.  The first-slot keys of all 27 chains are loaded before any is examined
-// (mapreg.hip's mr_nearest); rows are read for matching cells only.  PLANAR (the plane calls): the candidates are the
+// The cell whose mean is nearest to w among the cells key + {-1,0,1}^3: slot, key and d2 of the winner (smallest d2, then
+// smallest key), d = w - mean.  Rows are read for matching cells only.  PLANAR (the plane calls): the candidates are the
 // rows with flag 2.0 and min_flag is not read; otherwise (the distribution calls) the rows with flag >= min_flag.
 template <bool PLANAR>
 __device__ __forceinline__ bool sf_nearest(const SurfView &m, map_u64 key, const double *w, double min_flag,
                                            uint32_t &bslot, map_u64 &bkey, double &bd2, double *d) {
-  const uint32_t mask = (uint32_t)((map_u64)m.hdr->capacity - 1);      // capacity <= 2^31
-  const int c[3] = {(int)(key >> 42) & 0x1fffff, (int)(key >> 21) & 0x1fffff, (int)key & 0x1fffff};
-  map_u64 k0[27];
-  uint32_t s0[27];
-#pragma unroll
-  for (int j = 0; j < 27; ++j) {
-    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
-    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
-    s0[j] = (uint32_t)map_mix(nk) & mask;      // (a neighbour outside the key space is not examined below; its slot is in range)
-    k0[j] = m.keys[s0[j]];
-  }
   bool found = false;
-#pragma unroll
-  for (int j = 0; j < 27; ++j) {
-    const int x = c[0] + j / 9 - 1, y = c[1] + (j / 3) % 3 - 1, z = c[2] + j % 3 - 1;
-    if (x < 1 || x > 0x1fffff || y < 1 || y > 0x1fffff || z < 1 || z > 0x1fffff) continue;      // |cell| >= 2^20
-    const map_u64 nk = ((map_u64)(uint32_t)x << 42) | ((map_u64)(uint32_t)y << 21) | (map_u64)(uint32_t)z;
-    map_u64 k = k0[j];
-    uint32_t s = s0[j];
-    for (int probe = 1; k != nk && k != MAP_KEY_NONE && probe < RSLO_MAP_MAX_PROBE; ++probe) {
-      s = (s + 1) & mask;
-      k = m.keys[s];
-    }
-    if (k != nk) continue;
+  map_neighbours(m.keys, m.hdr->capacity, key, [&](uint32_t s, map_u64 nk) {
     const double *row = m.rows + (size_t)s * 8;
-    if (PLANAR ? row[7] != 2.0 : !(row[7] >= min_flag)) continue;
+    if (PLANAR ? row[7] != 2.0 : !(row[7] >= min_flag)) return;
     const double dx = w[0] - row[0], dy = w[1] - row[1], dz = w[2] - row[2];
     const double d2 = dx * dx + dy * dy + dz * dz;
     if (!found || d2 < bd2 || (d2 == bd2 && nk < bkey)) {
@@ -646,79 +612,24 @@ __device__ __forceinline__ bool sf_nearest(const SurfView &m, map_u64 key, const
       d[1] = dy;
       d[2] = dz;
     }
-  }
+  });
   return found;
 }
 
-__global__ __launch_bounds__(SF_BLOCK) void k_surfel_nearest(const void *map, long long cap_max, double voxel,
-                                                             const float *__restrict__ points, int stride, int N,
-                                                             const double *__restrict__ pose, double max_dist,
-                                                             long long *__restrict__ keys_out, double *__restrict__ d2_out,
-                                                             double *__restrict__ rows_out) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N) return;
-  SurfView m;
-  long long kout = -1;
-  double d2 = -1.0;
-  map_u64 key, bkey;
-  double w[3], d[3], bd2;
-  uint32_t s;
-  const double *row = nullptr;
-  if (sf_view_of(map, cap_max, voxel, m) &&
-      !map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
-      sf_nearest<true>(m, key, w, 2.0, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
-    kout = (long long)bkey;
-    d2 = bd2;
-    row = m.rows + (size_t)s * 8;
-  }
-  keys_out[i] = kout;
-  d2_out[i] = d2;
-  if (rows_out)
-    for (int k = 0; k < 8; ++k) rows_out[(size_t)i * 8 + k] = row ? row[k] : 0.0;
+// The match of scan point p under `pose` in the map as the search calls accept it (reset, and with the cell edge the
+// caller was checked against): world position w, slot s, key and d = w - mean of the nearest candidate, closer than max_dist
+template <bool PLANAR>
+__device__ __forceinline__ bool sf_match(const void *map, long long cap_max, double voxel, const float *p, const double *pose,
+                                         double max_dist, double min_flag, SurfView &m, double *w, uint32_t &s,
+                                         map_u64 &bkey, double &bd2, double *d) {
+  map_u64 key;
+  return sf_view((void *)map, cap_max, m) && m.hdr->voxel == voxel &&
+         !map_point(p, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
+         sf_nearest<PLANAR>(m, key, w, min_flag, s, bkey, bd2, d) && bd2 < max_dist * max_dist;
 }
 
-// block partial [GN_NSUM] of the plane terms of points blockIdx.x * 256 .. + 255 at the pose in pose7.  WEIGHTED: the
-// 28 addends of a matched point are multiplied by rho = u*u, u = s2 / (s2 + e), e = r*r (s2 = scale*scale > 0).
-template <bool WEIGHTED>
-__global__ __launch_bounds__(SF_BLOCK) void k_surfel_accum(const void *map, long long cap_max, double voxel,
-                                                           const float *__restrict__ points, int stride, int N,
-                                                           const double *__restrict__ pose, double max_dist, int iter,
-                                                           const int32_t *__restrict__ flag,
-                                                           double *__restrict__ partials, double s2) {
-  if (iter > 0 && *flag) return;      // converged in an earlier iteration: the second stage does not read the partials
-  __shared__ double part[SF_BLOCK / 64 * GN_NSUM];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  double acc[GN_NSUM];
-#pragma unroll
-  for (int k = 0; k < GN_NSUM; ++k) acc[k] = 0.0;
-  SurfView m;
-  map_u64 key, bkey;
-  double w[3], d[3], bd2;
-  uint32_t s;
-  if (i < N && sf_view_of(map, cap_max, voxel, m)) {
-    if (!map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
-        sf_nearest<true>(m, key, w, 2.0, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
-      const double *row = m.rows + (size_t)s * 8;
-      const double n[3] = {row[3], row[4], row[5]};      // already in the world frame
-      double wn[3];
-      se3_cross(w, n, wn);
-      gn_plane_terms(n, wn, n[0] * d[0] + n[1] * d[1] + n[2] * d[2], acc);
-      acc[GN_NSUM - 1] = 1.0;
-      if (WEIGHTED) {
-        const double u = s2 / (s2 + acc[GN_NSUM - 2]);
-        const double rho = u * u;
-#pragma unroll
-        for (int k = 0; k < GN_NSUM - 1; ++k) acc[k] = rho * acc[k];
-      }
-    }
-  }
-  gn_block_reduce(acc, part, SF_BLOCK / 64, partials + (size_t)blockIdx.x * GN_NSUM);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Distribution cost (rules: "Distribution cost"): the matched cell's covariance, regularised and inverted, weighs the
-// whole residual d = w - mean.  The candidates are the rows with flag >= min_flag.
-// ---------------------------------------------------------------------------------------------------------------------
+// The parameters of the distribution cost (rules: "Distribution cost"): the matched cell's covariance, regularised and
+// inverted, weighs the whole residual d = w - mean.  The candidates are the rows with flag >= min_flag.
 struct SfDist {
   double min_flag, reg_rel, reg_abs;
 };
@@ -747,24 +658,24 @@ __device__ __forceinline__ bool sf_information(const long long *__restrict__ mo,
   return det > 0.0 && det < (double)__builtin_inff();
 }
 
+// PLANAR: the plane calls' search; dd and info_out are not read.  Otherwise the distribution calls', with
 // info_out row = {M00, M01, M02, M11, M12, M22, det, lam} of the matched cell (M as zeros for an unusable pair)
-__global__ __launch_bounds__(SF_BLOCK) void k_surfel_nearest_d(const void *map, long long cap_max, double voxel,
-                                                               const float *__restrict__ points, int stride, int N,
-                                                               const double *__restrict__ pose, double max_dist, SfDist dd,
-                                                               long long *__restrict__ keys_out, double *__restrict__ d2_out,
-                                                               double *__restrict__ rows_out, double *__restrict__ info_out) {
+template <bool PLANAR>
+__global__ __launch_bounds__(GN_BLOCK) void k_surfel_nearest(const void *map, long long cap_max, double voxel,
+                                                             const float *__restrict__ points, int stride, int N,
+                                                             const double *__restrict__ pose, double max_dist, SfDist dd,
+                                                             long long *__restrict__ keys_out, double *__restrict__ d2_out,
+                                                             double *__restrict__ rows_out, double *__restrict__ info_out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
   SurfView m;
   long long kout = -1;
   double d2 = -1.0;
-  map_u64 key, bkey;
+  map_u64 bkey;
   double w[3], d[3], bd2;
   uint32_t s = 0;
   bool got = false;
-  if (sf_view_of(map, cap_max, voxel, m) &&
-      !map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
-      sf_nearest<false>(m, key, w, dd.min_flag, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
+  if (sf_match<PLANAR>(map, cap_max, voxel, points + (int64_t)i * stride, pose, max_dist, dd.min_flag, m, w, s, bkey, bd2, d)) {
     kout = (long long)bkey;
     d2 = bd2;
     got = true;
@@ -775,7 +686,7 @@ __global__ __launch_bounds__(SF_BLOCK) void k_surfel_nearest_d(const void *map, 
     const double *row = got ? m.rows + (size_t)s * 8 : nullptr;
     for (int k = 0; k < 8; ++k) rows_out[(size_t)i * 8 + k] = row ? row[k] : 0.0;
   }
-  if (info_out) {
+  if (!PLANAR && info_out) {
     double v[8] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (got) {
       const bool usable = sf_information(m.mom + (size_t)s * 10, m.hdr->voxel, dd, v, v[6], v[7]);
@@ -786,86 +697,48 @@ __global__ __launch_bounds__(SF_BLOCK) void k_surfel_nearest_d(const void *map, 
   }
 }
 
-// k_surfel_accum with the distribution term.  The match comes first and leaves slot and d; only then are the winner's
-// moments read, so the 27-key arrays of sf_nearest are dead while M and the 3 x 6 product M J are live.  An unusable pair
-// adds nothing and is not counted.  WEIGHTED: rho = u*u, u = s2 / (s2 + e) on the 28 addends, e = d^T M d.
-template <bool WEIGHTED>
-__global__ __launch_bounds__(SF_BLOCK) void k_surfel_accum_d(const void *map, long long cap_max, double voxel,
-                                                             const float *__restrict__ points, int stride, int N,
-                                                             const double *__restrict__ pose, double max_dist, SfDist dd,
-                                                             int iter, const int32_t *__restrict__ flag,
-                                                             double *__restrict__ partials, double s2) {
-  if (iter > 0 && *flag) return;      // converged in an earlier iteration: the second stage does not read the partials
-  __shared__ double part[SF_BLOCK / 64 * GN_NSUM];
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  double acc[GN_NSUM];
-#pragma unroll
-  for (int k = 0; k < GN_NSUM; ++k) acc[k] = 0.0;
-  SurfView m;
-  map_u64 key, bkey;
-  double w[3], d[3], bd2;
-  uint32_t s;
-  if (i < N && sf_view_of(map, cap_max, voxel, m)) {
-    if (!map_point(points + (int64_t)i * stride, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w) &&
-        sf_nearest<false>(m, key, w, dd.min_flag, s, bkey, bd2, d) && bd2 < max_dist * max_dist) {
-      double M6[6], det, lam;
-      if (sf_information(m.mom + (size_t)s * 10, m.hdr->voxel, dd, M6, det, lam)) {
-        gn_info_terms(w, d, M6, acc);
-        acc[GN_NSUM - 1] = 1.0;
-        if (WEIGHTED) {
-          const double u = s2 / (s2 + acc[GN_NSUM - 2]);
-          const double rho = u * u;
-#pragma unroll
-          for (int k = 0; k < GN_NSUM - 1; ++k) acc[k] = rho * acc[k];
-        }
-      }
-    }
-  }
-  gn_block_reduce(acc, part, SF_BLOCK / 64, partials + (size_t)blockIdx.x * GN_NSUM);
-}
+// The plane cost: one plane term with the matched planar cell's normal, e = r*r
+struct SfPlaneCost {
+  const void *map;
+  long long cap_max;
+  double voxel;
 
-struct SfSolve {
-  int min_pairs;
-  double damping, tol_t, tol_r;
+  __device__ __forceinline__ bool terms(const float *p, const double *pose, double max_dist, double *acc) const {
+    SurfView m;
+    map_u64 bkey;
+    double w[3], d[3], bd2;
+    uint32_t s;
+    if (!sf_match<true>(map, cap_max, voxel, p, pose, max_dist, 2.0, m, w, s, bkey, bd2, d)) return false;
+    const double *row = m.rows + (size_t)s * 8;
+    const double n[3] = {row[3], row[4], row[5]};      // already in the world frame
+    double wn[3];
+    se3_cross(w, n, wn);
+    gn_plane_terms(n, wn, n[0] * d[0] + n[1] * d[1] + n[2] * d[2], acc);
+    return true;
+  }
 };
 
-// Second stage, one wave, as mapreg.hip's: lane j sums partial j of the blocks in block order.  out29
-// (rslo_surfel_normal_eq) receives the sums; with pose7 (rslo_surfel_register) lane 0 then takes the Gauss-Newton step
-// of iteration `iter` and writes its info row.  Iteration 0 does not read the flag and rewrites it: that clears it.
-__global__ __launch_bounds__(64) void k_surfel_finish(const double *__restrict__ partials, int n_blocks,
-                                                      double *__restrict__ out29, double *__restrict__ pose7, int iter,
-                                                      SfSolve sp, int32_t *__restrict__ flag, double *__restrict__ info) {
-  __shared__ double tot[GN_NSUM];
-  double *row = info ? info + (size_t)iter * 8 : nullptr;
-  if (pose7 && iter > 0 && *flag) {
-    if (threadIdx.x < 8) row[threadIdx.x] = threadIdx.x == 0 ? 3.0 : 0.0;
-    return;
+// The distribution cost, e = d^T M d.  The match comes first and leaves slot and d; only then are the winner's moments
+// read, so the 27-key arrays of the search are dead while M and the 3 x 6 product M J are live.  An unusable pair adds
+// nothing and is not counted.
+struct SfDistCost {
+  const void *map;
+  long long cap_max;
+  double voxel;
+  SfDist dd;
+
+  __device__ __forceinline__ bool terms(const float *p, const double *pose, double max_dist, double *acc) const {
+    SurfView m;
+    map_u64 bkey;
+    double w[3], d[3], bd2;
+    uint32_t s;
+    if (!sf_match<false>(map, cap_max, voxel, p, pose, max_dist, dd.min_flag, m, w, s, bkey, bd2, d)) return false;
+    double M6[6], det, lam;
+    if (!sf_information(m.mom + (size_t)s * 10, m.hdr->voxel, dd, M6, det, lam)) return false;
+    gn_info_terms(w, d, M6, acc);
+    return true;
   }
-  if (threadIdx.x < GN_NSUM) {
-    double v = 0.0;
-    for (int b = 0; b < n_blocks; ++b) v = v + partials[(size_t)b * GN_NSUM + threadIdx.x];
-    tot[threadIdx.x] = v;
-    if (out29) out29[threadIdx.x] = v;
-  }
-  __syncthreads();
-  if (!pose7 || threadIdx.x != 0) return;
-  int status = 0;
-  double nt = 0.0, th = 0.0;
-  const double pairs = tot[28], cost = tot[27];
-  if (pairs < (double)sp.min_pairs) {
-    status = 1;
-  } else if (!gn_step(tot, sp.damping, pose7, nt, th)) {
-    status = 2;      // not positive definite, or an overflowed step: no step
-    nt = th = 0.0;
-  }
-  *flag = (status == 0 && nt < sp.tol_t && th < sp.tol_r) ? 1 : 0;
-  row[0] = (double)status;
-  row[1] = pairs;
-  row[2] = cost;
-  row[3] = nt;
-  row[4] = th;
-  row[5] = row[6] = row[7] = 0.0;
-}
+};
 
 // ---------------------------------------------------------------------------------------------------------------------
 // C ABI
@@ -993,109 +866,9 @@ extern "C" int rslo_surfel_prune(void *map, size_t map_bytes, const double *cent
 
 static int sf_check(const char *name, const void *map, long long cap_max, double voxel, int stride, int N,
                     const double *pose7, double max_dist) {
-  RSLO_CHECK_ARG(map && cap_max > 0, "%s: no map (map_bytes below rslo_surfel_bytes(1024))", name);
-  RSLO_CHECK_ARG(N >= 0 && stride >= 3, "%s: N < 0 or stride_floats < 3", name);
-  RSLO_CHECK_ARG(pose7, "%s: pose7 is null", name);
-  RSLO_CHECK_ARG(voxel > 0.0 && voxel < (double)__builtin_inff(), "%s: voxel_size must be positive and finite", name);
-  RSLO_CHECK_ARG(max_dist > 0.0 && max_dist <= voxel, "%s: need 0 < max_dist <= voxel_size (NaN is refused)", name);
-  return RSLO_OK;
+  return gn_check(name, "rslo_surfel_bytes", map, cap_max, voxel, stride, N, pose7, max_dist);
 }
 
-extern "C" int rslo_surfel_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
-                                   int stride_floats, int N, const double *pose7, double max_dist, int64_t *keys_out,
-                                   double *d2_out, double *rows_out, void *stream) {
-  const long long cap_max = sf_cap_of_bytes(map_bytes);
-  const int rc = sf_check("surfel_nearest", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
-  if (rc) return rc;
-  if (N == 0) return RSLO_OK;
-  RSLO_CHECK_ARG(points && keys_out && d2_out, "surfel_nearest: null pointer");
-  hipLaunchKernelGGL(k_surfel_nearest, dim3((unsigned)rslo_cdiv(N, SF_BLOCK)), dim3(SF_BLOCK), 0, (hipStream_t)stream, map,
-                     cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, (long long *)keys_out, d2_out,
-                     rows_out);
-  RSLO_CHECK_LAUNCH("surfel_nearest");
-  return RSLO_OK;
-}
-
-extern "C" size_t rslo_surfel_register_ws_bytes(int N) {
-  if (N < 0) return 0;
-  const size_t nb = N > 0 ? (size_t)rslo_cdiv(N, SF_BLOCK) : 1;
-  return SF_WS_HDR + (nb * GN_NSUM * sizeof(double) + 255) / 256 * 256;
-}
-
-static bool sf_scale_ok(double scale) {      // the rule of "Robust weight"
-  const double s2 = scale * scale;
-  return scale == 0.0 || (scale > 0.0 && s2 > 0.0 && s2 < (double)__builtin_inff());
-}
-
-static int sf_check_sums(const char *name, const float *points, int N, double scale, void *ws, size_t ws_bytes) {
-  RSLO_CHECK_ARG(sf_scale_ok(scale), "%s: robust_scale must be 0 (no weights) or positive with a finite, non-zero square", name);
-  RSLO_CHECK_ARG(ws && ((uintptr_t)ws & 7) == 0 && (N == 0 || points),
-                 "%s: null pointer, or a workspace that is not 8-byte aligned", name);
-  if (ws_bytes < rslo_surfel_register_ws_bytes(N)) {
-    rslo_set_error("%s: workspace too small", name);
-    return RSLO_EWS;
-  }
-  return RSLO_OK;
-}
-
-// the launches of one evaluation of the normal equations (+ the step of iteration `iter` when pose_rw is given)
-static void sf_launch(const void *map, long long cap_max, double voxel, const float *points, int stride, int N,
-                      const double *pose, double max_dist, double scale, double *out29, double *pose_rw, int iter,
-                      const SfSolve &sp, double *info, void *ws, hipStream_t s) {
-  int32_t *flag = (int32_t *)ws;
-  double *partials = (double *)((unsigned char *)ws + SF_WS_HDR);
-  const int nb = (int)rslo_cdiv(N, SF_BLOCK);
-  if (nb > 0 && scale == 0.0)
-    hipLaunchKernelGGL(k_surfel_accum<false>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points, stride,
-                       N, pose, max_dist, iter, (const int32_t *)flag, partials, 0.0);
-  else if (nb > 0)
-    hipLaunchKernelGGL(k_surfel_accum<true>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points, stride,
-                       N, pose, max_dist, iter, (const int32_t *)flag, partials, scale * scale);
-  hipLaunchKernelGGL(k_surfel_finish, dim3(1), dim3(64), 0, s, (const double *)partials, nb, out29, pose_rw, iter, sp, flag,
-                     info);
-}
-
-extern "C" int rslo_surfel_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
-                                     int stride_floats, int N, const double *pose7, double max_dist, double robust_scale,
-                                     double *out29, void *ws, size_t ws_bytes, void *stream) {
-  const char *name = "surfel_normal_eq";
-  const long long cap_max = sf_cap_of_bytes(map_bytes);
-  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
-  if (rc) return rc;
-  RSLO_CHECK_ARG(out29, "%s: out29 is null", name);
-  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
-  if (rc) return rc;
-  const SfSolve sp = {0, 0.0, 0.0, 0.0};
-  sf_launch(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, out29, nullptr, 0, sp,
-            nullptr, ws, (hipStream_t)stream);
-  RSLO_CHECK_LAUNCH(name);
-  return RSLO_OK;
-}
-
-extern "C" int rslo_surfel_register(const void *map, size_t map_bytes, double voxel_size, const float *points,
-                                    int stride_floats, int N, double *pose7, int iters, double max_dist, double damping,
-                                    int min_pairs, double tol_t, double tol_r, double robust_scale, double *info, void *ws,
-                                    size_t ws_bytes, void *stream) {
-  const char *name = "surfel_register";
-  const long long cap_max = sf_cap_of_bytes(map_bytes);
-  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
-  if (rc) return rc;
-  RSLO_CHECK_ARG(iters >= 1 && iters <= SF_MAX_ITERS, "%s: iters must be in 1 .. 32", name);
-  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "%s: tol_t and tol_r must be >= 0 (NaN is refused)", name);
-  RSLO_CHECK_ARG(info, "%s: info is null", name);
-  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
-  if (rc) return rc;
-  const SfSolve sp = {min_pairs, damping, tol_t, tol_r};
-  for (int it = 0; it < iters; ++it)
-    sf_launch(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, nullptr, pose7, it, sp,
-              info, ws, (hipStream_t)stream);
-  RSLO_CHECK_LAUNCH(name);
-  return RSLO_OK;
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// Distribution cost: the three calls above with candidates of flag >= min_flag and the cell's information matrix
-// ---------------------------------------------------------------------------------------------------------------------
 static int sf_check_dist(const char *name, int min_flag, double reg_rel, double reg_abs) {
   const double inf = (double)__builtin_inff();
   RSLO_CHECK_ARG(min_flag == 1 || min_flag == 2, "%s: min_flag must be 1 or 2", name);
@@ -1104,22 +877,89 @@ static int sf_check_dist(const char *name, int min_flag, double reg_rel, double 
   return RSLO_OK;
 }
 
-static void sf_launch_d(const void *map, long long cap_max, double voxel, const float *points, int stride, int N,
-                        const double *pose, double max_dist, double scale, const SfDist &dd, double *out29, double *pose_rw,
-                        int iter, const SfSolve &sp, double *info, void *ws, hipStream_t s) {
-  int32_t *flag = (int32_t *)ws;
-  double *partials = (double *)((unsigned char *)ws + SF_WS_HDR);
-  const int nb = (int)rslo_cdiv(N, SF_BLOCK);
-  if (nb > 0 && scale == 0.0)
-    hipLaunchKernelGGL(k_surfel_accum_d<false>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points,
-                       stride, N, pose, max_dist, dd, iter, (const int32_t *)flag, partials, 0.0);
-  else if (nb > 0)
-    hipLaunchKernelGGL(k_surfel_accum_d<true>, dim3((unsigned)nb), dim3(SF_BLOCK), 0, s, map, cap_max, voxel, points,
-                       stride, N, pose, max_dist, dd, iter, (const int32_t *)flag, partials, scale * scale);
-  hipLaunchKernelGGL(k_surfel_finish, dim3(1), dim3(64), 0, s, (const double *)partials, nb, out29, pose_rw, iter, sp, flag,
-                     info);
+extern "C" size_t rslo_surfel_register_ws_bytes(int N) { return N < 0 ? 0 : gn_ws_bytes(N); }
+
+static int sf_check_sums(const char *name, const float *points, int N, double scale, void *ws, size_t ws_bytes) {
+  RSLO_CHECK_ARG(gn_scale_ok(scale), "%s: " GN_SCALE_TEXT, name);
+  return gn_check_ws(name, points, N, ws, ws_bytes);
 }
 
+// What the plane and the distribution calls share behind sf_check (and sf_check_dist): the remaining checks, the launches
+template <bool PLANAR>
+static int sf_nearest_call(const char *name, const void *map, long long cap_max, double voxel, const float *points,
+                           int stride, int N, const double *pose7, double max_dist, const SfDist &dd, int64_t *keys_out,
+                           double *d2_out, double *rows_out, double *info_out, void *stream) {
+  if (N == 0) return RSLO_OK;
+  RSLO_CHECK_ARG(points && keys_out && d2_out, "%s: null pointer", name);
+  hipLaunchKernelGGL(k_surfel_nearest<PLANAR>, dim3((unsigned)rslo_cdiv(N, GN_BLOCK)), dim3(GN_BLOCK), 0, (hipStream_t)stream,
+                     map, cap_max, voxel, points, stride, N, pose7, max_dist, dd, (long long *)keys_out, d2_out, rows_out,
+                     info_out);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
+template <class Cost>
+static int sf_normal_eq(const char *name, const Cost &cost, const float *points, int stride, int N, const double *pose7,
+                        double max_dist, double scale, double *out29, void *ws, size_t ws_bytes, void *stream) {
+  RSLO_CHECK_ARG(out29, "%s: out29 is null", name);
+  const int rc = sf_check_sums(name, points, N, scale, ws, ws_bytes);
+  if (rc) return rc;
+  gn_normal_eq(cost, points, stride, N, pose7, max_dist, scale, out29, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
+template <class Cost>
+static int sf_register(const char *name, const Cost &cost, const float *points, int stride, int N, double *pose7, int iters,
+                       double max_dist, double damping, int min_pairs, double tol_t, double tol_r, double scale,
+                       double *info, void *ws, size_t ws_bytes, void *stream) {
+  int rc = gn_check_iters(name, iters, tol_t, tol_r);
+  if (rc) return rc;
+  RSLO_CHECK_ARG(info, "%s: info is null", name);
+  rc = sf_check_sums(name, points, N, scale, ws, ws_bytes);
+  if (rc) return rc;
+  const GnSolve sp = {min_pairs, damping, tol_t, tol_r, 0, 0.0, 0.0};
+  gn_iterate(cost, points, stride, N, pose7, iters, max_dist, scale, sp, info, ws, (hipStream_t)stream);
+  RSLO_CHECK_LAUNCH(name);
+  return RSLO_OK;
+}
+
+extern "C" int rslo_surfel_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                   int stride_floats, int N, const double *pose7, double max_dist, int64_t *keys_out,
+                                   double *d2_out, double *rows_out, void *stream) {
+  const char *name = "surfel_nearest";
+  const long long cap_max = sf_cap_of_bytes(map_bytes);
+  const int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  return sf_nearest_call<true>(name, map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, SfDist{2.0, 0.0, 0.0},
+                               keys_out, d2_out, rows_out, nullptr, stream);
+}
+
+extern "C" int rslo_surfel_normal_eq(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                     int stride_floats, int N, const double *pose7, double max_dist, double robust_scale,
+                                     double *out29, void *ws, size_t ws_bytes, void *stream) {
+  const char *name = "surfel_normal_eq";
+  const SfPlaneCost cost = {map, sf_cap_of_bytes(map_bytes), voxel_size};
+  const int rc = sf_check(name, map, cost.cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  return sf_normal_eq(name, cost, points, stride_floats, N, pose7, max_dist, robust_scale, out29, ws, ws_bytes, stream);
+}
+
+extern "C" int rslo_surfel_register(const void *map, size_t map_bytes, double voxel_size, const float *points,
+                                    int stride_floats, int N, double *pose7, int iters, double max_dist, double damping,
+                                    int min_pairs, double tol_t, double tol_r, double robust_scale, double *info, void *ws,
+                                    size_t ws_bytes, void *stream) {
+  const char *name = "surfel_register";
+  const SfPlaneCost cost = {map, sf_cap_of_bytes(map_bytes), voxel_size};
+  const int rc = sf_check(name, map, cost.cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  if (rc) return rc;
+  return sf_register(name, cost, points, stride_floats, N, pose7, iters, max_dist, damping, min_pairs, tol_t, tol_r,
+                     robust_scale, info, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Distribution cost: the three calls above with candidates of flag >= min_flag and the cell's information matrix
+// ---------------------------------------------------------------------------------------------------------------------
 extern "C" int rslo_surfel_nearest_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
                                      int stride_floats, int N, const double *pose7, double max_dist, int min_flag,
                                      double reg_rel, double reg_abs, int64_t *keys_out, double *d2_out, double *rows_out,
@@ -1130,14 +970,8 @@ extern "C" int rslo_surfel_nearest_d(const void *map, size_t map_bytes, double v
   if (rc) return rc;
   rc = sf_check_dist(name, min_flag, reg_rel, reg_abs);
   if (rc) return rc;
-  if (N == 0) return RSLO_OK;
-  RSLO_CHECK_ARG(points && keys_out && d2_out, "%s: null pointer", name);
-  const SfDist dd = {(double)min_flag, reg_rel, reg_abs};
-  hipLaunchKernelGGL(k_surfel_nearest_d, dim3((unsigned)rslo_cdiv(N, SF_BLOCK)), dim3(SF_BLOCK), 0, (hipStream_t)stream,
-                     map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, dd, (long long *)keys_out, d2_out,
-                     rows_out, info_out);
-  RSLO_CHECK_LAUNCH(name);
-  return RSLO_OK;
+  return sf_nearest_call<false>(name, map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist,
+                                SfDist{(double)min_flag, reg_rel, reg_abs}, keys_out, d2_out, rows_out, info_out, stream);
 }
 
 extern "C" int rslo_surfel_normal_eq_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
@@ -1145,20 +979,12 @@ extern "C" int rslo_surfel_normal_eq_d(const void *map, size_t map_bytes, double
                                        double reg_rel, double reg_abs, double robust_scale, double *out29, void *ws,
                                        size_t ws_bytes, void *stream) {
   const char *name = "surfel_normal_eq_d";
-  const long long cap_max = sf_cap_of_bytes(map_bytes);
-  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  const SfDistCost cost = {map, sf_cap_of_bytes(map_bytes), voxel_size, {(double)min_flag, reg_rel, reg_abs}};
+  int rc = sf_check(name, map, cost.cap_max, voxel_size, stride_floats, N, pose7, max_dist);
   if (rc) return rc;
   rc = sf_check_dist(name, min_flag, reg_rel, reg_abs);
   if (rc) return rc;
-  RSLO_CHECK_ARG(out29, "%s: out29 is null", name);
-  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
-  if (rc) return rc;
-  const SfSolve sp = {0, 0.0, 0.0, 0.0};
-  const SfDist dd = {(double)min_flag, reg_rel, reg_abs};
-  sf_launch_d(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, dd, out29, nullptr, 0, sp,
-              nullptr, ws, (hipStream_t)stream);
-  RSLO_CHECK_LAUNCH(name);
-  return RSLO_OK;
+  return sf_normal_eq(name, cost, points, stride_floats, N, pose7, max_dist, robust_scale, out29, ws, ws_bytes, stream);
 }
 
 extern "C" int rslo_surfel_register_d(const void *map, size_t map_bytes, double voxel_size, const float *points,
@@ -1166,21 +992,11 @@ extern "C" int rslo_surfel_register_d(const void *map, size_t map_bytes, double 
                                       int min_pairs, double tol_t, double tol_r, double robust_scale, int min_flag,
                                       double reg_rel, double reg_abs, double *info, void *ws, size_t ws_bytes, void *stream) {
   const char *name = "surfel_register_d";
-  const long long cap_max = sf_cap_of_bytes(map_bytes);
-  int rc = sf_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
+  const SfDistCost cost = {map, sf_cap_of_bytes(map_bytes), voxel_size, {(double)min_flag, reg_rel, reg_abs}};
+  int rc = sf_check(name, map, cost.cap_max, voxel_size, stride_floats, N, pose7, max_dist);
   if (rc) return rc;
   rc = sf_check_dist(name, min_flag, reg_rel, reg_abs);
   if (rc) return rc;
-  RSLO_CHECK_ARG(iters >= 1 && iters <= SF_MAX_ITERS, "%s: iters must be in 1 .. 32", name);
-  RSLO_CHECK_ARG(tol_t >= 0.0 && tol_r >= 0.0, "%s: tol_t and tol_r must be >= 0 (NaN is refused)", name);
-  RSLO_CHECK_ARG(info, "%s: info is null", name);
-  rc = sf_check_sums(name, points, N, robust_scale, ws, ws_bytes);
-  if (rc) return rc;
-  const SfSolve sp = {min_pairs, damping, tol_t, tol_r};
-  const SfDist dd = {(double)min_flag, reg_rel, reg_abs};
-  for (int it = 0; it < iters; ++it)
-    sf_launch_d(map, cap_max, voxel_size, points, stride_floats, N, pose7, max_dist, robust_scale, dd, nullptr, pose7, it,
-                sp, info, ws, (hipStream_t)stream);
-  RSLO_CHECK_LAUNCH(name);
-  return RSLO_OK;
+  return sf_register(name, cost, points, stride_floats, N, pose7, iters, max_dist, damping, min_pairs, tol_t, tol_r,
+                     robust_scale, info, ws, ws_bytes, stream);
 }

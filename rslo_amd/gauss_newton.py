@@ -2,8 +2,8 @@
 csrc/gauss_newton.h).  The 28 sums of a set of matched points are the upper triangle of H = sum J^T J (21, row-major),
 g = sum J^T r (6) and the cost sum r.r, for the world-frame twist (dt, dtheta).  terms_of gives their addends row by row
 in the operand order of gn_point_terms / gn_plane_terms, info_terms those of gn_info_terms (H = sum J^T M J with a
-cell's information matrix M); gauss_newton_step is gn_step, scalar float64 in the order of
-the device's one thread."""
+cell's information matrix M); robust_weighted is the Geman-McClure block of k_gn_accum; gauss_newton_step is gn_step,
+scalar float64 in the order of the device's one thread; register_loop is the iteration loop of the register calls."""
 import math
 
 import numpy as np
@@ -121,3 +121,40 @@ def gauss_newton_step(sums, pose, damping=0.0):
     r += [dq[1 + a] * q[0] + q[1 + a] * dq[0] + vx[a] for a in range(3)]
     nr = math.sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3])
     return np.array(tn + [v / nr for v in r], np.float64), nt, th
+
+
+def robust_weighted(terms, scale):
+    """terms [K, 28] with every row multiplied by its Geman-McClure weight rho = u * u, u = s2 / (s2 + e), e the row's
+    cost addend and s2 = scale * scale; scale 0: the terms as they are"""
+    if scale == 0.0:
+        return terms
+    s2 = scale * scale
+    with np.errstate(all="ignore"):
+        u = s2 / (s2 + terms[:, 27])
+        rho = u * u
+        return terms * rho[:, None]
+
+
+def register_loop(normal_equations, pose, iters, damping, min_pairs, tol_t, tol_r):
+    """-> (pose [7] float64, info [iters, 8]): Gauss-Newton iterations on the 29 sums normal_equations(pose) returns.
+    Row = (status, pairs, cost, |dt|, theta, 0, 0, 0); status 1 (fewer than min_pairs pairs) and 2 (no step: not positive
+    definite, or overflowed) leave the pose as it is, status 3 marks the iterations after a step below both tolerances."""
+    pose = np.array(pose, dtype=np.float64).reshape(7)
+    info = np.zeros((int(iters), 8), np.float64)
+    done = False
+    for it in range(int(iters)):
+        if done:
+            info[it, 0] = 3.0
+            continue
+        sums = normal_equations(pose)
+        info[it, 1], info[it, 2] = sums[28], sums[27]
+        if sums[28] < min_pairs:
+            info[it, 0] = 1.0
+            continue
+        step = gauss_newton_step(sums[:28], pose, damping)
+        if step is None:
+            info[it, 0] = 2.0
+            continue
+        pose, info[it, 3], info[it, 4] = step
+        done = bool(info[it, 3] < tol_t and info[it, 4] < tol_r)
+    return pose, info

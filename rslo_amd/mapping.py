@@ -121,7 +121,7 @@ and on the pyramids MapPyramid (device) / MapPyramidRef (numpy):
 import numpy as np
 
 from . import se3
-from .gauss_newton import gauss_newton_step, point_jacobian, terms_of
+from .gauss_newton import point_jacobian, register_loop, robust_weighted, terms_of
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full")
 PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
@@ -527,14 +527,7 @@ class VoxelMapRef:
     def _weighted_terms(self, points, pose, metric="plane", max_dist=None, min_hits=1, robust_scale=0.0):
         """_pair_terms with every row multiplied by its Geman-McClure weight rho (module docstring); scale 0: as they are"""
         scale = check_scale(robust_scale)
-        terms = self._pair_terms(points, pose, metric, max_dist, min_hits)
-        if scale == 0.0:
-            return terms
-        s2 = scale * scale
-        with np.errstate(all="ignore"):
-            u = s2 / (s2 + terms[:, 27])
-            rho = u * u
-            return terms * rho[:, None]
+        return robust_weighted(self._pair_terms(points, pose, metric, max_dist, min_hits), scale)
 
     def normal_equations(self, points, pose, metric="plane", max_dist=None, min_hits=1, robust_scale=0.0):
         """[29] float64: the column sums of _pair_terms (weighted when robust_scale > 0), then the number of pairs."""
@@ -548,25 +541,8 @@ class VoxelMapRef:
         check_scale(robust_scale)
         pts = np.asarray(points)
         metric = _metric_of(metric, pts.shape[1] if pts.ndim == 2 else 0)
-        pose = np.array(pose, dtype=np.float64).reshape(7)
-        info = np.zeros((int(iters), 8), np.float64)
-        done = False
-        for it in range(int(iters)):
-            if done:
-                info[it, 0] = 3.0
-                continue
-            sums = self.normal_equations(pts, pose, metric, max_dist, min_hits, robust_scale)
-            info[it, 1], info[it, 2] = sums[28], sums[27]
-            if sums[28] < min_pairs:
-                info[it, 0] = 1.0
-                continue
-            step = gauss_newton_step(sums[:28], pose, damping)
-            if step is None:
-                info[it, 0] = 2.0
-                continue
-            pose, info[it, 3], info[it, 4] = step
-            done = bool(info[it, 3] < tol_t and info[it, 4] < tol_r)
-        return pose, info
+        return register_loop(lambda at: self.normal_equations(pts, at, metric, max_dist, min_hits, robust_scale), pose, iters,
+                             damping, min_pairs, tol_t, tol_r)
 
     def stats(self):
         return dict(self.counters, dropped_full=0)

@@ -42,7 +42,7 @@ bit.  The rules in one place:
 """
 import numpy as np
 
-from .gauss_newton import gauss_newton_step, info_terms, terms_of
+from .gauss_newton import info_terms, register_loop, robust_weighted, terms_of
 from .mapping import VoxelMapRef, _check_params, _check_register, _max_dist_of, check_scale
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full", "n_planar")
@@ -437,14 +437,7 @@ class SurfelMapRef:
 
     def _weighted_terms(self, points, pose, max_dist=None, robust_scale=0.0, dist=None):
         scale = check_scale(robust_scale)
-        terms = self._pair_terms(points, pose, max_dist, dist)
-        if scale == 0.0:
-            return terms
-        s2 = scale * scale
-        with np.errstate(all="ignore"):
-            u = s2 / (s2 + terms[:, 27])
-            rho = u * u
-            return terms * rho[:, None]
+        return robust_weighted(self._pair_terms(points, pose, max_dist, dist), scale)
 
     def normal_equations(self, points, pose, max_dist=None, robust_scale=0.0, cost="plane", min_flag=None, reg_rel=None,
                          reg_abs=None):
@@ -463,25 +456,8 @@ class SurfelMapRef:
         _check_register(iters, tol_t, tol_r)
         check_scale(robust_scale)
         _max_dist_of(max_dist, self.voxel_size)
-        pose = np.array(pose, dtype=np.float64).reshape(7)
-        info = np.zeros((int(iters), 8), np.float64)
-        done = False
-        for it in range(int(iters)):
-            if done:
-                info[it, 0] = 3.0
-                continue
-            sums = self.normal_equations(points, pose, max_dist, robust_scale, **cost_kw)
-            info[it, 1], info[it, 2] = sums[28], sums[27]
-            if sums[28] < min_pairs:
-                info[it, 0] = 1.0
-                continue
-            step = gauss_newton_step(sums[:28], pose, damping)
-            if step is None:
-                info[it, 0] = 2.0
-                continue
-            pose, info[it, 3], info[it, 4] = step
-            done = bool(info[it, 3] < tol_t and info[it, 4] < tol_r)
-        return pose, info
+        return register_loop(lambda at: self.normal_equations(points, at, max_dist, robust_scale, **cost_kw), pose, iters,
+                             damping, min_pairs, tol_t, tol_r)
 
     def stats(self):
         return dict(self.counters, dropped_full=0)
