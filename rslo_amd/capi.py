@@ -1172,6 +1172,40 @@ def _pose7(pose, name):
     return pose.data_ptr()
 
 
+def _insert_frames(name, buf, store_buf, capacity, K, poses):
+    """the body of map_insert_frames / surfel_insert_frames: rslo_<name> with the checks both make"""
+    ptr, nbytes = _map_buf(buf)
+    sptr, sbytes = _map_buf(store_buf)
+    if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float64 and poses.dim() == 2
+            and poses.shape[1] == 7 and poses.is_contiguous()):
+        raise RsloHipError("%s: poses must be contiguous float64 [n, 7] rows (t, q wxyz) on the GPU" % name)
+    if poses.device != buf.device or store_buf.device != buf.device:
+        raise RsloHipError("%s: the map, the store and the poses must live on one device" % name)
+    if poses.shape[0] == 0:      # an empty tensor has no address to hand over; the call would launch nothing
+        return
+    _chk(getattr(lib(), "rslo_" + name)(ptr, nbytes, sptr, sbytes, int(capacity), int(K), poses.data_ptr(),
+                                        int(poses.shape[0]), _stream()), "rslo_" + name)
+
+
+def _prune_ws(name, capacity, device):
+    """the body of map_prune_ws / surfel_prune_ws: rslo_<name>_bytes(capacity) bytes as an int64 tensor"""
+    nbytes = int(getattr(lib(), "rslo_%s_bytes" % name)(int(capacity)))
+    if nbytes == 0:
+        raise RsloHipError("%s: capacity must be a power of two >= 1024, got %r" % (name, capacity))
+    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+
+
+def _center3(name, center, exact):
+    """the address of a centre argument, None for None: float64 CUDA, contiguous, of 3 (exact: an export) or >= 3
+    elements (a prune)"""
+    if center is None:
+        return None
+    if not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64 and center.is_contiguous()
+            and (center.numel() == 3 if exact else center.numel() >= 3)):
+        raise RsloHipError("%s: center must be %s contiguous float64 values on the GPU" % (name, "3" if exact else ">= 3"))
+    return center.data_ptr()
+
+
 def map_reset(buf, capacity, voxel_size, min_range=0.0, max_range=float("inf")):
     """rslo_map_reset on the current stream: empties the table and writes the header (rules: include/rslo_hip.h)."""
     ptr, nbytes = _map_buf(buf)
@@ -1194,17 +1228,7 @@ def map_insert_frames(buf, store_buf, capacity, K, poses):
     handed to keyframe_reset) under its own row of poses (float64 CUDA [n, 7], contiguous, read in place), as n
     successive map_insert calls would leave the map; n is clamped to the store's entry count on the device.  Three
     launches, no workspace, no host read."""
-    ptr, nbytes = _map_buf(buf)
-    sptr, sbytes = _map_buf(store_buf)
-    if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float64 and poses.dim() == 2
-            and poses.shape[1] == 7 and poses.is_contiguous()):
-        raise RsloHipError("map_insert_frames: poses must be contiguous float64 [n, 7] rows (t, q wxyz) on the GPU")
-    if poses.device != buf.device or store_buf.device != buf.device:
-        raise RsloHipError("map_insert_frames: the map, the store and the poses must live on one device")
-    if poses.shape[0] == 0:      # an empty tensor has no address to hand over; the call would launch nothing
-        return
-    _chk(lib().rslo_map_insert_frames(ptr, nbytes, sptr, sbytes, int(capacity), int(K), poses.data_ptr(),
-                                      int(poses.shape[0]), _stream()), "rslo_map_insert_frames")
+    _insert_frames("map_insert_frames", buf, store_buf, capacity, K, poses)
 
 
 def map_lookup(buf, points, pose, hits=None, tags=None):
@@ -1231,12 +1255,10 @@ def map_export(buf, min_hits=1, center=None, radius=0.0, rows=None, tags=None, h
     R = 0 if rows is None else rows.shape[0]
     if R and (rows.shape != (R, 4) or tags is None or hits is None or tags.shape != (R,) or hits.shape != (R,)):
         raise RsloHipError("map_export: rows [R, 4], tags [R] and hits [R] go together")
-    if center is not None and not (center.is_cuda and center.dtype == torch.float64 and center.numel() == 3
-                                   and center.is_contiguous()):
-        raise RsloHipError("map_export: center must be 3 contiguous float64 values on the GPU")
+    cptr = _center3("map_export", center, exact=True)
     if counts is None:
         counts = torch.empty((2,), dtype=torch.int64, device=buf.device)
-    _chk(lib().rslo_map_export(ptr, nbytes, int(min_hits), _dp(center), float(radius),
+    _chk(lib().rslo_map_export(ptr, nbytes, int(min_hits), cptr, float(radius),
                                _ptr(rows, torch.float32, "rows") if R else None,
                                _ptr(tags, torch.int64, "tags") if R else None,
                                _ptr(hits, torch.int32, "hits") if R else None, R,
@@ -1250,10 +1272,7 @@ MAP_PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
 
 def map_prune_ws(capacity, device):
     """a workspace for map_prune on a map of `capacity` slots: rslo_map_prune_ws_bytes(capacity) bytes"""
-    nbytes = int(lib().rslo_map_prune_ws_bytes(int(capacity)))
-    if nbytes == 0:
-        raise RsloHipError("map_prune_ws: capacity must be a power of two >= 1024, got %r" % (capacity,))
-    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+    return _prune_ws("map_prune_ws", capacity, device)
 
 
 def map_prune(buf, ws, center=None, radius=0.0, min_hits=1, grace=0):
@@ -1261,12 +1280,10 @@ def map_prune(buf, ws, center=None, radius=0.0, min_hits=1, grace=0):
     else float64 CUDA, contiguous, >= 3 elements, read in place: a [7] trajectory row will do) or that have fewer than
     min_hits hits and are at least `grace` scans old, by rebuilding the table through ws (map_prune_ws).  No host read."""
     ptr, nbytes = _map_buf(buf)
-    if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64
-                                   and center.numel() >= 3 and center.is_contiguous()):
-        raise RsloHipError("map_prune: center must be >= 3 contiguous float64 values on the GPU")
+    cptr = _center3("map_prune", center, exact=False)
     if not (torch.is_tensor(ws) and ws.is_cuda and ws.is_contiguous()):
         raise RsloHipError("map_prune: ws must be a contiguous CUDA tensor (map_prune_ws)")
-    _chk(lib().rslo_map_prune(ptr, nbytes, None if center is None else center.data_ptr(), float(radius), int(min_hits),
+    _chk(lib().rslo_map_prune(ptr, nbytes, cptr, float(radius), int(min_hits),
                               int(grace), ws.data_ptr(), ws.numel() * ws.element_size(), _stream()), "rslo_map_prune")
 
 
@@ -1498,17 +1515,7 @@ def surfel_insert(buf, points, pose, ws):
 def surfel_insert_frames(buf, store_buf, capacity, K, poses):
     """rslo_surfel_insert_frames: every frame of the keyframe store store_buf under its own row of poses (float64 CUDA
     [n, 7], contiguous), as n successive surfel_insert calls would leave the table.  Three launches, no host read."""
-    ptr, nbytes = _map_buf(buf)
-    sptr, sbytes = _map_buf(store_buf)
-    if not (torch.is_tensor(poses) and poses.is_cuda and poses.dtype == torch.float64 and poses.dim() == 2
-            and poses.shape[1] == 7 and poses.is_contiguous()):
-        raise RsloHipError("surfel_insert_frames: poses must be contiguous float64 [n, 7] rows (t, q wxyz) on the GPU")
-    if poses.device != buf.device or store_buf.device != buf.device:
-        raise RsloHipError("surfel_insert_frames: the map, the store and the poses must live on one device")
-    if poses.shape[0] == 0:      # an empty tensor has no address to hand over; the call would launch nothing
-        return
-    _chk(lib().rslo_surfel_insert_frames(ptr, nbytes, sptr, sbytes, int(capacity), int(K), poses.data_ptr(),
-                                         int(poses.shape[0]), _stream()), "rslo_surfel_insert_frames")
+    _insert_frames("surfel_insert_frames", buf, store_buf, capacity, K, poses)
 
 
 def surfel_export(buf, min_flag=1, center=None, radius=0.0, keys=None, moments=None, rows=None, counts=None):
@@ -1518,12 +1525,10 @@ def surfel_export(buf, min_flag=1, center=None, radius=0.0, keys=None, moments=N
     R = 0 if keys is None else keys.shape[0]
     if R and (keys.shape != (R,) or moments is None or rows is None or moments.shape != (R, 10) or rows.shape != (R, 8)):
         raise RsloHipError("surfel_export: keys [R], moments [R, 10] and rows [R, 8] go together")
-    if center is not None and not (center.is_cuda and center.dtype == torch.float64 and center.numel() == 3
-                                   and center.is_contiguous()):
-        raise RsloHipError("surfel_export: center must be 3 contiguous float64 values on the GPU")
+    cptr = _center3("surfel_export", center, exact=True)
     if counts is None:
         counts = torch.empty((2,), dtype=torch.int64, device=buf.device)
-    _chk(lib().rslo_surfel_export(ptr, nbytes, int(min_flag), _dp(center), float(radius),
+    _chk(lib().rslo_surfel_export(ptr, nbytes, int(min_flag), cptr, float(radius),
                                   _ptr(keys, torch.int64, "keys") if R else None,
                                   _ptr(moments, torch.int64, "moments") if R else None,
                                   _ptr(rows, torch.float64, "rows") if R else None, R,
@@ -1537,10 +1542,7 @@ SURFEL_PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
 
 def surfel_prune_ws(capacity, device):
     """a workspace for surfel_prune on a map of `capacity` slots: rslo_surfel_prune_ws_bytes(capacity) bytes"""
-    nbytes = int(lib().rslo_surfel_prune_ws_bytes(int(capacity)))
-    if nbytes == 0:
-        raise RsloHipError("surfel_prune_ws: capacity must be a power of two >= 1024, got %r" % (capacity,))
-    return torch.empty((nbytes // 8,), dtype=torch.int64, device=device)
+    return _prune_ws("surfel_prune_ws", capacity, device)
 
 
 def surfel_prune(buf, ws, center=None, radius=0.0, inner_radius=0.0, min_count=1):
@@ -1549,12 +1551,10 @@ def surfel_prune(buf, ws, center=None, radius=0.0, inner_radius=0.0, min_count=1
     fewer than min_count points and lie at least inner_radius from it, by rebuilding the table through ws
     (surfel_prune_ws).  Five launches, no host read."""
     ptr, nbytes = _map_buf(buf)
-    if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64
-                                   and center.numel() >= 3 and center.is_contiguous()):
-        raise RsloHipError("surfel_prune: center must be >= 3 contiguous float64 values on the GPU")
+    cptr = _center3("surfel_prune", center, exact=False)
     if not (torch.is_tensor(ws) and ws.is_cuda and ws.is_contiguous()):
         raise RsloHipError("surfel_prune: ws must be a contiguous CUDA tensor (surfel_prune_ws)")
-    _chk(lib().rslo_surfel_prune(ptr, nbytes, None if center is None else center.data_ptr(), float(radius),
+    _chk(lib().rslo_surfel_prune(ptr, nbytes, cptr, float(radius),
                                  float(inner_radius), int(min_count), ws.data_ptr(), ws.numel() * ws.element_size(),
                                  _stream()), "rslo_surfel_prune")
 

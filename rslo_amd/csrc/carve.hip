@@ -8,17 +8,17 @@
 // on arrival order, so the image is the restatement's to the bit.
 // rslo_map_carve moves every stored cell into the sensor frame, finds its pixel by the same function, and evicts it when
 // the nearest return in a small window about that pixel lies further than the cell by a margin.  The table is then
-// rebuilt in place by the launches of rslo_map_prune (map_rebuild.h): this file adds only the scan pass and the header
+// rebuilt in place by the launches of rslo_map_prune (map_core.h): this file adds only the scan pass and the header
 // update.  All arithmetic is IEEE double without contraction, in the order the header states.
 #include "rslo_common.h"
 
 #include <math.h>
 
 #include "map_table.h"
-#include "map_rebuild.h"
 
 #pragma clang fp contract(off)
 
+#include "map_core.h"     /* the staging area and the rebuild launches of rslo_map_prune */
 #include "azimuth.h"      /* after the pragma: uncontracted here, as in deskew.hip */
 
 #define CARVE_EMPTY 0xFFFFFFFFu
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(256) void k_map_carve_scan(void *map, long long cap
 __global__ void k_map_carve_done(void *map, long long cap_max, const void *ws) {
   MapView m;
   if (threadIdx.x != 0 || !map_view(map, cap_max, m)) return;
-  const PruneCtl *ctl = (const PruneCtl *)ws;
+  const RebuildCtl *ctl = (const RebuildCtl *)ws;
   m.hdr->n_carves = m.hdr->n_carves + 1;
   if (ctl->evicted == 0) return;
   m.hdr->n_cells = ctl->kept - ctl->lost;
@@ -211,7 +211,7 @@ extern "C" int rslo_map_carve(void *map, size_t map_bytes, const uint32_t *img, 
   a.H = H, a.W = W, a.win_rows = win_rows, a.win_cols = win_cols, a.grace = grace;
   a.tan_lo = tan_lo, a.tan_hi = tan_hi, a.margin_abs = margin_abs, a.margin_rel = margin_rel, a.max_range = max_range;
   map_rebuild_begin(ws, s);
-  hipLaunchKernelGGL(k_map_carve_scan, dim3(map_rebuild_blocks(cap_max)), dim3(256), 0, s, map, cap_max, img, pose7, a, ws);
+  hipLaunchKernelGGL(k_map_carve_scan, dim3(table_blocks(cap_max)), dim3(256), 0, s, map, cap_max, img, pose7, a, ws);
   map_rebuild_table(map, cap_max, ws, s);
   hipLaunchKernelGGL(k_map_carve_done, dim3(1), dim3(64), 0, s, map, cap_max, (const void *)ws);
   RSLO_CHECK_LAUNCH("map_carve");

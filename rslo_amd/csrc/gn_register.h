@@ -126,12 +126,6 @@ static void gn_iterate(const Cost &cost, const float *points, int stride, int N,
 // ---------------------------------------------------------------------------------------------------------------------
 // The argument rules the calls share; `name` is the call's, `bytes_fn` the backend's rslo_*_bytes.
 // ---------------------------------------------------------------------------------------------------------------------
-static long long gn_cap_of_bytes(size_t bytes, size_t (*bytes_of)(int64_t)) {      // the largest capacity the allocation can hold (0: none)
-  long long cap = 0;
-  for (long long c = MAP_MIN_CAP; c <= ((long long)1 << 31) && bytes_of(c) <= bytes; c *= 2) cap = c;
-  return cap;
-}
-
 static int gn_check(const char *name, const char *bytes_fn, const void *map, long long cap_max, double voxel, int stride,
                     int N, const double *pose7, double max_dist) {
   RSLO_CHECK_ARG(map && cap_max > 0, "%s: no map (map_bytes below %s(1024))", name, bytes_fn);

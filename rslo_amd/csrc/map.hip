@@ -26,12 +26,10 @@
 #include <cstddef>
 
 #include "map_table.h"
-#include "map_rebuild.h"         /* the staging area and the rebuild launches rslo_map_carve shares (csrc/carve.hip) */
-#include "kf_store.h"            /* rslo_map_insert_frames reads a keyframe store */
 
 #pragma clang fp contract(off)   /* the cell of a point must not depend on FMA formation */
 
-#define MAP_FRAMES_BLOCKS 2048u          /* workgroups of rslo_map_insert_frames' points pass: eight per CU */
+#include "map_core.h"            /* the table's write side, shared with csrc/surfel.hip; the rebuild rslo_map_carve shares */
 
 // filled in one launch: the header by thread 0, the sections by everybody
 __global__ __launch_bounds__(256) void k_map_reset(void *map, long long cap, double voxel, double min_range,
@@ -62,48 +60,18 @@ __global__ __launch_bounds__(256) void k_map_reset(void *map, long long cap, dou
 // Point i of scan number `scan` (p: its x, y, z) under `pose` into the table: the slot's key, tag and hits, and the
 // five counters n_cells .. dropped_full of `c` -- the map's header itself (rslo_map_insert), or a workgroup's tally in
 // LDS that is added to the header once (rslo_map_insert_frames).  -> the slot, or -1 for a point that was dropped.
-// The one insert of both calls.
+// The one insert of both calls; the probe is table_slot's (map_core.h).
 template <class Counters>
 __device__ __forceinline__ int32_t map_put(const MapView &m, Counters *c, const float *__restrict__ p,
                                            const double *__restrict__ pose, map_u64 scan, uint32_t i) {
-  map_u64 key;
   double w[3];
-  const int why = map_point(p, pose, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w);
-  if (why) {
-    // both adds by every dropped lane, each to ONE address: the compiler then folds an add into one per wave.  (Given
-    // `if (why == 1) add(a, 1); else add(b, 1);` it merges the two into one add whose address differs per lane, which
-    // is issued lane by lane: 1.4 ms for a scan whose points are all dropped.)
-    atomicAdd(&c->dropped_invalid, (map_u64)(why == 1));
-    atomicAdd(&c->dropped_range, (map_u64)(why == 2));
-    return -1;
-  }
-  const map_u64 mask = (map_u64)m.hdr->capacity - 1;
-  map_u64 s = map_mix(key) & mask;
-  int found = 0;
-  for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
-    map_u64 prev = __builtin_nontemporal_load(&m.keys[s]);
-    if (prev == MAP_KEY_NONE) {
-      prev = atomicCAS(&m.keys[s], MAP_KEY_NONE, key);
-      if (prev == MAP_KEY_NONE) {
-        atomicAdd(&c->n_cells, (map_u64)1);
-        prev = key;
-      }
-    }
-    if (prev == key) {
-      found = 1;
-      break;
-    }
-    s = (s + 1) & mask;
-  }
-  if (!found) {
-    atomicAdd(&c->dropped_full, (map_u64)1);
-    return -1;
-  }
+  const int32_t s = table_slot(m, c, p, pose, w);
+  if (s < 0) return -1;
   const map_u64 tag = (scan << 32) | (map_u64)i;
   if (__builtin_nontemporal_load(&m.tags[s]) > tag) atomicMin(&m.tags[s], tag);
   atomicAdd(&m.hits[s], 1);
   atomicAdd(&c->n_points, (map_u64)1);
-  return (int32_t)s;      // capacity <= 2^31 slots (rslo_map_bytes)
+  return s;
 }
 
 __global__ __launch_bounds__(256) void k_map_insert(void *map, long long cap_max, const float *__restrict__ points,
@@ -137,63 +105,18 @@ __global__ __launch_bounds__(256) void k_map_rows(void *map, long long cap_max, 
   *(float4 *)(m.rows + (size_t)s * 4) = make_float4((float)w[0], (float)w[1], (float)w[2], width >= 4 ? p[3] : 0.f);
 }
 
-__global__ void k_map_scan_done(void *map, long long cap_max) {
-  MapView m;
-  if (threadIdx.x == 0 && map_view(map, cap_max, m)) m.hdr->n_scans = m.hdr->n_scans + 1;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // rslo_map_insert_frames: every frame of a keyframe store under its own pose, as n successive inserts would leave the
 // map (rules: include/rslo_hip.h "World voxel map").  Three launches whatever the data, no workspace.
 // ---------------------------------------------------------------------------------------------------------------------
-// n = min(the store's entry count, read here and held to the store's capacity; n_poses)
-__device__ __forceinline__ long long map_frames_n(const KfView &v, int n_poses) {
-  long long n = v.hdr->n_entries;
-  n = n < 0 ? 0 : (n > v.hdr->capacity ? v.hdr->capacity : n);
-  return n < (long long)n_poses ? n : (long long)n_poses;
-}
-
-// the five header counters an insert adds to, in the header's order (n_cells .. dropped_full)
-struct MapTally {
-  map_u64 n_cells, n_points, dropped_invalid, dropped_range, dropped_full;
+// pass 1 is k_table_frames_points (map_core.h) with this body: a valid point is put, the other lanes have nothing to do.
+// Pass 3, k_table_frames_done, is map_core.h's as well; table_insert_frames launches the three.
+struct MapFramesBody {
+  static __device__ __forceinline__ void point(const MapView &m, InsertTally *tally, bool valid, const float *p,
+                                               const double *pose, map_u64 scan, uint32_t i) {
+    if (valid) map_put(m, tally, p, pose, scan, i);
+  }
 };
-static_assert(offsetof(MapHdr, n_points) == offsetof(MapHdr, n_cells) + 8 &&
-              offsetof(MapHdr, dropped_invalid) == offsetof(MapHdr, n_cells) + 16 &&
-              offsetof(MapHdr, dropped_range) == offsetof(MapHdr, n_cells) + 24 &&
-              offsetof(MapHdr, dropped_full) == offsetof(MapHdr, n_cells) + 32, "MapTally mirrors the header's counters");
-
-// pass 1: one thread per (frame, row) in tiles of 256 rows, bpf tiles per frame; frame, pose and count are uniform over
-// a tile.  A workgroup takes tiles blockIdx.x, blockIdx.x + gridDim.x, ... and counts in LDS: with the header as the
-// sink every WAVE would add to the same few words, and adds to one address are served one after the other on the
-// memory side -- measured at 0.8 us per wave, 45 ms for 4096 frames -- so the header gets one add per workgroup and
-// non-zero counter.  The scan number of frame e is n_scans + e: the header's n_scans does not change before pass 3.
-__global__ __launch_bounds__(256) void k_map_frames_points(void *map, long long cap_max, void *store, size_t store_bytes,
-                                                           long long kf_cap, int K, const double *__restrict__ poses,
-                                                           int n_poses, int bpf) {
-  __shared__ MapTally tally;
-  if (threadIdx.x < 5) ((map_u64 *)&tally)[threadIdx.x] = 0;
-  __syncthreads();
-  MapView m;
-  KfView v;
-  if (!map_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;      // uniform over the grid
-  const long long tiles = map_frames_n(v, n_poses) * bpf;
-  const map_u64 s0 = m.hdr->n_scans;
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const long long e = tile / bpf;
-    const int i = (int)(tile % bpf) * 256 + (int)threadIdx.x;
-    int count = v.counts[e];
-    count = count < 0 ? 0 : (count > K ? K : count);
-    if (i >= count) continue;
-    const float4 r = *(const float4 *)(v.rows + ((size_t)e * K + i) * 4);
-    const float p[3] = {r.x, r.y, r.z};
-    map_put(m, &tally, p, poses + (size_t)e * 7, s0 + (map_u64)e, (uint32_t)i);
-  }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    const map_u64 add = ((map_u64 *)&tally)[threadIdx.x];
-    if (add) atomicAdd(&m.hdr->n_cells + threadIdx.x, add);
-  }
-}
 
 // pass 2, over the SLOTS: behind the kernel boundary the tags are final.  A tag whose scan number lies in
 // [n_scans, n_scans + n) was set by pass 1 (older cells carry smaller scan numbers and are never re-owned) and names
@@ -205,7 +128,7 @@ __global__ __launch_bounds__(256) void k_map_frames_rows(void *map, long long ca
   MapView m;
   KfView v;
   if (!map_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;
-  const map_u64 n = (map_u64)map_frames_n(v, n_poses), s0 = m.hdr->n_scans;
+  const map_u64 n = (map_u64)table_frames_n(v, n_poses), s0 = m.hdr->n_scans;
   const long long cap = m.hdr->capacity;
   for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
     if (m.keys[s] == MAP_KEY_NONE) continue;
@@ -220,15 +143,6 @@ __global__ __launch_bounds__(256) void k_map_frames_rows(void *map, long long ca
     if (map_point(p, poses + (size_t)e * 7, m.hdr->voxel, m.hdr->min_range, m.hdr->max_range, key, w)) continue;
     *(float4 *)(m.rows + (size_t)s * 4) = make_float4((float)w[0], (float)w[1], (float)w[2], r.w);
   }
-}
-
-// pass 3: an empty frame still counts as a scan
-__global__ void k_map_frames_done(void *map, long long cap_max, void *store, size_t store_bytes, long long kf_cap, int K,
-                                  int n_poses) {
-  MapView m;
-  KfView v;
-  if (threadIdx.x != 0 || !map_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;
-  m.hdr->n_scans = m.hdr->n_scans + (map_u64)map_frames_n(v, n_poses);
 }
 
 __global__ __launch_bounds__(256) void k_map_lookup(void *map, long long cap_max, const float *__restrict__ points,
@@ -291,13 +205,13 @@ __global__ __launch_bounds__(256) void k_map_export(void *map, long long cap_max
 // ---------------------------------------------------------------------------------------------------------------------
 // rslo_map_prune: evict far and sparse cells by rebuilding the table (rules: include/rslo_hip.h "Rolling local map").
 // Workspace: control block (256 bytes, zeroed by the first, one-thread launch) | staged keys u64 [cap] |
-// tags u64 [cap] | rows f32 [cap, 4] | hits i32 [cap] -- the map's own section layout (map_rebuild.h).
+// tags u64 [cap] | rows f32 [cap, 4] | hits i32 [cap] -- the map's own section layout (map_core.h).
 // ---------------------------------------------------------------------------------------------------------------------
 // the control block starts every call at zero
-__global__ void k_map_prune_begin(void *ws) {
+__global__ void k_table_rebuild_begin(void *ws) {
   if (threadIdx.x == 0) {
-    PruneCtl *ctl = (PruneCtl *)ws;
-    ctl->kept = ctl->evicted = ctl->lost = 0;
+    RebuildCtl *ctl = (RebuildCtl *)ws;
+    ctl->kept = ctl->evicted = ctl->lost = ctl->planar = 0;
   }
 }
 
@@ -340,7 +254,7 @@ __global__ __launch_bounds__(256) void k_map_prune_scan(void *map, long long cap
 __global__ __launch_bounds__(256) void k_map_prune_clear(void *map, long long cap_max, const void *ws) {
   MapView m;
   if (!map_view(map, cap_max, m)) return;
-  if (((const PruneCtl *)ws)->evicted == 0) return;
+  if (((const RebuildCtl *)ws)->evicted == 0) return;
   const long long cap = m.hdr->capacity;
   for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
     m.keys[s] = MAP_KEY_NONE;
@@ -350,42 +264,21 @@ __global__ __launch_bounds__(256) void k_map_prune_clear(void *map, long long ca
   }
 }
 
-// pass 3: the staged keys are distinct, so whoever wins the CAS on a slot owns it and writes the rest with plain
-// stores; the kernel boundary publishes them.  The same bounded probe as the insert: a record without a slot is lost whole.
-__global__ __launch_bounds__(256) void k_map_prune_reinsert(void *map, long long cap_max, void *ws) {
-  MapView m;
-  if (!map_view(map, cap_max, m)) return;
-  const long long cap = m.hdr->capacity;
-  const PruneStage st = prune_stage(ws, cap);
-  if (st.ctl->evicted == 0) return;
-  const long long n = (long long)st.ctl->kept < cap ? (long long)st.ctl->kept : cap;
-  const map_u64 mask = (map_u64)cap - 1;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const map_u64 key = st.keys[i];
-    map_u64 s = map_mix(key) & mask;
-    bool found = false;
-    for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
-      // a stale read can only show "empty": in this launch a key goes from empty to set and never back
-      if (__builtin_nontemporal_load(&m.keys[s]) == MAP_KEY_NONE &&
-          atomicCAS(&m.keys[s], MAP_KEY_NONE, key) == MAP_KEY_NONE) {
-        found = true;
-        break;
-      }
-      s = (s + 1) & mask;
-    }
-    if (found) {
-      m.tags[s] = st.tags[i];
-      *(float4 *)(m.rows + (size_t)s * 4) = st.rows[i];
-      m.hits[s] = st.hits[i];
-    }
-    atomicAdd(&st.ctl->lost, (map_u64)(!found));
+// pass 3 is k_table_reinsert (map_core.h) over these records: the CAS winner alone writes tag / row / hits of its slot
+struct MapRecords {
+  static __device__ __forceinline__ PruneStage stage(void *ws, long long cap) { return prune_stage(ws, cap); }
+  static __device__ __forceinline__ unsigned put(const MapView &m, const PruneStage &st, size_t i, size_t s) {
+    m.tags[s] = st.tags[i];
+    *(float4 *)(m.rows + s * 4) = st.rows[i];
+    m.hits[s] = st.hits[i];
+    return 0;
   }
-}
+};
 
 __global__ void k_map_prune_done(void *map, long long cap_max, const void *ws) {
   MapView m;
   if (threadIdx.x != 0 || !map_view(map, cap_max, m)) return;
-  const PruneCtl *ctl = (const PruneCtl *)ws;
+  const RebuildCtl *ctl = (const RebuildCtl *)ws;
   m.hdr->n_prunes = m.hdr->n_prunes + 1;
   if (ctl->evicted == 0) return;
   m.hdr->n_cells = ctl->kept - ctl->lost;
@@ -430,13 +323,13 @@ extern "C" int rslo_map_insert(void *map, size_t map_bytes, const float *points,
       rslo_set_error("map_insert: workspace too small");
       return RSLO_EWS;
     }
-    int32_t *slot_of = (int32_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    int32_t *slot_of = table_slot_of(ws);
     const unsigned nb = (unsigned)rslo_cdiv(N, 256);
     hipLaunchKernelGGL(k_map_insert, dim3(nb), dim3(256), 0, s, map, cap_max, points, stride_floats, N, pose7, slot_of);
     hipLaunchKernelGGL(k_map_rows, dim3(nb), dim3(256), 0, s, map, cap_max, points, stride_floats, width, N, pose7,
                        (const int32_t *)slot_of);
   }
-  hipLaunchKernelGGL(k_map_scan_done, dim3(1), dim3(64), 0, s, map, cap_max);      // N == 0 still counts as a scan
+  hipLaunchKernelGGL(k_table_scan_done<MapView>, dim3(1), dim3(64), 0, s, map, cap_max);      // N == 0 still counts as a scan
   RSLO_CHECK_LAUNCH("map_insert");
   return RSLO_OK;
 }
@@ -445,26 +338,11 @@ extern "C" int rslo_map_insert_frames(void *map, size_t map_bytes, const void *s
                                       int K, const double *poses, int n_poses, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const long long cap_max = map_cap_of_bytes(map_bytes);
-  RSLO_CHECK_ARG(map && cap_max > 0, "map_insert_frames: no map (map_bytes below rslo_map_bytes(1024))");
-  RSLO_CHECK_ARG(store && ((uintptr_t)store & 15) == 0, "map_insert_frames: store is null or not 16-byte aligned");
-  RSLO_CHECK_ARG(kf_shape_ok(capacity, K),
-                 "map_insert_frames: need capacity in 1 .. 2^16 and K a multiple of 64 in 64 .. 4096");
-  RSLO_CHECK_ARG(store_bytes >= kf_bytes_of(capacity, K), "map_insert_frames: store_bytes is smaller than rslo_keyframe_bytes");
-  RSLO_CHECK_ARG(poses, "map_insert_frames: poses is null");
-  RSLO_CHECK_ARG(n_poses >= 0, "map_insert_frames: n_poses < 0");
-  if (n_poses == 0) return RSLO_OK;
-  const int frames = n_poses < capacity ? n_poses : (int)capacity;      // the store holds no more
-  const int bpf = rslo_cdiv(K, 256);
-  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
-  const unsigned tiles = (unsigned)frames * (unsigned)bpf;      // <= 2^16 * 16
-  hipLaunchKernelGGL(k_map_frames_points, dim3(tiles < MAP_FRAMES_BLOCKS ? tiles : MAP_FRAMES_BLOCKS), dim3(256), 0, s, map,
-                     cap_max, (void *)store, store_bytes, (long long)capacity, K, poses, n_poses, bpf);
-  hipLaunchKernelGGL(k_map_frames_rows, dim3(nb), dim3(256), 0, s, map, cap_max, (void *)store, store_bytes,
-                     (long long)capacity, K, poses, n_poses);
-  hipLaunchKernelGGL(k_map_frames_done, dim3(1), dim3(64), 0, s, map, cap_max, (void *)store, store_bytes, (long long)capacity,
-                     K, n_poses);
-  RSLO_CHECK_LAUNCH("map_insert_frames");
-  return RSLO_OK;
+  return table_insert_frames<MapView, MapFramesBody>(
+      "map_insert_frames", "rslo_map_bytes", map, cap_max, store, store_bytes, capacity, K, poses, n_poses, s, [&](unsigned nb) {
+        hipLaunchKernelGGL(k_map_frames_rows, dim3(nb), dim3(256), 0, s, map, cap_max, (void *)store, store_bytes,
+                           (long long)capacity, K, poses, n_poses);
+      });
 }
 
 extern "C" int rslo_map_lookup(const void *map, size_t map_bytes, const float *points, int stride_floats, int N,
@@ -491,20 +369,20 @@ extern "C" int rslo_map_export(const void *map, size_t map_bytes, int min_hits, 
   RSLO_CHECK_ARG(max_rows == 0 || (rows && tags && hits), "map_export: null output");
   RSLO_CHECK_ARG(!center3 || radius >= 0.0, "map_export: radius must be >= 0 (NaN is refused)");
   RSLO_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s));
-  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  const unsigned nb = table_blocks(cap_max);
   hipLaunchKernelGGL(k_map_export, dim3(nb), dim3(256), 0, s, (void *)map, cap_max, min_hits, center3, radius, rows,
                      (map_u64 *)tags, hits, (long long)max_rows, (map_u64 *)counts);
   RSLO_CHECK_LAUNCH("map_export");
   return RSLO_OK;
 }
 
-// the launches of a rebuild that do not depend on who removes the cells (map_rebuild.h)
-void map_rebuild_begin(void *ws, hipStream_t s) { hipLaunchKernelGGL(k_map_prune_begin, dim3(1), dim3(64), 0, s, ws); }
+// the launches of a rebuild that do not depend on who removes the cells (map_core.h)
+void map_rebuild_begin(void *ws, hipStream_t s) { hipLaunchKernelGGL(k_table_rebuild_begin, dim3(1), dim3(64), 0, s, ws); }
 
 void map_rebuild_table(void *map, long long cap_max, void *ws, hipStream_t s) {
-  const unsigned nb = map_rebuild_blocks(cap_max);
+  const unsigned nb = table_blocks(cap_max);
   hipLaunchKernelGGL(k_map_prune_clear, dim3(nb), dim3(256), 0, s, map, cap_max, (const void *)ws);
-  hipLaunchKernelGGL(k_map_prune_reinsert, dim3(nb), dim3(256), 0, s, map, cap_max, ws);
+  hipLaunchKernelGGL((k_table_reinsert<MapView, MapRecords>), dim3(nb), dim3(256), 0, s, map, cap_max, ws);
 }
 
 extern "C" size_t rslo_map_prune_ws_bytes(int64_t capacity) {
@@ -524,7 +402,7 @@ extern "C" int rslo_map_prune(void *map, size_t map_bytes, const double *center3
     rslo_set_error("map_prune: workspace too small");
     return RSLO_EWS;
   }
-  const unsigned nb = map_rebuild_blocks(cap_max);
+  const unsigned nb = table_blocks(cap_max);
   map_rebuild_begin(ws, s);
   hipLaunchKernelGGL(k_map_prune_scan, dim3(nb), dim3(256), 0, s, map, cap_max, center3, radius, min_hits, grace, ws);
   map_rebuild_table(map, cap_max, ws, s);

@@ -1,7 +1,7 @@
 // The table of the world voxel map as its kernels see it (csrc/map.hip, csrc/mapreg.hip; csrc/surfel.hip shares the hash,
 // the point function and the search): header and section layout, the hash, the one function that turns a point into its
-// world position and cell, and the 27-cell neighbour search.  Rules: include/rslo_hip.h
-// "World voxel map".
+// world position and cell, and the 27-cell neighbour search.  The write side of the table, which the surfel map shares
+// too, is map_core.h.  Rules: include/rslo_hip.h "World voxel map".
 #pragma once
 #include "rslo_common.h"
 
@@ -15,6 +15,17 @@ typedef unsigned long long map_u64;
 #define MAP_HDR_BYTES 256
 #define MAP_MAXC 1048576.0               /* 2^20: |cell| of a stored point is below it */
 #define MAP_MIN_CAP 1024
+#define MAP_SLOT_BYTES 36                /* key 8 + tag 8 + row 16 + hits 4 */
+
+// host: the largest capacity that an allocation of `bytes` can hold of a table with this header and slot size (0: none)
+static inline long long table_cap_of_bytes(size_t bytes, size_t hdr_bytes, size_t slot_bytes) {
+  if (bytes < hdr_bytes + slot_bytes * MAP_MIN_CAP) return 0;
+  const size_t slots = (bytes - hdr_bytes) / slot_bytes;
+  long long cap = MAP_MIN_CAP;
+  while ((size_t)cap * 2 <= slots && cap < ((long long)1 << 31)) cap *= 2;
+  return cap;
+}
+static inline long long map_cap_of_bytes(size_t bytes) { return table_cap_of_bytes(bytes, MAP_HDR_BYTES, MAP_SLOT_BYTES); }
 
 struct MapHdr {                          // int64 words: 0 magic, 1 capacity, 2-4 parameters, 5-7 prune counters, 8-13 counters,
   map_u64 magic;                         // 14-15 carve counters
@@ -46,6 +57,7 @@ __device__ __forceinline__ bool map_view(void *map, long long cap_max, MapView &
   v.hits = (int32_t *)(p + (size_t)cap * 32);
   return true;
 }
+__device__ __forceinline__ bool table_view(void *map, long long cap_max, MapView &v) { return map_view(map, cap_max, v); }
 
 __device__ __forceinline__ map_u64 map_mix(map_u64 x) {      // splitmix64 finaliser
   x ^= x >> 30;

@@ -30,8 +30,6 @@
 #define MR_MAX_SCHED_ITERS 64              /* sum of the iterations of a schedule */
 #define MR_MAX_LEVELS 8
 
-static long long mr_cap_max(size_t bytes) { return gn_cap_of_bytes(bytes, rslo_map_bytes); }
-
 // The stored point nearest to w among the cells key + {-1,0,1}^3: slot and d2 of the winner (smallest d2, then smallest
 // tag), its position in mm.  False when no candidate cell is stored with hits >= min_hits.  Rows, hits and tags are read
 // for stored cells only, a tag only to break a tie on d2.
@@ -120,7 +118,7 @@ struct MrCost {
 };
 
 extern "C" int rslo_map_params(const void *map, size_t map_bytes, double *params3_host, void *stream) {
-  RSLO_CHECK_ARG(map && mr_cap_max(map_bytes) > 0, "map_params: no map (map_bytes below rslo_map_bytes(1024))");
+  RSLO_CHECK_ARG(map && map_cap_of_bytes(map_bytes) > 0, "map_params: no map (map_bytes below rslo_map_bytes(1024))");
   RSLO_CHECK_ARG(params3_host, "map_params: params3_host is null");
   long long words[5];
   RSLO_HIP(hipMemcpyAsync(words, map, sizeof(words), hipMemcpyDeviceToHost, (hipStream_t)stream));
@@ -138,7 +136,7 @@ static int mr_check(const char *name, const void *map, long long cap_max, double
 extern "C" int rslo_map_nearest(const void *map, size_t map_bytes, double voxel_size, const float *points,
                                 int stride_floats, int N, const double *pose7, double max_dist, int min_hits,
                                 int64_t *tags_out, double *d2_out, float *rows_out, void *stream) {
-  const long long cap_max = mr_cap_max(map_bytes);
+  const long long cap_max = map_cap_of_bytes(map_bytes);
   const int rc = mr_check("map_nearest", map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
   if (rc) return rc;
   if (N == 0) return RSLO_OK;
@@ -164,7 +162,7 @@ static int mr_check_sums(const char *name, const float *points, int stride, int 
 static int mr_normal_eq(const char *name, const void *map, size_t map_bytes, double voxel_size, const float *points,
                         int stride_floats, int width, int N, const double *pose7, int metric, double max_dist,
                         int min_hits, double scale, double *out29, void *ws, size_t ws_bytes, void *stream) {
-  const long long cap_max = mr_cap_max(map_bytes);
+  const long long cap_max = map_cap_of_bytes(map_bytes);
   int rc = mr_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
   if (rc) return rc;
   RSLO_CHECK_ARG(out29, "%s: out29 is null", name);
@@ -196,7 +194,7 @@ static int mr_register(const char *name, const void *map, size_t map_bytes, doub
                        int stride_floats, int width, int N, double *pose7, int iters, int metric, double max_dist,
                        int min_hits, double damping, int min_pairs, double tol_t, double tol_r, double scale, double *info,
                        void *ws, size_t ws_bytes, void *stream) {
-  const long long cap_max = mr_cap_max(map_bytes);
+  const long long cap_max = map_cap_of_bytes(map_bytes);
   int rc = mr_check(name, map, cap_max, voxel_size, stride_floats, N, pose7, max_dist);
   if (rc) return rc;
   rc = gn_check_iters(name, iters, tol_t, tol_r);
@@ -242,7 +240,7 @@ extern "C" int rslo_map_register_sched(const void *const *maps, const size_t *ma
   RSLO_CHECK_ARG(n_stages >= 1 && n_stages <= MR_MAX_SCHED_ITERS, "%s: n_stages must be in 1 .. 64", name);
   long long cap_max[MR_MAX_LEVELS];
   for (int l = 0; l < n_levels; ++l) {
-    cap_max[l] = mr_cap_max(map_bytes[l]);
+    cap_max[l] = map_cap_of_bytes(map_bytes[l]);
     RSLO_CHECK_ARG(maps[l] && cap_max[l] > 0, "%s: level %d has no map (null, or map_bytes below rslo_map_bytes(1024))", name, l);
     RSLO_CHECK_ARG(voxel_sizes[l] > 0.0 && voxel_sizes[l] < (double)__builtin_inff(),
                    "%s: voxel_sizes[%d] must be positive and finite", name, l);

@@ -3,7 +3,8 @@
 // no scan normals (rules: include/rslo_hip.h "Surfel map"; float64 restatement: rslo_amd/surfels.py SurfelMapRef).
 //
 // One caller-owned allocation: header (256 bytes) | keys u64 [cap] | moments i64 [cap, 10] | rows f64 [cap, 8] |
-// dirty i32 [cap].  The table is the world voxel map's (map_table.h: map_point, map_mix, the bounded probe).
+// dirty i32 [cap].  The table is the world voxel map's (map_table.h: map_point, map_mix, the bounded probe; map_core.h:
+// the claim probe, the insert_frames scaffold and the rebuild's re-insert pass).
 //
 // Order freedom.  A point adds fixed-point INTEGERS to its cell -- count, the three first and the six second moments of
 // its position inside the cell in units of voxel / 16384 -- by 64-bit integer atomics (the lanes of a wave that follow
@@ -23,10 +24,10 @@
 #include <math.h>
 
 #include "map_table.h"
-#include "kf_store.h"            /* rslo_surfel_insert_frames reads a keyframe store */
 
 #pragma clang fp contract(off)   /* every rule is stated operation by operation */
 
+#include "map_core.h"            /* the table's write side, shared with csrc/map.hip */
 #include "gauss_newton.h"        /* after the pragma and after map_table.h's se3.h */
 #include "gn_register.h"         /* the registration scaffold: workspace, accumulate and finish kernels, shared rules */
 
@@ -34,7 +35,6 @@
 #define SF_HDR_BYTES 256
 #define SF_SLOT_BYTES 156                /* key 8 + moments 80 + row 64 + dirty 4 */
 #define SF_Q 16384.0                     /* fixed-point steps per cell edge */
-#define SF_FRAMES_BLOCKS 2048u
 
 struct SurfHdr {      // int64 words: 0 magic, 1 capacity, 2-4 map parameters, 5-7 plane parameters, 8-14 counters, 15-17 prune
   map_u64 magic;
@@ -47,6 +47,7 @@ struct SurfHdr {      // int64 words: 0 magic, 1 capacity, 2-4 map parameters, 5
 };
 static_assert(sizeof(SurfHdr) <= SF_HDR_BYTES, "surfel header");
 static_assert(offsetof(SurfHdr, n_prunes) == 8 * RSLO_SURFEL_HDR_PRUNE, "the prune counters are header words 15 .. 17");
+static_assert(table_tally_mirrors<SurfHdr>(), "InsertTally mirrors the header's counters");
 
 struct SurfView {
   SurfHdr *hdr;
@@ -68,13 +69,14 @@ __device__ __forceinline__ bool sf_view(void *map, long long cap_max, SurfView &
   v.dirty = (int32_t *)(p + (size_t)cap * 152);
   return true;
 }
+__device__ __forceinline__ bool table_view(void *map, long long cap_max, SurfView &v) { return sf_view(map, cap_max, v); }
 
 extern "C" size_t rslo_surfel_bytes(int64_t capacity) {
   if (capacity < MAP_MIN_CAP || capacity > ((int64_t)1 << 31) || (capacity & (capacity - 1))) return 0;
   return (size_t)SF_HDR_BYTES + (size_t)SF_SLOT_BYTES * (size_t)capacity;
 }
 
-static long long sf_cap_of_bytes(size_t bytes) { return gn_cap_of_bytes(bytes, rslo_surfel_bytes); }
+static long long sf_cap_of_bytes(size_t bytes) { return table_cap_of_bytes(bytes, SF_HDR_BYTES, SF_SLOT_BYTES); }
 
 __global__ __launch_bounds__(256) void k_surfel_reset(void *map, long long cap, double voxel, double min_range,
                                                       double max_range, int min_points, double planar_ratio,
@@ -105,52 +107,16 @@ __global__ __launch_bounds__(256) void k_surfel_reset(void *map, long long cap, 
   }
 }
 
-// the five header counters an insert adds to, in the header's order (n_cells .. dropped_full)
-struct SurfTally {
-  map_u64 n_cells, n_points, dropped_invalid, dropped_range, dropped_full;
-};
-static_assert(offsetof(SurfHdr, n_points) == offsetof(SurfHdr, n_cells) + 8 &&
-              offsetof(SurfHdr, dropped_invalid) == offsetof(SurfHdr, n_cells) + 16 &&
-              offsetof(SurfHdr, dropped_range) == offsetof(SurfHdr, n_cells) + 24 &&
-              offsetof(SurfHdr, dropped_full) == offsetof(SurfHdr, n_cells) + 32, "SurfTally mirrors the header's counters");
-
-// One point (p: x, y, z) under `pose` into the table: the probe of map.hip's map_put; counters go to `c`, the header
-// itself or a workgroup's tally in LDS.  -> the slot and the point's fixed-point position q in its cell, or -1 for a
-// point that was dropped.  The one probe of both calls.
+// One point (p: x, y, z) under `pose` into the table, by table_slot (map_core.h); counters go to `c`, the header itself
+// or a workgroup's tally in LDS.  -> the slot and the point's fixed-point position q in its cell, or -1 for a point
+// that was dropped.  The one probe of both calls.
 template <class Counters>
 __device__ __forceinline__ int32_t sf_slot(const SurfView &m, Counters *c, const float *__restrict__ p,
                                            const double *__restrict__ pose, long long *q) {
-  map_u64 key;
   double w[3];
   const double voxel = m.hdr->voxel;
-  const int why = map_point(p, pose, voxel, m.hdr->min_range, m.hdr->max_range, key, w);
-  if (why) {      // both adds by every dropped lane, each to one address (see map_put)
-    atomicAdd(&c->dropped_invalid, (map_u64)(why == 1));
-    atomicAdd(&c->dropped_range, (map_u64)(why == 2));
-    return -1;
-  }
-  const map_u64 mask = (map_u64)m.hdr->capacity - 1;
-  map_u64 s = map_mix(key) & mask;
-  int found = 0;
-  for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
-    map_u64 prev = __builtin_nontemporal_load(&m.keys[s]);      // a stale read can only show "empty": then the CAS decides
-    if (prev == MAP_KEY_NONE) {
-      prev = atomicCAS(&m.keys[s], MAP_KEY_NONE, key);
-      if (prev == MAP_KEY_NONE) {
-        atomicAdd(&c->n_cells, (map_u64)1);
-        prev = key;
-      }
-    }
-    if (prev == key) {
-      found = 1;
-      break;
-    }
-    s = (s + 1) & mask;
-  }
-  if (!found) {
-    atomicAdd(&c->dropped_full, (map_u64)1);
-    return -1;
-  }
+  const int32_t s = table_slot(m, c, p, pose, w);
+  if (s < 0) return -1;
   for (int a = 0; a < 3; ++a) {
     const double sc = w[a] / voxel;
     const double f = sc - floor(sc);                     // 1.0 for a tiny negative sc: the clamp below is part of the rule
@@ -158,7 +124,7 @@ __device__ __forceinline__ int32_t sf_slot(const SurfView &m, Counters *c, const
     q[a] = v < 0 ? 0 : (v > 16383 ? 16383 : v);
   }
   atomicAdd(&c->n_points, (map_u64)1);
-  return (int32_t)s;      // capacity <= 2^31 slots
+  return s;
 }
 
 // The ten adds of a wave's points, called by EVERY lane of the wave (s = -1: nothing to add).  Consecutive points of a
@@ -305,52 +271,20 @@ __global__ __launch_bounds__(256) void k_surfel_derive_scan(void *map, long long
   if (ok && threadIdx.x == 0 && moved) atomicAdd(&m.hdr->n_planar, (map_u64)(long long)moved);
 }
 
-__global__ void k_surfel_scan_done(void *map, long long cap_max) {
-  SurfView m;
-  if (threadIdx.x == 0 && sf_view(map, cap_max, m)) m.hdr->n_scans = m.hdr->n_scans + 1;
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // rslo_surfel_insert_frames: every frame of a keyframe store under its own pose.  Three launches whatever the data.
 // ---------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long sf_frames_n(const KfView &v, int n_poses) {
-  long long n = v.hdr->n_entries;
-  n = n < 0 ? 0 : (n > v.hdr->capacity ? v.hdr->capacity : n);
-  return n < (long long)n_poses ? n : (long long)n_poses;
-}
-
-// pass 1: one thread per (frame, row) in tiles of 256 rows, bpf tiles per frame; a workgroup takes tiles blockIdx.x,
-// blockIdx.x + gridDim.x, ... and counts in LDS: the header gets one add per workgroup and non-zero counter (map.hip).
-__global__ __launch_bounds__(256) void k_surfel_frames_points(void *map, long long cap_max, void *store, size_t store_bytes,
-                                                              long long kf_cap, int K, const double *__restrict__ poses,
-                                                              int n_poses, int bpf) {
-  __shared__ SurfTally tally;
-  if (threadIdx.x < 5) ((map_u64 *)&tally)[threadIdx.x] = 0;
-  __syncthreads();
-  SurfView m;
-  KfView v;
-  if (!sf_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;      // uniform over the grid
-  const long long tiles = sf_frames_n(v, n_poses) * bpf;
-  for (long long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
-    const long long e = tile / bpf;
-    const int i = (int)(tile % bpf) * 256 + (int)threadIdx.x;
-    int count = v.counts[e];
-    count = count < 0 ? 0 : (count > K ? K : count);
+// pass 1 is k_table_frames_points (map_core.h) with this body, which every lane of the wave enters.  Pass 3,
+// k_table_frames_done, is map_core.h's as well; table_insert_frames launches the three.
+struct SfFramesBody {
+  static __device__ __forceinline__ void point(const SurfView &m, InsertTally *tally, bool valid, const float *p,
+                                               const double *pose, map_u64, uint32_t) {
     int32_t s = -1;
     long long q[3] = {0, 0, 0};
-    if (i < count) {
-      const float4 r = *(const float4 *)(v.rows + ((size_t)e * K + i) * 4);
-      const float p[3] = {r.x, r.y, r.z};
-      s = sf_slot(m, &tally, p, poses + (size_t)e * 7, q);
-    }
+    if (valid) s = sf_slot(m, tally, p, pose, q);
     sf_add(m, s, q);      // every lane of the wave
   }
-  __syncthreads();
-  if (threadIdx.x < 5) {
-    const map_u64 add = ((map_u64 *)&tally)[threadIdx.x];
-    if (add) atomicAdd(&m.hdr->n_cells + threadIdx.x, add);
-  }
-}
+};
 
 // pass 2, over the SLOTS: a slot belongs to one thread, which clears its dirty word and derives its row
 __global__ __launch_bounds__(256) void k_surfel_derive_slots(void *map, long long cap_max) {
@@ -370,15 +304,6 @@ __global__ __launch_bounds__(256) void k_surfel_derive_slots(void *map, long lon
   }
   __syncthreads();
   if (ok && threadIdx.x == 0 && moved) atomicAdd(&m.hdr->n_planar, (map_u64)(long long)moved);
-}
-
-// pass 3: an empty frame still counts as a scan
-__global__ void k_surfel_frames_done(void *map, long long cap_max, void *store, size_t store_bytes, long long kf_cap, int K,
-                                     int n_poses) {
-  SurfView m;
-  KfView v;
-  if (threadIdx.x != 0 || !sf_view(map, cap_max, m) || !kf_view(store, store_bytes, kf_cap, K, v)) return;
-  m.hdr->n_scans = m.hdr->n_scans + (map_u64)sf_frames_n(v, n_poses);
 }
 
 __global__ __launch_bounds__(256) void k_surfel_export(void *map, long long cap_max, int min_flag,
@@ -414,33 +339,20 @@ __global__ __launch_bounds__(256) void k_surfel_export(void *map, long long cap_
 // keys u64 [cap] | moments i64 [cap, 10] | rows f64 [cap, 8] -- the table's own section layout without the dirty words.
 // Rows are copied as 64-bit words, never re-derived.
 // ---------------------------------------------------------------------------------------------------------------------
-#define SF_PRUNE_CTL_BYTES 256
 #define SF_STAGE_BYTES 152               /* key 8 + moments 80 + row 64 */
-struct SfPruneCtl {
-  map_u64 kept, evicted, lost, planar;
-};
-
 struct SfStage {
-  SfPruneCtl *ctl;
+  RebuildCtl *ctl;
   map_u64 *keys, *mom, *rows;
 };
 
 __device__ __forceinline__ SfStage sf_stage(void *ws, long long cap) {
-  unsigned char *p = (unsigned char *)ws + SF_PRUNE_CTL_BYTES;
+  unsigned char *p = (unsigned char *)ws + PRUNE_CTL_BYTES;
   SfStage st;
-  st.ctl = (SfPruneCtl *)ws;
+  st.ctl = (RebuildCtl *)ws;
   st.keys = (map_u64 *)p;
   st.mom = (map_u64 *)(p + (size_t)cap * 8);
   st.rows = (map_u64 *)(p + (size_t)cap * 88);
   return st;
-}
-
-// the control block starts every call at zero
-__global__ void k_surfel_prune_begin(void *ws) {
-  if (threadIdx.x == 0) {
-    SfPruneCtl *ctl = (SfPruneCtl *)ws;
-    ctl->kept = ctl->evicted = ctl->lost = ctl->planar = 0;
-  }
 }
 
 // pass 1: keep or evict every stored cell from its key and its count alone; the other 144 bytes are read for kept cells
@@ -521,7 +433,7 @@ __global__ __launch_bounds__(256) void k_surfel_prune_scan(void *map, long long 
 __global__ __launch_bounds__(256) void k_surfel_prune_clear(void *map, long long cap_max, const void *ws) {
   SurfView m;
   if (!sf_view(map, cap_max, m)) return;
-  if (((const SfPruneCtl *)ws)->evicted == 0) return;
+  if (((const RebuildCtl *)ws)->evicted == 0) return;
   const long long cap = m.hdr->capacity;
   for (long long s = (long long)blockIdx.x * blockDim.x + threadIdx.x; s < cap; s += (long long)gridDim.x * blockDim.x) {
     if (m.keys[s] == MAP_KEY_NONE) continue;
@@ -532,54 +444,21 @@ __global__ __launch_bounds__(256) void k_surfel_prune_clear(void *map, long long
   }
 }
 
-// pass 3: the staged keys are distinct, so whoever wins the CAS on a slot owns it and writes moments and row with plain
-// stores; the kernel boundary publishes them.  The insert's bounded probe: a record without a slot is lost whole.  The
-// lost records and the planar rows are counted per thread, summed in LDS and added once per workgroup.
-__global__ __launch_bounds__(256) void k_surfel_prune_reinsert(void *map, long long cap_max, void *ws) {
-  __shared__ unsigned int tally[2];      // lost, planar
-  if (threadIdx.x < 2) tally[threadIdx.x] = 0;
-  __syncthreads();
-  SurfView m;
-  if (!sf_view(map, cap_max, m)) return;      // uniform over the grid
-  const long long cap = m.hdr->capacity;
-  const SfStage st = sf_stage(ws, cap);
-  if (st.ctl->evicted == 0) return;           // uniform over the grid
-  const long long n = (long long)st.ctl->kept < cap ? (long long)st.ctl->kept : cap;
-  const map_u64 mask = (map_u64)cap - 1;
-  unsigned int lost = 0, planar = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const map_u64 key = st.keys[i];
-    map_u64 s = map_mix(key) & mask;
-    bool found = false;
-    for (int probe = 0; probe < RSLO_MAP_MAX_PROBE; ++probe) {
-      // a stale read can only show "empty": in this launch a key goes from empty to set and never back
-      if (__builtin_nontemporal_load(&m.keys[s]) == MAP_KEY_NONE &&
-          atomicCAS(&m.keys[s], MAP_KEY_NONE, key) == MAP_KEY_NONE) {
-        found = true;
-        break;
-      }
-      s = (s + 1) & mask;
-    }
-    if (!found) {
-      ++lost;
-      continue;
-    }
-    map_u64 *mo = (map_u64 *)m.mom + (size_t)s * 10, *row = (map_u64 *)m.rows + (size_t)s * 8;
-    for (int k = 0; k < 10; ++k) mo[k] = st.mom[(size_t)i * 10 + k];
-    for (int k = 0; k < 8; ++k) row[k] = st.rows[(size_t)i * 8 + k];
-    planar += st.rows[(size_t)i * 8 + 7] == 0x4000000000000000ull;      // the bits of 2.0
+// pass 3 is k_table_reinsert (map_core.h) over these records: the CAS winner writes moments and row as 64-bit words
+struct SfRecords {
+  static __device__ __forceinline__ SfStage stage(void *ws, long long cap) { return sf_stage(ws, cap); }
+  static __device__ __forceinline__ unsigned put(const SurfView &m, const SfStage &st, size_t i, size_t s) {
+    map_u64 *mo = (map_u64 *)m.mom + s * 10, *row = (map_u64 *)m.rows + s * 8;
+    for (int k = 0; k < 10; ++k) mo[k] = st.mom[i * 10 + k];
+    for (int k = 0; k < 8; ++k) row[k] = st.rows[i * 8 + k];
+    return st.rows[i * 8 + 7] == 0x4000000000000000ull;      // the bits of 2.0
   }
-  if (lost) atomicAdd(&tally[0], lost);
-  if (planar) atomicAdd(&tally[1], planar);
-  __syncthreads();
-  if (threadIdx.x == 0 && tally[0]) atomicAdd(&st.ctl->lost, (map_u64)tally[0]);
-  if (threadIdx.x == 1 && tally[1]) atomicAdd(&st.ctl->planar, (map_u64)tally[1]);
-}
+};
 
 __global__ void k_surfel_prune_done(void *map, long long cap_max, const void *ws) {
   SurfView m;
   if (threadIdx.x != 0 || !sf_view(map, cap_max, m)) return;
-  const SfPruneCtl *ctl = (const SfPruneCtl *)ws;
+  const RebuildCtl *ctl = (const RebuildCtl *)ws;
   m.hdr->n_prunes = m.hdr->n_prunes + 1;
   if (ctl->evicted == 0) return;
   m.hdr->n_cells = ctl->kept - ctl->lost;
@@ -779,12 +658,12 @@ extern "C" int rslo_surfel_insert(void *map, size_t map_bytes, const float *poin
       rslo_set_error("surfel_insert: workspace too small");
       return RSLO_EWS;
     }
-    int32_t *slot_of = (int32_t *)(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    int32_t *slot_of = table_slot_of(ws);
     const unsigned nb = (unsigned)rslo_cdiv(N, 256);
     hipLaunchKernelGGL(k_surfel_moments, dim3(nb), dim3(256), 0, s, map, cap_max, points, stride_floats, N, pose7, slot_of);
     hipLaunchKernelGGL(k_surfel_derive_scan, dim3(nb), dim3(256), 0, s, map, cap_max, N, (const int32_t *)slot_of);
   }
-  hipLaunchKernelGGL(k_surfel_scan_done, dim3(1), dim3(64), 0, s, map, cap_max);      // N == 0 still counts as a scan
+  hipLaunchKernelGGL(k_table_scan_done<SurfView>, dim3(1), dim3(64), 0, s, map, cap_max);      // N == 0 still counts as a scan
   RSLO_CHECK_LAUNCH("surfel_insert");
   return RSLO_OK;
 }
@@ -793,25 +672,9 @@ extern "C" int rslo_surfel_insert_frames(void *map, size_t map_bytes, const void
                                          int64_t capacity, int K, const double *poses, int n_poses, void *stream) {
   hipStream_t s = (hipStream_t)stream;
   const long long cap_max = sf_cap_of_bytes(map_bytes);
-  RSLO_CHECK_ARG(map && cap_max > 0, "surfel_insert_frames: no map (map_bytes below rslo_surfel_bytes(1024))");
-  RSLO_CHECK_ARG(store && ((uintptr_t)store & 15) == 0, "surfel_insert_frames: store is null or not 16-byte aligned");
-  RSLO_CHECK_ARG(kf_shape_ok(capacity, K),
-                 "surfel_insert_frames: need capacity in 1 .. 2^16 and K a multiple of 64 in 64 .. 4096");
-  RSLO_CHECK_ARG(store_bytes >= kf_bytes_of(capacity, K), "surfel_insert_frames: store_bytes is smaller than rslo_keyframe_bytes");
-  RSLO_CHECK_ARG(poses, "surfel_insert_frames: poses is null");
-  RSLO_CHECK_ARG(n_poses >= 0, "surfel_insert_frames: n_poses < 0");
-  if (n_poses == 0) return RSLO_OK;
-  const int frames = n_poses < capacity ? n_poses : (int)capacity;      // the store holds no more
-  const int bpf = (int)rslo_cdiv(K, 256);
-  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
-  const unsigned tiles = (unsigned)frames * (unsigned)bpf;      // <= 2^16 * 16
-  hipLaunchKernelGGL(k_surfel_frames_points, dim3(tiles < SF_FRAMES_BLOCKS ? tiles : SF_FRAMES_BLOCKS), dim3(256), 0, s,
-                     map, cap_max, (void *)store, store_bytes, (long long)capacity, K, poses, n_poses, bpf);
-  hipLaunchKernelGGL(k_surfel_derive_slots, dim3(nb), dim3(256), 0, s, map, cap_max);
-  hipLaunchKernelGGL(k_surfel_frames_done, dim3(1), dim3(64), 0, s, map, cap_max, (void *)store, store_bytes,
-                     (long long)capacity, K, n_poses);
-  RSLO_CHECK_LAUNCH("surfel_insert_frames");
-  return RSLO_OK;
+  return table_insert_frames<SurfView, SfFramesBody>(
+      "surfel_insert_frames", "rslo_surfel_bytes", map, cap_max, store, store_bytes, capacity, K, poses, n_poses, s,
+      [&](unsigned nb) { hipLaunchKernelGGL(k_surfel_derive_slots, dim3(nb), dim3(256), 0, s, map, cap_max); });
 }
 
 extern "C" int rslo_surfel_export(const void *map, size_t map_bytes, int min_flag, const double *center3, double radius,
@@ -825,7 +688,7 @@ extern "C" int rslo_surfel_export(const void *map, size_t map_bytes, int min_fla
   RSLO_CHECK_ARG(max_rows == 0 || (keys && moments && rows), "surfel_export: null output");
   RSLO_CHECK_ARG(!center3 || radius >= 0.0, "surfel_export: radius must be >= 0 (NaN is refused)");
   RSLO_HIP(hipMemsetAsync(counts, 0, 2 * sizeof(int64_t), s));
-  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  const unsigned nb = table_blocks(cap_max);
   hipLaunchKernelGGL(k_surfel_export, dim3(nb), dim3(256), 0, s, (void *)map, cap_max, min_flag, center3, radius,
                      (map_u64 *)keys, (long long *)moments, rows, (long long)max_rows, (map_u64 *)counts);
   RSLO_CHECK_LAUNCH("surfel_export");
@@ -834,7 +697,7 @@ extern "C" int rslo_surfel_export(const void *map, size_t map_bytes, int min_fla
 
 extern "C" size_t rslo_surfel_prune_ws_bytes(int64_t capacity) {
   if (rslo_surfel_bytes(capacity) == 0) return 0;
-  return (size_t)SF_PRUNE_CTL_BYTES + (size_t)SF_STAGE_BYTES * (size_t)capacity;
+  return (size_t)PRUNE_CTL_BYTES + (size_t)SF_STAGE_BYTES * (size_t)capacity;
 }
 
 extern "C" int rslo_surfel_prune(void *map, size_t map_bytes, const double *center3, double radius, double inner_radius,
@@ -851,14 +714,14 @@ extern "C" int rslo_surfel_prune(void *map, size_t map_bytes, const double *cent
     rslo_set_error("surfel_prune: workspace too small");
     return RSLO_EWS;
   }
-  const unsigned nb = (unsigned)(cap_max / 256 < 2048 ? cap_max / 256 : 2048);
+  const unsigned nb = table_blocks(cap_max);
   const long long scan_wg = cap_max / (256 * SF_PRUNE_STEP);      // a workgroup of the scan pass takes 2048 slots per step
   const unsigned nb_scan = (unsigned)(scan_wg < 1 ? 1 : (scan_wg < 256 ? scan_wg : 256));
-  hipLaunchKernelGGL(k_surfel_prune_begin, dim3(1), dim3(64), 0, s, ws);
+  map_rebuild_begin(ws, s);
   hipLaunchKernelGGL(k_surfel_prune_scan, dim3(nb_scan), dim3(256), 0, s, map, cap_max, center3, radius, inner_radius,
                      min_count, ws);
   hipLaunchKernelGGL(k_surfel_prune_clear, dim3(nb), dim3(256), 0, s, map, cap_max, (const void *)ws);
-  hipLaunchKernelGGL(k_surfel_prune_reinsert, dim3(nb), dim3(256), 0, s, map, cap_max, ws);
+  hipLaunchKernelGGL((k_table_reinsert<SurfView, SfRecords>), dim3(nb), dim3(256), 0, s, map, cap_max, ws);
   hipLaunchKernelGGL(k_surfel_prune_done, dim3(1), dim3(64), 0, s, map, cap_max, (const void *)ws);
   RSLO_CHECK_LAUNCH("surfel_prune");
   return RSLO_OK;

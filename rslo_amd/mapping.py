@@ -552,21 +552,22 @@ class VoxelMapRef:
         write_ply(path, rows, hits)
 
 
-class VoxelMap:
-    """The device map: owns the table (one allocation of rslo_map_bytes(capacity) bytes) and the insert and registration
-    workspaces, which grow only when a larger scan arrives, and prune's workspace (about one more table), allocated by
-    the first prune() or by reserve_prune().  insert / lookup / overlap / nearest / normal_equations / register / prune
-    enqueue on the current stream and read nothing on the host; points(), stats() and prune_stats() make one host read
-    each."""
+class _DeviceTable:
+    """What the device maps VoxelMap and surfels.SurfelMap share: the table's allocation, the workspace fields, the pose
+    and centre arguments, insert_frames, prune's workspace and the header reads.  A subclass names its capi functions
+    by their prefix (_CAPI) and brings reserve() and reset()."""
 
-    def __init__(self, voxel_size=0.2, capacity=1 << 22, device="cuda", min_range=0.0, max_range=float("inf")):
+    _CAPI = None      # "map" / "surfel": capi.<_CAPI>_bytes, _insert_frames, _prune_ws and capi.<_CAPI upper>_HDR_PRUNE
+
+    def __init__(self, voxel_size, capacity, device, min_range, max_range, **more):
         import torch
         from rslo_amd import capi
         self.voxel_size, self.min_range, self.max_range = _check_params(voxel_size, min_range, max_range)
+        self._set_params(**more)
         self.capacity = int(capacity)
-        nbytes = capi.map_bytes(self.capacity)
+        nbytes = self._capi("bytes")(self.capacity)
         if nbytes == 0:
-            raise capi.RsloHipError("VoxelMap: capacity must be a power of two >= 1024, got %r" % (capacity,))
+            raise capi.RsloHipError("%s: capacity must be a power of two >= 1024, got %r" % (type(self).__name__, capacity))
         self.device = torch.device(device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -577,6 +578,87 @@ class VoxelMap:
         self._identity = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float64, device=self.device)
         self.reserve(0)
         self.reset()
+
+    def _set_params(self):
+        """the subclass's own parameters, checked behind the three every table has"""
+
+    def _capi(self, name):
+        from rslo_amd import capi
+        return getattr(capi, "%s_%s" % (self._CAPI, name))
+
+    def _pose(self, pose):
+        """a float64 CUDA [7] tensor as it is (a row of OdometryRunner's trajectory); None = identity; anything else is copied"""
+        import torch
+        if pose is None:
+            return self._identity
+        if torch.is_tensor(pose) and pose.is_cuda and pose.dtype == torch.float64:
+            return pose
+        return torch.as_tensor(np.asarray(pose, dtype=np.float64).reshape(7)).to(self.device)
+
+    def _center(self, center, exact):
+        """None or a float64 CUDA tensor as it is (read in place); anything else is copied to the device: its 3 values
+        (exact: an export) or its first 3 (a prune, which also takes a [7] trajectory row)"""
+        import torch
+        if center is None or (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
+            return center
+        host = np.asarray(center, dtype=np.float64)
+        return torch.as_tensor(host.reshape(3) if exact else host.reshape(-1)[:3].copy()).to(self.device)
+
+    def _frame_poses(self, store, poses):
+        """a float64 CUDA [m, 7] contiguous tensor on this map's device as it is; anything else that is not a device
+        tensor is copied to the device; a wrong device, dtype or shape is an error"""
+        import torch
+        from rslo_amd import capi
+        name = type(self).__name__
+        if store.device != self.device:
+            raise capi.RsloHipError("%s.insert_frames: the keyframe store lives on %s, the map on %s"
+                                    % (name, store.device, self.device))
+        if not (torch.is_tensor(poses) and poses.is_cuda):
+            host = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, dtype=np.float64)
+            if host.ndim != 2 or host.shape[1] != 7:
+                raise capi.RsloHipError("%s.insert_frames: poses must be [m, 7] rows (t, q wxyz), got %s" % (name, host.shape,))
+            return torch.as_tensor(np.ascontiguousarray(host)).to(self.device)
+        if poses.device != self.device:
+            raise capi.RsloHipError("%s.insert_frames: the poses live on %s, the map on %s" % (name, poses.device, self.device))
+        if poses.dtype != torch.float64 or poses.dim() != 2 or poses.shape[1] != 7:
+            raise capi.RsloHipError("%s.insert_frames: poses must be float64 [m, 7] rows (t, q wxyz), got %s %s"
+                                    % (name, poses.dtype, tuple(poses.shape)))
+        return poses.contiguous()
+
+    def insert_frames(self, store, poses):
+        """Every frame of `store` (a loops.KeyframeStore) under its own row of poses -- float64 CUDA [m, 7], contiguous:
+        read in place (optimized_trajectory() will do); anything else is copied -- as min(entries, m) successive insert()
+        calls would leave the map (module docstring).  Three launches on the current stream, no host read, nothing
+        allocated for a device tensor: capturable."""
+        self._capi("insert_frames")(self._buf, store._buf, store.capacity, store.K, self._frame_poses(store, poses))
+
+    def reserve_prune(self):
+        """Allocate prune's workspace (about one more table) now, so that a later prune() allocates nothing."""
+        if self._prune_ws is None:
+            self._prune_ws = self._capi("prune_ws")(self.capacity, self.device)
+
+    def _header(self, first_word, names):
+        """the int64 header words first_word .. as a dict under `names` (one host read)"""
+        vals = self._buf[first_word:first_word + len(names)].tolist()
+        return dict(zip(names, (int(v) for v in vals)))
+
+    def prune_stats(self):
+        """{n_prunes, n_evicted, n_lost} of the map's header (one host read)."""
+        from rslo_amd import capi
+        return self._header(getattr(capi, "%s_HDR_PRUNE" % self._CAPI.upper()), PRUNE_COUNTERS)
+
+
+class VoxelMap(_DeviceTable):
+    """The device map: owns the table (one allocation of rslo_map_bytes(capacity) bytes) and the insert and registration
+    workspaces, which grow only when a larger scan arrives, and prune's workspace (about one more table), allocated by
+    the first prune() or by reserve_prune().  insert / lookup / overlap / nearest / normal_equations / register / prune
+    enqueue on the current stream and read nothing on the host; points(), stats() and prune_stats() make one host read
+    each."""
+
+    _CAPI = "map"
+
+    def __init__(self, voxel_size=0.2, capacity=1 << 22, device="cuda", min_range=0.0, max_range=float("inf")):
+        super().__init__(voxel_size, capacity, device, min_range, max_range)
 
     def reset(self):
         """Empty the map; the scan counter restarts at 0 (a new sequence has a new frame)."""
@@ -593,47 +675,11 @@ class VoxelMap:
             self._reg_ws = capi.map_register_ws(int(n_points), self.device)      # normal_equations / register
             self._ws_points = int(n_points)
 
-    def _pose(self, pose):
-        """a float64 CUDA [7] tensor as it is (a row of OdometryRunner's trajectory); None = identity; anything else is copied"""
-        import torch
-        if pose is None:
-            return self._identity
-        if torch.is_tensor(pose) and pose.is_cuda and pose.dtype == torch.float64:
-            return pose
-        return torch.as_tensor(np.asarray(pose, dtype=np.float64).reshape(7)).to(self.device)
-
     def insert(self, points, pose=None):
         """One scan (fp32 CUDA [P, F >= 3], read in place; column 3 is the intensity when F >= 4) under pose (t, q wxyz)."""
         from rslo_amd import capi
         self.reserve(points.shape[0])
         capi.map_insert(self._buf, points, self._pose(pose), self._ws)
-
-    def _frame_poses(self, store, poses):
-        """a float64 CUDA [m, 7] contiguous tensor on this map's device as it is; anything else that is not a device
-        tensor is copied to the device; a wrong device, dtype or shape is an error"""
-        import torch
-        from rslo_amd import capi
-        if store.device != self.device:
-            raise capi.RsloHipError("VoxelMap.insert_frames: the keyframe store lives on %s, the map on %s"
-                                    % (store.device, self.device))
-        if not (torch.is_tensor(poses) and poses.is_cuda):
-            host = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, dtype=np.float64)
-            if host.ndim != 2 or host.shape[1] != 7:
-                raise capi.RsloHipError("VoxelMap.insert_frames: poses must be [m, 7] rows (t, q wxyz), got %s" % (host.shape,))
-            return torch.as_tensor(np.ascontiguousarray(host)).to(self.device)
-        if poses.device != self.device:
-            raise capi.RsloHipError("VoxelMap.insert_frames: the poses live on %s, the map on %s" % (poses.device, self.device))
-        if poses.dtype != torch.float64 or poses.dim() != 2 or poses.shape[1] != 7:
-            raise capi.RsloHipError("VoxelMap.insert_frames: poses must be float64 [m, 7] rows (t, q wxyz), got %s %s"
-                                    % (poses.dtype, tuple(poses.shape)))
-        return poses.contiguous()
-
-    def insert_frames(self, store, poses):
-        """Every frame of `store` (a loops.KeyframeStore) under its own row of poses -- float64 CUDA [m, 7], contiguous:
-        read in place (optimized_trajectory() will do) -- as min(entries, m) successive insert() calls would leave the
-        map (module docstring).  Three launches on the current stream, no host read, nothing allocated: capturable."""
-        from rslo_amd import capi
-        capi.map_insert_frames(self._buf, store._buf, store.capacity, store.K, self._frame_poses(store, poses))
 
     def lookup(self, points, pose=None, return_tags=False):
         """hits int32 [P]: -1 for a skipped or out-of-range point, 0 for a cell that is not in the map, else its hits."""
@@ -681,30 +727,15 @@ class VoxelMap:
                                  robust_scale=scale if scale else None)
         return pose, info
 
-    def reserve_prune(self):
-        """Allocate prune's workspace (about one more table) now, so that a later prune() allocates nothing."""
-        from rslo_amd import capi
-        if self._prune_ws is None:
-            self._prune_ws = capi.map_prune_ws(self.capacity, self.device)
-
     def prune(self, center=None, radius=None, min_hits=1, grace=0):
         """Evict the cells that are not within radius of center, or that have fewer than min_hits hits and were created
         at least `grace` scans ago (module docstring).  center: None, a sequence, or a float64 CUDA tensor of >= 3
         elements that is read in place (a [7] trajectory row).  Enqueued on the current stream; no host read, and
         nothing allocated after reserve_prune() when center is a device tensor (or None): capturable."""
-        import torch
         from rslo_amd import capi
         r = check_prune(center, radius, min_hits, grace)
-        if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
-            center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(-1)[:3].copy()).to(self.device)
         self.reserve_prune()
-        capi.map_prune(self._buf, self._prune_ws, center, r, int(min_hits), int(grace))
-
-    def prune_stats(self):
-        """{n_prunes, n_evicted, n_lost} of the map's header (one host read)."""
-        from rslo_amd import capi
-        vals = self._buf[capi.MAP_HDR_PRUNE:capi.MAP_HDR_PRUNE + len(PRUNE_COUNTERS)].tolist()
-        return dict(zip(PRUNE_COUNTERS, (int(v) for v in vals)))
+        capi.map_prune(self._buf, self._prune_ws, self._center(center, exact=False), r, int(min_hits), int(grace))
 
     def carve(self, image, pose, tan_lo=None, tan_hi=None, win_rows=1, win_cols=1, margin_abs=0.3, margin_rel=0.0,
               max_range=60.0, grace=1):
@@ -723,8 +754,7 @@ class VoxelMap:
     def carve_stats(self):
         """{n_carves, n_carved} of the map's header (one host read)."""
         from rslo_amd import capi
-        vals = self._buf[capi.MAP_HDR_CARVE:capi.MAP_HDR_CARVE + len(CARVE_COUNTERS)].tolist()
-        return dict(zip(CARVE_COUNTERS, (int(v) for v in vals)))
+        return self._header(capi.MAP_HDR_CARVE, CARVE_COUNTERS)
 
     def points(self, min_hits=1, center=None, radius=None, sort=True):
         """(rows [M, 4] fp32, tags [M] int64, hits [M] int32) of the cells with hits >= min_hits, and within radius of
@@ -732,11 +762,9 @@ class VoxelMap:
         deterministic bit for bit."""
         import torch
         from rslo_amd import capi
-        if center is not None:
-            if radius is None:
-                raise ValueError("points: a center needs a radius")
-            if not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
-                center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(3)).to(self.device)
+        if center is not None and radius is None:
+            raise ValueError("points: a center needs a radius")
+        center = self._center(center, exact=True)
         r = 0.0 if radius is None else float(radius)
         M = int(capi.map_export(self._buf, min_hits, center, r)[0])      # count only; nothing else changes the map meanwhile
         rows = torch.empty((M, 4), dtype=torch.float32, device=self.device)
@@ -752,8 +780,7 @@ class VoxelMap:
     def stats(self):
         """The six counters of the map's header as a dict (one host read)."""
         from rslo_amd import capi
-        vals = self._buf[capi.MAP_HDR_COUNTERS:capi.MAP_HDR_COUNTERS + len(COUNTERS)].tolist()
-        return dict(zip(COUNTERS, (int(v) for v in vals)))
+        return self._header(capi.MAP_HDR_COUNTERS, COUNTERS)
 
     def save_ply(self, path, min_hits=1):
         rows, _, hits = self.points(min_hits)

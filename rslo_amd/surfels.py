@@ -43,7 +43,7 @@ bit.  The rules in one place:
 import numpy as np
 
 from .gauss_newton import info_terms, register_loop, robust_weighted, terms_of
-from .mapping import VoxelMapRef, _check_params, _check_register, _max_dist_of, check_scale
+from .mapping import VoxelMapRef, _DeviceTable, _check_params, _check_register, _max_dist_of, check_scale
 
 COUNTERS = ("n_scans", "n_cells", "n_points", "dropped_invalid", "dropped_range", "dropped_full", "n_planar")
 PRUNE_COUNTERS = ("n_prunes", "n_evicted", "n_lost")
@@ -466,33 +466,22 @@ class SurfelMapRef:
         write_surfel_ply(path, self.cells(min_flag)[2])
 
 
-class SurfelMap:
+class SurfelMap(_DeviceTable):
     """The device surfel map: owns the table (one allocation of rslo_surfel_bytes(capacity) bytes) and the insert and
     registration workspaces, which grow only when a larger scan arrives, and prune's workspace (about one more table),
     allocated by the first prune() or by reserve_prune().  insert / insert_frames / nearest / normal_equations /
     register / prune enqueue on the current stream and read nothing on the host; cells(), stats() and prune_stats()
     make one host read each."""
 
+    _CAPI = "surfel"
+
     def __init__(self, voxel_size=0.4, capacity=1 << 20, device="cuda", min_range=0.0, max_range=float("inf"),
                  min_points=5, planar_ratio=0.1, line_ratio=0.05):
-        import torch
-        from rslo_amd import capi
-        self.voxel_size, self.min_range, self.max_range = _check_params(voxel_size, min_range, max_range)
+        super().__init__(voxel_size, capacity, device, min_range, max_range, min_points=min_points,
+                         planar_ratio=planar_ratio, line_ratio=line_ratio)
+
+    def _set_params(self, min_points, planar_ratio, line_ratio):
         self.min_points, self.planar_ratio, self.line_ratio = _check_plane_params(min_points, planar_ratio, line_ratio)
-        self.capacity = int(capacity)
-        nbytes = capi.surfel_bytes(self.capacity)
-        if nbytes == 0:
-            raise capi.RsloHipError("SurfelMap: capacity must be a power of two >= 1024, got %r" % (capacity,))
-        self.device = torch.device(device)
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self._buf = torch.empty((nbytes // 8,), dtype=torch.int64, device=self.device)
-        self._ws = None
-        self._ws_points = -1
-        self._prune_ws = None
-        self._identity = torch.tensor([0, 0, 0, 1, 0, 0, 0], dtype=torch.float64, device=self.device)
-        self.reserve(0)
-        self.reset()
 
     def reset(self):
         """Empty the table; every counter restarts at 0."""
@@ -508,35 +497,11 @@ class SurfelMap:
             self._reg_ws = capi.surfel_register_ws(int(n_points), self.device)
             self._ws_points = int(n_points)
 
-    def _pose(self, pose):
-        """a float64 CUDA [7] tensor as it is (a trajectory row); None = identity; anything else is copied"""
-        import torch
-        if pose is None:
-            return self._identity
-        if torch.is_tensor(pose) and pose.is_cuda and pose.dtype == torch.float64:
-            return pose
-        return torch.as_tensor(np.asarray(pose, dtype=np.float64).reshape(7)).to(self.device)
-
     def insert(self, points, pose=None):
         """One scan (fp32 CUDA [P, F >= 3], read in place; only x, y, z are read) under pose (t, q wxyz)."""
         from rslo_amd import capi
         self.reserve(points.shape[0])
         capi.surfel_insert(self._buf, points, self._pose(pose), self._ws)
-
-    def insert_frames(self, store, poses):
-        """Every frame of `store` (a loops.KeyframeStore) under its own row of poses (float64 CUDA [m, 7] read in place,
-        anything else copied), as min(entries, m) successive insert() calls would leave the table.  Three launches."""
-        import torch
-        from rslo_amd import capi
-        if store.device != self.device:
-            raise capi.RsloHipError("SurfelMap.insert_frames: the keyframe store lives on %s, the map on %s"
-                                    % (store.device, self.device))
-        if not (torch.is_tensor(poses) and poses.is_cuda):
-            host = np.asarray(poses.cpu() if torch.is_tensor(poses) else poses, dtype=np.float64)
-            if host.ndim != 2 or host.shape[1] != 7:
-                raise capi.RsloHipError("SurfelMap.insert_frames: poses must be [m, 7] rows (t, q wxyz), got %s" % (host.shape,))
-            poses = torch.as_tensor(np.ascontiguousarray(host)).to(self.device)
-        capi.surfel_insert_frames(self._buf, store._buf, store.capacity, store.K, poses.contiguous())
 
     def nearest(self, points, pose=None, max_dist=None, return_rows=False, cost="plane", min_flag=None, reg_rel=None,
                 reg_abs=None, return_info=False):
@@ -591,41 +556,24 @@ class SurfelMap:
                                           tol_r, scale, *dist, info=info, ws=self._reg_ws)
         return pose, info
 
-    def reserve_prune(self):
-        """Allocate prune's workspace (152 bytes per slot) now, so that a later prune() allocates nothing."""
-        from rslo_amd import capi
-        if self._prune_ws is None:
-            self._prune_ws = capi.surfel_prune_ws(self.capacity, self.device)
-
     def prune(self, center=None, radius=None, inner_radius=None, min_count=1):
         """Evict the cells whose centre is not within radius of center, or that hold fewer than min_count points and
         lie at least inner_radius (None: radius) from it (module docstring).  center: None, a sequence, or a float64
         CUDA tensor of >= 3 elements that is read in place (a [7] trajectory row).  Enqueued on the current stream; no
         host read, and nothing allocated after reserve_prune() when center is a device tensor (or None): capturable."""
-        import torch
         from rslo_amd import capi
         r, ri, mc = check_surfel_prune(center, radius, inner_radius, min_count)
-        if center is not None and not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
-            center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(-1)[:3].copy()).to(self.device)
         self.reserve_prune()
-        capi.surfel_prune(self._buf, self._prune_ws, center, r, ri, mc)
-
-    def prune_stats(self):
-        """{n_prunes, n_evicted, n_lost} of the map's header (one host read)."""
-        from rslo_amd import capi
-        vals = self._buf[capi.SURFEL_HDR_PRUNE:capi.SURFEL_HDR_PRUNE + len(PRUNE_COUNTERS)].tolist()
-        return dict(zip(PRUNE_COUNTERS, (int(v) for v in vals)))
+        capi.surfel_prune(self._buf, self._prune_ws, self._center(center, exact=False), r, ri, mc)
 
     def cells(self, min_flag=1, center=None, radius=None):
         """(keys int64 [M], moments int64 [M, 10], rows float64 [M, 8]) of the cells with flag >= min_flag (and whose mean
         lies within radius of center, when one is given), sorted by key: deterministic bit for bit.  One host read (M)."""
         import torch
         from rslo_amd import capi
-        if center is not None:
-            if radius is None:
-                raise ValueError("cells: a center needs a radius")
-            if not (torch.is_tensor(center) and center.is_cuda and center.dtype == torch.float64):
-                center = torch.as_tensor(np.asarray(center, dtype=np.float64).reshape(3)).to(self.device)
+        if center is not None and radius is None:
+            raise ValueError("cells: a center needs a radius")
+        center = self._center(center, exact=True)
         r = 0.0 if radius is None else float(radius)
         M = int(capi.surfel_export(self._buf, min_flag, center, r)[0])      # count only; nothing else changes the map meanwhile
         keys = torch.empty((M,), dtype=torch.int64, device=self.device)
@@ -640,8 +588,7 @@ class SurfelMap:
     def stats(self):
         """The seven counters of the header as a dict (one host read)."""
         from rslo_amd import capi
-        vals = self._buf[capi.SURFEL_HDR_COUNTERS:capi.SURFEL_HDR_COUNTERS + len(COUNTERS)].tolist()
-        return dict(zip(COUNTERS, (int(v) for v in vals)))
+        return self._header(capi.SURFEL_HDR_COUNTERS, COUNTERS)
 
     def save_ply(self, path, min_flag=2):
         write_surfel_ply(path, self.cells(min_flag)[2].cpu().numpy())

@@ -312,6 +312,49 @@ def test_insert_frames_more_tiles_than_workgroups():
     assert_same(smap, ref, "2100 frames")
 
 
+def test_insert_frames_clamps():
+    """Fewer poses than entries, more poses than entries, and a pose row of NaN (tests/test_gpu_map_frames.py
+    test_clamps): keys, moments, rows and all seven counters are the restatement's."""
+    from rslo_amd.surfels import SurfelMap, SurfelMapRef
+    K, voxel, counts = 64, 4.0, (0, 1, 63, 64, 64)          # a 4 m cell: frames share cells, and some cells get a row
+    frames, poses = make_frames(K, counts, seed=K), make_poses(9, seed=5)
+    sref, store = store_ref(frames, K), dev_store(frames, K)
+    bad = poses[:5].copy()
+    bad[2] = np.nan                                         # the frame of 63 points
+    for label, rows, n in (("3 poses", poses[:3], 3), ("9 poses", poses, 5), ("a NaN pose", bad, 5)):
+        ref = SurfelMapRef(voxel)
+        ref.insert_frames(sref, rows)
+        assert ref.stats()["n_scans"] == n and ref.stats()["n_points"] + ref.stats()["dropped_range"] == sum(counts[:n])
+        assert ref.stats()["dropped_range"] == (63 if rows is bad else 0)
+        assert n == 3 or (ref.moments[:, 0] >= 5).sum() >= 8
+        smap = SurfelMap(voxel, 1 << 12)
+        smap.insert_frames(store, dev(rows))
+        assert_same(smap, ref, label + ", 5 entries")
+
+
+def test_insert_frames_full_table():
+    """40 frames x 64 points in 2560 distinct cells and only 1024 slots (tests/test_gpu_map_frames.py test_overflow):
+    dropped_full > 0 is certain by counting.  Slots only fill, so a key that is stored has received all of its points:
+    every stored cell holds the reference's moments and row of that key."""
+    from rslo_amd.surfels import SurfelMap, SurfelMapRef
+    K, voxel, F = 64, 0.1, 40
+    frames, poses = make_frames(K, (K,) * F, seed=11, spread=40.0), make_poses(F, seed=11)
+    ref = SurfelMapRef(voxel)
+    ref.insert_frames(store_ref(frames, K, capacity=64), poses)
+    assert len(ref.keys) == F * K == 2560 and ref.stats()["n_cells"] == 2560 and ref.stats()["n_points"] == 2560
+    smap = SurfelMap(voxel, 1024)
+    smap.insert_frames(dev_store(frames, K, capacity=64), dev(poses))
+    st = smap.stats()
+    keys, mom, rows = got_of(smap)
+    print("insert_frames into a full table:", st)
+    assert st["dropped_full"] > 0 and st["n_points"] + st["dropped_full"] == ref.stats()["n_points"]
+    assert st["n_scans"] == F
+    assert st["n_cells"] == len(keys) <= 1024 and len(set(keys.tolist())) == len(keys)
+    at = np.searchsorted(ref.keys, keys)
+    assert (at < len(ref.keys)).all() and (ref.keys[at] == keys).all()
+    assert (mom == ref.moments[at]).all() and (rows.view(np.int64) == ref.rows[at].view(np.int64)).all()
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # nearest
 # ---------------------------------------------------------------------------------------------------------------------
