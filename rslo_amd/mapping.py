@@ -190,6 +190,41 @@ def check_prune(center, radius, min_hits, grace, has_center=None):
     return r
 
 
+def check_local_map(options, voxel_map, surfels):
+    """The local_map= options of an OdometryRunner against the maps it was given (ValueError): -> dict(radius, every,
+    min_hits, grace), plus surfels=dict(min_count, inner_radius) when the surfels key asks for the surfel map to be
+    pruned too (True: its defaults).  Without that key a voxel_map is required; with it, surfels is."""
+    from .surfels import check_surfel_prune
+    o = dict(options)
+    surfel_prune = o.pop("surfels", None)
+    if surfel_prune is None or surfel_prune is False:
+        surfel_prune = None
+        if voxel_map is None:
+            raise ValueError("local_map needs a voxel_map to prune")
+    else:
+        if surfels is None:
+            raise ValueError("local_map's surfels key needs surfels=SurfelMap(...) to prune")
+        surfel_prune = {} if surfel_prune is True else dict(surfel_prune)
+        unknown = set(surfel_prune) - {"min_count", "inner_radius"}
+        if unknown:
+            raise ValueError("local_map surfels takes min_count and inner_radius; got %s" % sorted(unknown))
+    unknown = set(o) - {"radius", "every", "min_hits", "grace"}
+    if unknown:
+        raise ValueError("local_map takes radius, every, min_hits, grace and surfels; got %s" % sorted(unknown))
+    if "radius" not in o:
+        raise ValueError("local_map needs a radius")
+    every, min_hits, grace = o.get("every", 1), o.get("min_hits", 1), o.get("grace", 0)
+    if int(every) != every or every < 1:
+        raise ValueError("local_map every must be an integer >= 1, got %r" % (every,))
+    radius = check_prune(None, o["radius"], min_hits, grace, has_center=True)
+    out = dict(radius=radius, every=int(every), min_hits=int(min_hits), grace=int(grace))
+    if surfel_prune is not None:
+        _, inner, min_count = check_surfel_prune(None, radius, surfel_prune.get("inner_radius"),
+                                                 surfel_prune.get("min_count", 1), has_center=True)
+        out["surfels"] = dict(min_count=min_count, inner_radius=inner)
+    return out
+
+
 def check_carve_call(image, tan_lo, tan_hi, win_rows, win_cols, margin_abs, margin_rel, max_range, grace):
     """The argument errors of carve (ValueError), raised before anything is written.  image: anything with a 2-D .shape,
     or a carve.RangeImage, whose tangents stand in for tan_lo / tan_hi = None (else carve.CARVE_DEFAULTS).

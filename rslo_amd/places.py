@@ -61,6 +61,19 @@ def check_query(exclude_recent, num_candidates, top_k):
     return int(exclude_recent), int(num_candidates), int(top_k)
 
 
+LOOP_DEFAULTS = dict(exclude_recent=50, num_candidates=10, top_k=1)
+
+
+def check_loop(options):
+    """The loop= options of an OdometryRunner (ValueError): -> the keyword arguments of PlaceDB.query, LOOP_DEFAULTS
+    filled in.  None: the defaults."""
+    o = dict(LOOP_DEFAULTS, **(options or {}))
+    unknown = set(o) - set(LOOP_DEFAULTS)
+    if unknown:
+        raise ValueError("loop takes exclude_recent, num_candidates and top_k; got %s" % sorted(unknown))
+    return dict(zip(LOOP_DEFAULTS, check_query(**o)))
+
+
 def tables(R, S, max_range):
     """float64 [2*(S+1) + R+1]: dirs [S+1, 2] flattened, then edge2 [R+1].  Made once; both sides read these values."""
     R, S, max_range, _ = check_params(R, S, max_range, 0.0)

@@ -423,6 +423,6 @@ def test_runner_carves_in_front_of_the_insert():
         assert ref.stats()["n_cells"] > 10000
         _assert_same(vmap, ref, "runner, carve")
         assert vmap.stats()["dropped_full"] == 0 and vmap.prune_stats()["n_lost"] == 0
-        assert (runner._range_image.numpy() == carve.range_image_ref(scans[-1].cpu().numpy())).all()
+        assert (runner.backend.range_image.numpy() == carve.range_image_ref(scans[-1].cpu().numpy())).all()
     finally:
         runner.close()
