@@ -443,46 +443,10 @@ extern "C" int rslo_rulebook_conv_T(const int32_t *coords_in, int64_t N, int B, 
 // order) and a linked list of its points.  Voxel id = exclusive scan over "is first point"
 // flags (= rank of the first index), rank of a point inside its voxel = number of list
 // members with a smaller index.  Everything is order-independent, hence deterministic.
+// There is ONE implementation, for a batch of clouds (the kb_vox_* kernels in front of rslo_plan_encoder below):
+// rslo_plan_encoder runs it over all clouds of a step, rslo_voxelize over a batch of one.
 // ---------------------------------------------------------------------------------------
-struct VoxWs {
-  uint32_t *keys;
-  int32_t *first, *head, *vid, *next, *slot, *pos, *cutoff;
-  uint32_t *flags;
-  void *scan_ws;
-  size_t scan_bytes;
-  int64_t cap;
-};
-
 static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t vox_ws_layout(int64_t P, void *base, VoxWs *w) {
-  const int64_t cap = rslo_hash_capacity(P);
-  size_t off = 0;
-  char *b = (char *)base;
-  auto take = [&](size_t bytes) {
-    void *p = b ? (void *)(b + off) : nullptr;
-    off += align256(bytes);
-    return p;
-  };
-  // keys | head are filled with 0xFF and first | cutoff with 0x7F: adjacent, so each pair is ONE memset (cap * 4 is a
-  // multiple of 256: no padding in between)
-  void *keys = take(cap * 4), *head = take(cap * 4), *first = take(cap * 4);
-  void *cutoff = take(256);
-  void *vid = take(cap * 4);
-  void *next = take((size_t)P * 4), *slot = take((size_t)P * 4), *pos = take((size_t)P * 4),
-       *flags = take((size_t)P * 4);
-  size_t sb = rslo_scan_ws_bytes(P);
-  void *sws = take(sb);
-  if (w) {
-    w->keys = (uint32_t *)keys; w->first = (int32_t *)first; w->head = (int32_t *)head;
-    w->vid = (int32_t *)vid; w->next = (int32_t *)next; w->slot = (int32_t *)slot;
-    w->pos = (int32_t *)pos; w->flags = (uint32_t *)flags; w->cutoff = (int32_t *)cutoff;
-    w->scan_ws = sws; w->scan_bytes = sb; w->cap = cap;
-  }
-  return off;
-}
-
-extern "C" size_t rslo_voxelize_ws_bytes(int64_t P) { return vox_ws_layout(P > 0 ? P : 1, nullptr, nullptr); }
 
 struct VoxGeom {
   float lo[3], vs[3];
@@ -498,147 +462,6 @@ __device__ __forceinline__ bool vox_coord(const float *__restrict__ p, const Vox
     c[j] = (int)fl;
   }
   return true;
-}
-
-__global__ void k_vox_insert(const float *__restrict__ pts, int64_t P, int F, VoxGeom G,
-                             uint32_t *__restrict__ keys, int32_t *__restrict__ first,
-                             int32_t *__restrict__ head, int32_t *__restrict__ next,
-                             int32_t *__restrict__ slot, uint32_t mask, int shift) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  int c[3];
-  if (!vox_coord(pts + i * F, G, c)) {
-    slot[i] = -1;
-    return;
-  }
-  const uint32_t key = ((uint32_t)c[2] * G.g[1] + c[1]) * G.g[0] + c[0];
-  uint32_t s = rslo_hslot(key, shift);
-  while (true) {
-    uint32_t prev = atomicCAS(&keys[s], RSLO_EMPTY_KEY, key);
-    if (prev == RSLO_EMPTY_KEY || prev == key) break;
-    s = (s + 1) & mask;
-  }
-  atomicMin(&first[s], (int32_t)i);
-  next[i] = atomicExch(&head[s], (int32_t)i);
-  slot[i] = (int32_t)s;
-}
-
-__global__ void k_vox_flags(const int32_t *__restrict__ slot, const int32_t *__restrict__ first, int64_t P,
-                            uint32_t *__restrict__ flags) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  const int32_t s = slot[i];
-  flags[i] = (s >= 0 && first[s] == (int32_t)i) ? 1u : 0u;
-}
-
-__global__ void k_vox_assign(const uint32_t *__restrict__ keys, const int32_t *__restrict__ slot,
-                             const uint32_t *__restrict__ flags, const int32_t *__restrict__ pos, int64_t P,
-                             VoxGeom G, int max_voxels, int32_t *__restrict__ vid,
-                             int32_t *__restrict__ coords, int32_t *__restrict__ cutoff,
-                             int32_t *__restrict__ d_nvox) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  if (i == P - 1) {
-    const int32_t tot = pos[i] + (int32_t)flags[i];
-    *d_nvox = tot < max_voxels ? tot : max_voxels;
-  }
-  if (!flags[i]) return;
-  const int32_t s = slot[i];
-  const int32_t v = pos[i];
-  vid[s] = v;
-  if (v < max_voxels) {
-    uint32_t key = keys[s];
-    const int x = key % G.g[0];
-    key /= G.g[0];
-    const int y = key % G.g[1];
-    const int z = key / G.g[1];
-    coords[v * 3 + 0] = z;
-    coords[v * 3 + 1] = y;
-    coords[v * 3 + 2] = x;
-  } else if (v == max_voxels) {
-    *cutoff = (int32_t)i;  // the reference loop `break`s here
-  }
-}
-
-__global__ void k_vox_fill(const float *__restrict__ pts, int64_t P, int F, int T,
-                           const int32_t *__restrict__ slot, const int32_t *__restrict__ head,
-                           const int32_t *__restrict__ next, const int32_t *__restrict__ vid,
-                           const int32_t *__restrict__ cutoff, float *__restrict__ voxels,
-                           int32_t *__restrict__ num_points) {
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= P) return;
-  const int32_t s = slot[i];
-  if (s < 0 || i >= (int64_t)*cutoff) return;
-  int rank = 0;
-  for (int32_t j = head[s]; j >= 0; j = next[j]) rank += (j < (int32_t)i);
-  if (rank >= T) return;
-  const int32_t v = vid[s];
-  float *dst = voxels + ((int64_t)v * T + rank) * F;
-  const float *src = pts + i * F;
-  for (int f = 0; f < F; ++f) dst[f] = src[f];
-  atomicAdd(&num_points[v], 1);
-}
-
-// the voxelizer's launches for one cloud (outputs already zero-filled by the caller)
-static int vox_run(const float *points, int64_t P, int F, const VoxGeom &G, int T, int max_voxels, void *ws,
-                   float *voxels, int32_t *coords, int32_t *num_points, int32_t *d_nvox, hipStream_t st) {
-  VoxWs w;
-  vox_ws_layout(P, ws, &w);
-  RSLO_HIP(hipMemsetAsync(w.keys, 0xFF, (size_t)w.cap * 8, st));                 // keys | head
-  RSLO_HIP(hipMemsetAsync(w.first, 0x7F, (size_t)w.cap * 4 + sizeof(int32_t), st));    // first | cutoff
-  const unsigned nb = (unsigned)rslo_cdiv(P, 256);
-  const int shift = 32 - rslo_log2_i64(w.cap);
-  hipLaunchKernelGGL(k_vox_insert, dim3(nb), dim3(256), 0, st, points, P, F, G, w.keys, w.first, w.head,
-                     w.next, w.slot, (uint32_t)(w.cap - 1), shift);
-  hipLaunchKernelGGL(k_vox_flags, dim3(nb), dim3(256), 0, st, w.slot, w.first, P, w.flags);
-  RSLO_CHECK_LAUNCH("vox_insert");
-  if (int rc = scan_exclusive<false>(w.flags, w.pos, P, w.scan_ws, w.scan_bytes, nullptr, st)) return rc;
-  hipLaunchKernelGGL(k_vox_assign, dim3(nb), dim3(256), 0, st, w.keys, w.slot, w.flags, w.pos, P, G,
-                     max_voxels, w.vid, coords, w.cutoff, d_nvox);
-  hipLaunchKernelGGL(k_vox_fill, dim3(nb), dim3(256), 0, st, points, P, F, T, w.slot, w.head, w.next,
-                     w.vid, w.cutoff, voxels, num_points);
-  RSLO_CHECK_LAUNCH("vox_fill");
-  return RSLO_OK;
-}
-
-extern "C" int rslo_voxelize(const float *points, int64_t P, int F, const float *range6,
-                             const float *vsize3, const int32_t *grid_xyz, int T, int max_voxels,
-                             void *ws, size_t ws_bytes, float *voxels, int32_t *coords,
-                             int32_t *num_points, int32_t *d_nvox, void *stream) {
-  hipStream_t st = (hipStream_t)stream;
-  RSLO_CHECK_ARG(F >= 3 && T >= 1 && max_voxels >= 1, "voxelize: bad F/T/max_voxels");
-  RSLO_CHECK_ARG(P < (int64_t)2000000000, "voxelize: too many points");
-  {
-    int32_t d[3] = {grid_xyz[2], grid_xyz[1], grid_xyz[0]};
-    if (int rc = check_volume(1, d)) return rc;
-  }
-  {
-    // the four outputs are zero-filled; a caller that lays them out back to back (voxels | num_points | coords | d_nvox,
-    // as rslo_amd.capi does) gets ONE fill instead of four
-    const size_t bv = (size_t)max_voxels * T * F * sizeof(float), bn = (size_t)max_voxels * sizeof(int32_t),
-                 bc = (size_t)max_voxels * 3 * sizeof(int32_t);
-    char *v0 = (char *)voxels;
-    if ((char *)num_points == v0 + bv && (char *)coords == v0 + bv + bn && (char *)d_nvox == v0 + bv + bn + bc) {
-      RSLO_HIP(hipMemsetAsync(voxels, 0, bv + bn + bc + sizeof(int32_t), st));
-    } else {
-      RSLO_HIP(hipMemsetAsync(voxels, 0, bv, st));
-      RSLO_HIP(hipMemsetAsync(num_points, 0, bn, st));
-      RSLO_HIP(hipMemsetAsync(coords, 0, bc, st));
-      RSLO_HIP(hipMemsetAsync(d_nvox, 0, sizeof(int32_t), st));
-    }
-  }
-  if (P == 0) return RSLO_OK;
-  if (ws_bytes < rslo_voxelize_ws_bytes(P)) {
-    rslo_set_error("voxelize: workspace too small (%zu < %zu)", ws_bytes, rslo_voxelize_ws_bytes(P));
-    return RSLO_EWS;
-  }
-  VoxGeom G;
-  for (int j = 0; j < 3; ++j) {
-    G.lo[j] = range6[j];
-    G.vs[j] = vsize3[j];
-    G.g[j] = grid_xyz[j];
-  }
-  return vox_run(points, P, F, G, T, max_voxels, ws, voxels, coords, num_points, d_nvox, st);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1194,12 +1017,13 @@ extern "C" int rslo_rulebook_row_order(const int32_t *nbr, int64_t n_rows, int K
 // and 7 blocking reads per step on a helper thread.
 // ---------------------------------------------------------------------------------------
 // ---------------------------------------------------------------------------------------
-// The voxelizer for ALL clouds of a step in one set of launches (rslo_plan_encoder): grid (blocks of the largest cloud,
-// cloud).  Same algorithm as vox_run -- per-cloud hash with atomicMin(first point) + linked list, voxel id = rank of the
-// first point, in-voxel rank = list members with a smaller index -- with the per-point arrays of all clouds back to back
-// (ONE scan over all "is first point" flags: a cloud's voxel ids are the global prefix minus the prefix at its first
-// point) and the per-cloud tables back to back (one fill each for keys | head and first | cutoff).  8 clouds: 11
-// launches instead of 80, and launches of ~4000 workgroups instead of ~480.
+// The voxelizer (algorithm: "voxelizer." above) for a batch of clouds in one set of launches: grid (blocks of the largest
+// cloud, cloud).  Per-cloud hash with atomicMin(first point) + linked list, voxel id = rank of the first point, in-voxel
+// rank = list members with a smaller index, with the per-point arrays of all clouds back to back (ONE scan over all "is
+// first point" flags: a cloud's voxel ids are the global prefix minus the prefix at its first point) and the per-cloud
+// tables back to back (one fill each for keys | head and first | cutoff).  rslo_plan_encoder passes all clouds of a step
+// (8 clouds: 11 launches instead of 80, and launches of ~4000 workgroups instead of ~480), rslo_voxelize a batch of one.
+// The two differ in where the counts go (the nvox / base pointers) and in the coordinate rows (ROWS of kb_vox_assign).
 // ---------------------------------------------------------------------------------------
 struct VoxBatch {
   const float *pts[RSLO_PLAN_MAX_CLOUDS];
@@ -1227,7 +1051,7 @@ __global__ void kb_vox_insert(VoxBatch B, int F, VoxGeom G, VoxBatchWs w) {
     return;
   }
   const uint32_t key = ((uint32_t)cc[2] * G.g[1] + cc[1]) * G.g[0] + cc[0];
-  const uint32_t mask = (1u << (32 - B.shift[c])) - 1u;
+  const uint32_t mask = 0xFFFFFFFFu >> B.shift[c];      // capacity - 1, also for the 2^32-slot table of a cloud of > 2^30 points
   uint32_t *keys = w.keys + B.tab[c];
   uint32_t s = rslo_hslot(key, B.shift[c]);
   // plain reads first: 3 of 4 points land in a voxel that already has its slot, and in scan order most of them are not
@@ -1253,27 +1077,50 @@ __global__ void kb_vox_flags(VoxBatch B, VoxBatchWs w) {
   w.flags[gi] = (s >= 0 && w.first[B.tab[c] + s] == i) ? 1u : 0u;
 }
 
-// one block: per cloud the number of voxels (capped), the row base of the next cloud, the prefix at its first point
-__global__ void kb_vox_bases(VoxBatch B, VoxBatchWs w, int max_voxels, int32_t *__restrict__ cnt) {
+// one block: per cloud the number of voxels (capped) -> nvox[c], the row base of the next cloud -> base[c + 1], the prefix
+// at its first point
+__global__ void kb_vox_bases(VoxBatch B, VoxBatchWs w, int max_voxels, int32_t *__restrict__ nvox,
+                             int32_t *__restrict__ base) {
   if (threadIdx.x != 0) return;
   const int total_pts = B.start[B.n];
   const int32_t all = total_pts > 0 ? w.pos[total_pts - 1] + (int32_t)w.flags[total_pts - 1] : 0;
-  int32_t base = 0;
-  cnt[RSLO_PLAN_CNT_BASE] = 0;
+  int32_t rows = 0;
+  base[0] = 0;
   for (int c = 0; c < B.n; ++c) {
     const int32_t s0 = B.start[c] < total_pts ? w.pos[B.start[c]] : all;
     const int32_t s1 = B.start[c + 1] < total_pts ? w.pos[B.start[c + 1]] : all;
     const int32_t tot = s1 - s0;
     const int32_t nv = tot < max_voxels ? tot : max_voxels;
     w.pre[c] = s0;
-    cnt[RSLO_PLAN_CNT_NVOX + c] = nv;
-    base += nv;
-    cnt[RSLO_PLAN_CNT_BASE + c + 1] = base;
+    nvox[c] = nv;
+    rows += nv;
+    base[c + 1] = rows;
   }
 }
 
-__global__ void kb_vox_assign(VoxBatch B, VoxGeom G, VoxBatchWs w, int max_voxels, const int32_t *__restrict__ cnt,
-                              int32_t *__restrict__ coords_frame, int32_t *__restrict__ coords_all) {
+// What the two entry points write per voxel (the ROWS of kb_vox_assign) and the names their launch checks report.
+struct PlanRows {      // rslo_plan_encoder: two int4 rows, (cloud within its frame, z, y, x) and (cloud, z, y, x)
+  int32_t *coords_frame, *coords_all;
+  static constexpr const char *insert_check = "plan vox_insert", *fill_check = "plan vox_fill";
+  __device__ __forceinline__ void put(int32_t row, int c, int clouds_per_frame, int z, int y, int x) const {
+    reinterpret_cast<int4 *>(coords_frame)[row] = make_int4(c % clouds_per_frame, z, y, x);
+    reinterpret_cast<int4 *>(coords_all)[row] = make_int4(c, z, y, x);
+  }
+};
+
+struct ZyxRows {       // rslo_voxelize: one [row, 3] row (z, y, x)
+  int32_t *coords;
+  static constexpr const char *insert_check = "vox_insert", *fill_check = "vox_fill";
+  __device__ __forceinline__ void put(int32_t row, int, int, int z, int y, int x) const {
+    coords[row * 3 + 0] = z;
+    coords[row * 3 + 1] = y;
+    coords[row * 3 + 2] = x;
+  }
+};
+
+template <class ROWS>
+__global__ void kb_vox_assign(VoxBatch B, VoxGeom G, VoxBatchWs w, int max_voxels, const int32_t *__restrict__ base,
+                              ROWS rows) {
   const int c = blockIdx.y;
   const int P = B.start[c + 1] - B.start[c];
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1289,15 +1136,13 @@ __global__ void kb_vox_assign(VoxBatch B, VoxGeom G, VoxBatchWs w, int max_voxel
     key /= G.g[0];
     const int y = key % G.g[1];
     const int z = key / G.g[1];
-    const int32_t row = cnt[RSLO_PLAN_CNT_BASE + c] + v;
-    reinterpret_cast<int4 *>(coords_frame)[row] = make_int4(c % B.clouds_per_frame, z, y, x);
-    reinterpret_cast<int4 *>(coords_all)[row] = make_int4(c, z, y, x);
+    rows.put(base[c] + v, c, B.clouds_per_frame, z, y, x);
   } else if (v == max_voxels) {
     w.cutoff[c] = i;      // the reference loop `break`s here
   }
 }
 
-__global__ void kb_vox_fill(VoxBatch B, int F, int T, VoxBatchWs w, const int32_t *__restrict__ cnt,
+__global__ void kb_vox_fill(VoxBatch B, int F, int T, VoxBatchWs w, const int32_t *__restrict__ base,
                             float *__restrict__ voxels, int32_t *__restrict__ num_points) {
   const int c = blockIdx.y;
   const int P = B.start[c + 1] - B.start[c];
@@ -1309,16 +1154,20 @@ __global__ void kb_vox_fill(VoxBatch B, int F, int T, VoxBatchWs w, const int32_
   int rank = 0;
   for (int32_t j = w.head[B.tab[c] + s]; j >= 0; j = w.next[B.start[c] + j]) rank += (j < i);
   if (rank >= T) return;
-  const int32_t v = w.vid[B.tab[c] + s] + cnt[RSLO_PLAN_CNT_BASE + c];
+  const int32_t v = w.vid[B.tab[c] + s] + base[c];
   float *dst = voxels + ((int64_t)v * T + rank) * F;
   const float *src = B.pts[c] + (int64_t)i * F;
   for (int f = 0; f < F; ++f) dst[f] = src[f];
   atomicAdd(&num_points[v], 1);
 }
 
-// workspace of the batched voxelizer: tables (per-cloud capacities back to back) + per-point arrays
-static size_t voxb_ws_layout(int n, const int64_t *h_n_points, void *base, VoxBatchWs *w, VoxBatch *B, void **scan_ws,
-                             size_t *scan_bytes, size_t *fill_ff, size_t *fill_7f) {
+struct VoxBatchHost {      // what only the host needs of the workspace: the scan's scratch and the sizes of the two fills
+  void *scan_ws;
+  size_t scan_bytes, fill_ff, fill_7f;
+};
+
+// workspace of the voxelizer: tables (per-cloud capacities back to back) + per-point arrays
+static size_t voxb_ws_layout(int n, const int64_t *h_n_points, void *base, VoxBatchWs *w, VoxBatch *B, VoxBatchHost *h) {
   int64_t caps = 0, pts = 0;
   for (int c = 0; c < n; ++c) {
     const int64_t cap = rslo_hash_capacity(h_n_points[c] > 0 ? h_n_points[c] : 1);
@@ -1350,11 +1199,88 @@ static size_t voxb_ws_layout(int n, const int64_t *h_n_points, void *base, VoxBa
     w->vid = (int32_t *)vid; w->pre = (int32_t *)pre; w->next = (int32_t *)next; w->slot = (int32_t *)slot;
     w->pos = (int32_t *)pos; w->flags = (uint32_t *)flags;
   }
-  if (scan_ws) *scan_ws = sws;
-  if (scan_bytes) *scan_bytes = sb;
-  if (fill_ff) *fill_ff = (size_t)caps * 8;
-  if (fill_7f) *fill_7f = (size_t)caps * 4 + 256;
+  if (h) *h = VoxBatchHost{sws, sb, (size_t)caps * 8, (size_t)caps * 4 + 256};
   return off;
+}
+
+// the voxelizer's launches for the clouds of VB (outputs already zero-filled by the caller): counts of cloud c -> nvox[c],
+// its first output row -> base[c] (base[n] = all rows), coordinates -> rows
+template <class ROWS>
+static int voxb_run(const VoxBatch &VB, const VoxBatchWs &W, const VoxBatchHost &H, const VoxGeom &G, int T, int F,
+                   int max_voxels, int32_t *nvox, int32_t *base, ROWS rows, float *voxels, int32_t *num_points,
+                   hipStream_t st) {
+  const int64_t total = VB.start[VB.n];
+  if (total == 0) return RSLO_OK;
+  int64_t maxP = 0;
+  for (int c = 0; c < VB.n; ++c)
+    if (VB.start[c + 1] - VB.start[c] > maxP) maxP = VB.start[c + 1] - VB.start[c];
+  RSLO_HIP(hipMemsetAsync(W.keys, 0xFF, H.fill_ff, st));       // keys | head
+  RSLO_HIP(hipMemsetAsync(W.first, 0x7F, H.fill_7f, st));      // first | cutoff
+  const dim3 grid((unsigned)rslo_cdiv(maxP, 256), (unsigned)VB.n);
+  hipLaunchKernelGGL(kb_vox_insert, grid, dim3(256), 0, st, VB, F, G, W);
+  hipLaunchKernelGGL(kb_vox_flags, grid, dim3(256), 0, st, VB, W);
+  RSLO_CHECK_LAUNCH(ROWS::insert_check);
+  if (int rc = scan_exclusive<false>(W.flags, W.pos, total, H.scan_ws, H.scan_bytes, nullptr, st)) return rc;
+  hipLaunchKernelGGL(kb_vox_bases, dim3(1), dim3(64), 0, st, VB, W, max_voxels, nvox, base);
+  hipLaunchKernelGGL(kb_vox_assign<ROWS>, grid, dim3(256), 0, st, VB, G, W, max_voxels, (const int32_t *)base, rows);
+  hipLaunchKernelGGL(kb_vox_fill, grid, dim3(256), 0, st, VB, F, T, W, (const int32_t *)base, voxels, num_points);
+  RSLO_CHECK_LAUNCH(ROWS::fill_check);
+  return RSLO_OK;
+}
+
+extern "C" size_t rslo_voxelize_ws_bytes(int64_t P) {
+  const int64_t p1 = P > 0 ? P : 1;
+  return voxb_ws_layout(1, &p1, nullptr, nullptr, nullptr, nullptr);
+}
+
+extern "C" int rslo_voxelize(const float *points, int64_t P, int F, const float *range6,
+                             const float *vsize3, const int32_t *grid_xyz, int T, int max_voxels,
+                             void *ws, size_t ws_bytes, float *voxels, int32_t *coords,
+                             int32_t *num_points, int32_t *d_nvox, void *stream) {
+  hipStream_t st = (hipStream_t)stream;
+  RSLO_CHECK_ARG(F >= 3 && T >= 1 && max_voxels >= 1, "voxelize: bad F/T/max_voxels");
+  // VoxBatch.start is int32: this bound is what keeps start[1] = P (and every point index) valid
+  RSLO_CHECK_ARG(P < (int64_t)2000000000, "voxelize: too many points");
+  {
+    int32_t d[3] = {grid_xyz[2], grid_xyz[1], grid_xyz[0]};
+    if (int rc = check_volume(1, d)) return rc;
+  }
+  {
+    // the four outputs are zero-filled; a caller that lays them out back to back (voxels | num_points | coords | d_nvox,
+    // as rslo_amd.capi does) gets ONE fill instead of four
+    const size_t bv = (size_t)max_voxels * T * F * sizeof(float), bn = (size_t)max_voxels * sizeof(int32_t),
+                 bc = (size_t)max_voxels * 3 * sizeof(int32_t);
+    char *v0 = (char *)voxels;
+    if ((char *)num_points == v0 + bv && (char *)coords == v0 + bv + bn && (char *)d_nvox == v0 + bv + bn + bc) {
+      RSLO_HIP(hipMemsetAsync(voxels, 0, bv + bn + bc + sizeof(int32_t), st));
+    } else {
+      RSLO_HIP(hipMemsetAsync(voxels, 0, bv, st));
+      RSLO_HIP(hipMemsetAsync(num_points, 0, bn, st));
+      RSLO_HIP(hipMemsetAsync(coords, 0, bc, st));
+      RSLO_HIP(hipMemsetAsync(d_nvox, 0, sizeof(int32_t), st));
+    }
+  }
+  if (P == 0) return RSLO_OK;
+  if (ws_bytes < rslo_voxelize_ws_bytes(P)) {
+    rslo_set_error("voxelize: workspace too small (%zu < %zu)", ws_bytes, rslo_voxelize_ws_bytes(P));
+    return RSLO_EWS;
+  }
+  VoxGeom G;
+  for (int j = 0; j < 3; ++j) {
+    G.lo[j] = range6[j];
+    G.vs[j] = vsize3[j];
+    G.g[j] = grid_xyz[j];
+  }
+  // a batch of one cloud
+  VoxBatch VB;
+  VoxBatchWs W;
+  VoxBatchHost H;
+  memset(&VB, 0, sizeof(VB));
+  voxb_ws_layout(1, &P, ws, &W, &VB, &H);
+  VB.n = VB.clouds_per_frame = 1;
+  VB.pts[0] = points;
+  // W.pre is a 256-byte slot with one word per cloud: behind the single word of this batch lie the two row bases (0, nvox)
+  return voxb_run(VB, W, H, G, T, F, max_voxels, d_nvox, W.pre + 1, ZyxRows{coords}, voxels, num_points, st);
 }
 
 static size_t plan_take(size_t &off, size_t bytes) {
@@ -1460,7 +1386,7 @@ extern "C" int rslo_plan_encoder_layout(const RsloEncoderSpec *spec, int n_cloud
   }
   if (pair_ws < 256) pair_ws = 256;
   lay->scratch_words = words;
-  lay->vox_ws_off = plan_take(off, voxb_ws_layout(n_clouds, h_n_points, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr));
+  lay->vox_ws_off = plan_take(off, voxb_ws_layout(n_clouds, h_n_points, nullptr, nullptr, nullptr, nullptr));
   lay->bitmap_off = lay->bitmap_level_off[0];      // (kept in the struct; the per-level bitmaps above are what is used)
   lay->prefix_off = plan_take(off, (size_t)words * 4);
   lay->scan_ws_off = plan_take(off, rslo_scan_ws_bytes(words));
@@ -1521,35 +1447,22 @@ extern "C" int rslo_plan_encoder(const RsloEncoderSpec *spec, const RsloPlanLayo
   {
     VoxBatch VB;
     VoxBatchWs W;
-    void *sws;
-    size_t sbytes, f_ff, f_7f;
+    VoxBatchHost H;
     memset(&VB, 0, sizeof(VB));
-    voxb_ws_layout(n_clouds, h_n_points, A + lay->vox_ws_off, &W, &VB, &sws, &sbytes, &f_ff, &f_7f);
+    voxb_ws_layout(n_clouds, h_n_points, A + lay->vox_ws_off, &W, &VB, &H);
     VB.n = n_clouds;
     VB.clouds_per_frame = clouds_per_frame;
-    int64_t maxP = 0;
+    int64_t total = 0;
     for (int c = 0; c < n_clouds; ++c) {
       VB.pts[c] = h_points[c];
       RSLO_CHECK_ARG(h_n_points[c] == 0 || h_points[c], "plan_encoder: null cloud");
-      if (h_n_points[c] > maxP) maxP = h_n_points[c];
+      total += h_n_points[c];
     }
-    const int64_t total = VB.start[n_clouds];
     RSLO_CHECK_ARG(total < (int64_t)2000000000, "plan_encoder: too many points");
-    if (total > 0) {
-      RSLO_HIP(hipMemsetAsync(W.keys, 0xFF, f_ff, st));       // keys | head
-      RSLO_HIP(hipMemsetAsync(W.first, 0x7F, f_7f, st));      // first | cutoff
-      const dim3 grid((unsigned)rslo_cdiv(maxP, 256), (unsigned)n_clouds);
-      hipLaunchKernelGGL(kb_vox_insert, grid, dim3(256), 0, st, VB, F, G, W);
-      hipLaunchKernelGGL(kb_vox_flags, grid, dim3(256), 0, st, VB, W);
-      RSLO_CHECK_LAUNCH("plan vox_insert");
-      if (int rc = scan_exclusive<false>(W.flags, W.pos, total, sws, sbytes, nullptr, st)) return rc;
-      // base + nvox <= level-0 capacity by construction: every cloud adds at most min(max_voxels, P) rows (layout)
-      hipLaunchKernelGGL(kb_vox_bases, dim3(1), dim3(64), 0, st, VB, W, spec->max_voxels, cnt);
-      hipLaunchKernelGGL(kb_vox_assign, grid, dim3(256), 0, st, VB, G, W, spec->max_voxels, (const int32_t *)cnt,
-                         coords_frame, coords0);
-      hipLaunchKernelGGL(kb_vox_fill, grid, dim3(256), 0, st, VB, F, T, W, (const int32_t *)cnt, voxels, num);
-      RSLO_CHECK_LAUNCH("plan vox_fill");
-    }
+    // base + nvox <= level-0 capacity by construction: every cloud adds at most min(max_voxels, P) rows (layout)
+    if (int rc = voxb_run(VB, W, H, G, T, F, spec->max_voxels, cnt + RSLO_PLAN_CNT_NVOX, cnt + RSLO_PLAN_CNT_BASE,
+                          PlanRows{coords_frame, coords0}, voxels, num, st))
+      return rc;
   }
   hipLaunchKernelGGL(kp_level0, dim3(1), dim3(RSLO_PLAN_MAX_CLOUDS + 1), 0, st, cnt, n_clouds);
   RSLO_CHECK_LAUNCH("plan level 0");

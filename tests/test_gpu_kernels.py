@@ -81,6 +81,102 @@ def test_host_voxelizer_equals_device_voxelizer(hip):
         assert (hv == dv.cpu().numpy()).all() and (hc == dc.cpu().numpy()).all() and (hn == dn.cpu().numpy()).all()
 
 
+EDGE_RANGE, EDGE_VS = [0, 0, 0, 8, 6, 3], [0.5, 0.5, 0.5]          # 16 x 12 x 6 voxels
+
+
+def _edge_pts(ids):
+    """One point per entry of ids at the centre of voxel ids[i] of the edge grid (x fastest); feature 3 = the index."""
+    ids = np.asarray(ids, np.int64)
+    xyz = np.stack([ids % 16, ids // 16 % 12, ids // 192], 1) * 0.5 + 0.25
+    return np.concatenate([xyz, np.arange(len(ids))[:, None]], 1).astype(np.float32)
+
+
+def _edge_cut_ids(maxv, k, extra):
+    """Point k opens the last new voxel: voxel number maxv - 1 (extra = False: no cutoff, the tail is still added) or
+    number maxv (extra = True: the reference loop breaks at k, the tail is not added).  In front of it the other voxels
+    in first-come order and points of them up to index k; behind it a tail of five points of voxels 0 and 1."""
+    n_pre = maxv if extra else maxv - 1
+    assert k >= n_pre
+    return list(range(n_pre)) + [j % n_pre for j in range(k - n_pre)] + [n_pre] + [0, 0, 0, 1, 1]
+
+
+def edge_clouds():
+    """(name, points, T, max_voxels) of test_voxelize_edges.  The oracle and the host library (rslo_host_voxelize), both
+    run on the CPU, return the same bits on every one of them: the oracle is unambiguous on these inputs."""
+    out = [("P=%d" % P, _edge_pts(range(P)), 5, 300) for P in (1, 255, 256, 257)]   # a launch block and its neighbours
+    outside = _edge_pts(range(300))
+    outside[:, 0] += np.where(np.arange(300) % 2, 8.0, -8.0).astype(np.float32)
+    out.append(("all outside", outside, 5, 300))
+    out.append(("300 in one voxel", _edge_pts([77] * 300), 5, 10))
+    for k in (None, 255, 256):
+        for extra in (False, True):
+            kk = (40 if extra else 39) if k is None else k
+            out.append(("cut k=%d extra=%d" % (kk, extra), _edge_pts(_edge_cut_ids(40, kk, extra)), 12, 40))
+    nan = _edge_pts(range(257))
+    nan[100, 0] = np.nan                      # a NaN coordinate fails both range comparisons: the point is dropped
+    out.append(("NaN x", nan, 5, 300))
+    return out
+
+
+def test_voxelize_edges(hip):
+    """Hand-built clouds at the launch-block, list-length and max_voxels edges, exact against the oracle.  The NaN row has
+    its NaN in x: the oracle and the host library both drop that point (they agree), so it is in."""
+    got = {name: _vox_both(hip, pts, EDGE_RANGE, EDGE_VS, T, maxv) for name, pts, T, maxv in edge_clouds()}
+    for P in (1, 255, 256, 257):
+        assert len(got["P=%d" % P][1]) == P
+    assert len(got["all outside"][1]) == 0
+    v, c, n = got["300 in one voxel"]
+    assert n.tolist() == [5] and v[0, :, 3].tolist() == [0, 1, 2, 3, 4] and c.tolist() == [[0, 4, 13]]
+    for k, pre in ((39, 0), (255, 6), (256, 6)):      # no cutoff: voxel 0 gets its one + pre points and the tail's three
+        v, c, n = got["cut k=%d extra=0" % k]
+        assert len(c) == 40 and int(n[0]) == 1 + pre + 3 and int(n[39]) == 1 and float(v[39, 0, 3]) == k
+    for k, pre in ((40, 0), (255, 6), (256, 6)):      # the break at k: nothing behind it is added
+        v, c, n = got["cut k=%d extra=1" % k]
+        assert len(c) == 40 and int(n[0]) == 1 + pre and float(v[:, :, 3].max()) < k
+    assert len(got["NaN x"][1]) == 256
+
+
+def test_plan_voxelizer_equals_single_cloud_calls(hip):
+    """Level 0 of ONE rslo_plan_encoder call over four clouds (257, 0, 1 and 300 points; the last one hits the max_voxels
+    break) is, to the bit, the concatenation of four rslo_voxelize calls: both run the same kernels."""
+    T, maxv, F = 3, 280, 4
+    clouds = [_edge_pts(list(range(200)) + list(range(57))), _edge_pts([]), _edge_pts([500]),
+              _edge_pts(list(range(285)) + [0] * 15)]
+    g = O.grid_size(EDGE_RANGE, EDGE_VS)
+    sp = hip.EncoderSpec()
+    sp.n_levels, sp.max_points, sp.max_voxels, sp.n_features = 1, T, maxv, F
+    for j in range(3):
+        sp.dims0[j], sp.grid_xyz[j], sp.vsize3[j] = int(g[2 - j]), int(g[j]), EDGE_VS[j]
+    for j in range(6):
+        sp.range6[j] = EDGE_RANGE[j]
+    lay = hip.plan_encoder_layout(sp, [len(p) for p in clouds])
+    arena = torch.zeros((int(lay.total_bytes),), dtype=torch.uint8, device="cuda")
+    counts = torch.zeros((hip.PLAN_CNT_WORDS,), dtype=torch.int32).pin_memory()
+    hip.plan_encoder(sp, lay, [dev(p) for p in clouds], 2, arena, counts)
+    torch.cuda.synchronize()
+    cnt = counts.numpy()
+    single = [hip.voxelize(dev(p), EDGE_RANGE, EDGE_VS, g, T, maxv) for p in clouds]
+    nv = [int(s[3].item()) for s in single]
+    assert nv == [200, 0, 1, 280]
+    assert cnt[hip.PLAN_CNT_NVOX:hip.PLAN_CNT_NVOX + 4].tolist() == nv and int(cnt[hip.PLAN_CNT_ROWS]) == sum(nv)
+    assert cnt[hip.PLAN_CNT_BOFF:hip.PLAN_CNT_BOFF + 5].tolist() == np.cumsum([0] + nv).tolist()
+    rows = sum(nv)
+
+    def section(off, count, dtype):
+        return arena[int(off):int(off) + 4 * count].view(dtype).cpu().numpy()
+
+    def cat(i, dtype):
+        return np.concatenate([s[i][:m].cpu().numpy() for s, m in zip(single, nv)]).astype(dtype)
+
+    assert (section(lay.voxels_off, rows * T * F, torch.float32).reshape(rows, T, F) == cat(0, np.float32)).all()
+    assert (section(lay.num_points_off, rows, torch.int32) == cat(2, np.int32)).all()
+    cloud = np.repeat(np.arange(4), nv)
+    coords = section(lay.coords_off[0], rows * 4, torch.int32).reshape(rows, 4)
+    assert (coords[:, 1:] == cat(1, np.int32)).all() and (coords[:, 0] == cloud).all()
+    frame = section(lay.coords_frame_off, rows * 4, torch.int32).reshape(rows, 4)
+    assert (frame[:, 1:] == coords[:, 1:]).all() and (frame[:, 0] == cloud % 2).all()
+
+
 # ------------------------------------------------------------------------------- rulebooks
 def _encoder_levels(hip, coords, batch, dims):
     """Runs the rulebook chain of SpMiddleFHDWithCov2_3 on both sides; yields per-level data."""
